@@ -14,13 +14,25 @@ sharded over ranks.  Default = weak scaling, 2048 cells per GPU (configs[3], 163
 of a cell of the 1-GPU point: `cell_epochs_per_s` is reported next to `value` for that reason.
 `--scaling strong --total-cells N` keeps the workload fixed (N cells in total at every GPU count).
 
-After the timed region the outputs of the last step are verified (driver.verify_outputs:
-contact conservation per interval, per-cell targets, occupancy, device status): `"checked": true`.
+A plain run sets up, warms up, times the steps, writes the outputs of the last step if
+`--dump-outputs DIR` is given, and prints its line.  `--full` adds what the headline figure does
+not need: after the timed region the outputs of the last step are verified (driver.verify_outputs:
+contact conservation per interval, per-cell targets, occupancy, device status): `"checked": true`;
+and, on one GPU, the CPU baseline is timed.
 
 Prints ONE JSON line on rank 0 (contract in the task statement): metric = simulated
 genome-cells/s (whole job), plus `roofline` (algorithmic HBM bytes of the simulation kernel over
-its HIP-event duration, against 8 TB/s) and `cpu_baseline` (the CPU oracle timed on the host
-cores over a bounded sample of the same workload; N = 1 only).
+its HIP-event duration, against 8 TB/s) and, with `--full`, `cpu_baseline` (the CPU oracle timed
+on the host cores over a bounded sample of the same workload; N = 1 only).
+
+`--dump-outputs DIR` (rank 0) writes what the last timed step computed, as float64 .npy files
+(at most DUMP_BUDGET_BYTES in all; the inputs depend on the arguments only, so two builds can be
+compared file for file):
+  contacts.npy   band-matrix words of every simulated interval, concatenated in plan order --
+                 a fixed, seeded sample of them (sorted flat indices) when there are more than
+                 DUMP_MAX_CONTACTS
+  occupancy.npy  1-D LEF occupancy track of every simulated interval, concatenated in plan order
+  cells.npy      one row per (interval, cell) task: CELL_FIELDS, each PRNG word as two 32-bit halves
 """
 import argparse
 import json
@@ -32,6 +44,15 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+
+# --dump-outputs: at most 4 Mi matrix words + 1 Mi occupancy bins + 64 Ki cell rows of 15 float64s (~48 MB)
+DUMP_MAX_CONTACTS = 1 << 22
+DUMP_MAX_OCCUPANCY = 1 << 20
+DUMP_MAX_CELLS = 1 << 16
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SEED = 20240607
+CELL_FIELDS = ("epochs", "burnin_epochs", "num_contacts", "raws_consumed", "sum_active_lefs", "sampling_events",
+               "sim_epochs")
 
 
 def launch_mode(info):
@@ -121,9 +142,60 @@ def parse_args():
                     help="deadline of one launch in seconds, single-GPU and distributed paths alike: past "
                          "it the launch is aborted (modle_hip_set_wait_timeout: the abort word is raised, "
                          "the kernel drains) and the job fails instead of hanging the box")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the self-check of the last step's "
+                         "outputs and, on one GPU, the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-sample-cells", type=int, default=None)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the outputs of the last timed step to DIR/<name>.npy (float64)")
     return ap.parse_args()
+
+
+def dump_sample(total, cap, salt):
+    """sorted flat indices of the words of an output of `total` words that --dump-outputs writes: all of
+    them up to `cap`, else a fixed, seeded sample of at most `cap` (the same for every run and build)"""
+    import numpy as np
+
+    if total <= cap:
+        return np.arange(total, dtype=np.int64)
+    rng = np.random.default_rng([DUMP_SEED, salt])
+    return np.unique(rng.integers(0, total, size=cap, dtype=np.int64))
+
+
+def dump_outputs(out_dir, tensors, last_results):
+    """--dump-outputs: the last step's band matrices, occupancy tracks and per-cell results as float64
+    arrays (module docstring).  `tensors[k]`: (matrix words, occupancy) of plan entry k or None;
+    `last_results[k]`: the CellResults of plan entry k's tasks in the last step."""
+    import numpy as np
+    import torch
+
+    live = [t for t in tensors if t is not None]
+    # the matrix tensors hold nrows * ncols words and one more: the band matrix is the first nrows * ncols
+    sizes = [t[0].numel() - 1 for t in live]
+    offsets = np.concatenate([[0], np.cumsum(sizes, dtype=np.int64)])
+    pick = dump_sample(int(offsets[-1]), DUMP_MAX_CONTACTS, 1)
+    contacts = []
+    for k, (c, _) in enumerate(live):
+        lo, hi = np.searchsorted(pick, [offsets[k], offsets[k + 1]])
+        if hi > lo:
+            idx = torch.from_numpy(pick[lo:hi] - offsets[k]).to(c.device)
+            words = c.index_select(0, idx).to(torch.int64) & 0xFFFFFFFF  # (uint32 words in an int32 tensor)
+            contacts.append(words.cpu().numpy())
+    occupancy = np.concatenate([t[1].cpu().numpy() for t in live]) if live else np.zeros(0, np.int64)
+    occupancy = occupancy[dump_sample(occupancy.size, DUMP_MAX_OCCUPANCY, 2)]
+    rows = [[getattr(r, f) for f in CELL_FIELDS]
+            + [w for x in r.prng_final for w in (x >> 32, x & 0xFFFFFFFF)]
+            for res in last_results for r in res]
+    cells = np.array(rows, dtype=np.float64).reshape(len(rows), len(CELL_FIELDS) + 8)
+    cells = cells[dump_sample(len(cells), DUMP_MAX_CELLS, 3)]
+    arrays = {"contacts": np.concatenate(contacts) if contacts else np.zeros(0),
+              "occupancy": occupancy, "cells": cells}
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float64) for name, a in arrays.items()}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def usable_cores():
@@ -357,7 +429,7 @@ def main():
             if t is not None:
                 t[0].zero_()
                 t[1].zero_()
-        if last:
+        if last and args.full:
             check["missed_before"] = driver.read_missed(sim, ids)
             check["matrix"] = [None] * len(tensors)
             check["occ"] = [None] * len(tensors)
@@ -394,7 +466,7 @@ def main():
                         os._exit(1)
                     time.sleep(0.0005)
                 with torch.cuda.stream(reduce_stream):
-                    if last:
+                    if last and args.full:
                         own_sums(k)
                     if args.dist_backend == "nccl":
                         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
@@ -448,7 +520,7 @@ def main():
         first = False
     sync()
     dt = time.perf_counter() - t0
-    if not use_dist:
+    if not use_dist and args.full:
         for k, t in enumerate(tensors):  # verify_after_timing: the last step's outputs, untouched since
             if t is not None:
                 check["matrix"][k] = t[0].sum(dtype=torch.int64)
@@ -466,12 +538,14 @@ def main():
     epochs = 0
     lef_epochs = 0  # sum over cells and simulated epochs of the active LEFs
     longest = 0  # epochs of the longest cell: a launch with fewer tasks than wave slots lasts as long as it does
+    last_results = []
     for entry, iid in zip(plan, ids):
         if iid is None:
             continue
         res = sim.results(iid)
         k = len(entry["tasks"])
         last = res[len(res) - k:]
+        last_results.append(last)
         step_bytes += driver.algorithmic_bytes(last, len(entry["interval"]["bar_pos"]),
                                                bool(cfg.track_1d_lef_position))
         epochs += sum(r.epochs for r in last)
@@ -486,16 +560,21 @@ def main():
     avg_kernel_s = (sum(timed) / len(timed)) / 1e3 if timed else None
     achieved = step_bytes / avg_kernel_s / 1e9 if avg_kernel_s else None
 
-    # verify the outputs of the last step (every rank checks its own shard; a violation raises
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, tensors, last_results)
+
+    # --full: verify the outputs of the last step (every rank checks its own shard; a violation raises
     # and fails the job: the number printed below comes from a launch whose results were looked at)
-    missed_after = driver.read_missed(sim, ids)
-    missed_delta = [None if a is None else a - b for a, b in zip(missed_after, check["missed_before"])]
-    msum = [None if x is None else int(x.item()) for x in check["matrix"]]
-    osum = [None if x is None else int(x.item()) for x in check["occ"]]
-    if os.environ.get("MODLE_BENCH_NO_VERIFY", "") not in ("", "0"):
+    if not args.full:
+        verified = {"skipped": "plain run (the self-check runs with --full)"}
+    elif os.environ.get("MODLE_BENCH_NO_VERIFY", "") not in ("", "0"):
         # (measurement builds that leave the output increments out: profiles/r05*/write_accounting.txt)
         verified = {"skipped": "MODLE_BENCH_NO_VERIFY"}
     else:
+        missed_after = driver.read_missed(sim, ids)
+        missed_delta = [None if a is None else a - b for a, b in zip(missed_after, check["missed_before"])]
+        msum = [None if x is None else int(x.item()) for x in check["matrix"]]
+        osum = [None if x is None else int(x.item()) for x in check["occ"]]
         verified = driver.verify_outputs(sim, cfg, plan, ids, msum, missed_delta, osum)
     if use_dist:
         import torch.distributed as dist
@@ -606,7 +685,7 @@ def main():
             out["multi_gpu"]["reduce_ms_per_rank"] = reduce_ms_per_rank
             out["multi_gpu"]["ranks"] = [{"host": h, "device": i, "uuid": u} for h, u, i in everyone]
             out["multi_gpu"]["backend"] = "RCCL" if args.dist_backend == "nccl" else "gloo (rehearsal)"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, genome, unit, args.cpu_sample_cells)
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(out) + "\n").encode())

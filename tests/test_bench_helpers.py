@@ -96,3 +96,40 @@ def test_the_committed_traffic_figure_is_of_the_committed_kernel():
     if stale:
         # (not a failure of the code: the line will say `traffic: null` until the profile round is run again)
         pytest.skip(f"profiles/traffic.json is stale for {stale}: re-run tools/profile_round.sh + tools/assemble_profile.py")
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs: every word of a small output, a seeded sample (the same in every run) of a large one"""
+    import numpy as np
+
+    assert np.array_equal(bench.dump_sample(5, 8, 1), np.arange(5))
+    a, b = bench.dump_sample(10**9, 1000, 1), bench.dump_sample(10**9, 1000, 1)
+    assert np.array_equal(a, b) and 0 < len(a) <= 1000
+    assert np.all(np.diff(a) > 0) and a[0] >= 0 and a[-1] < 10**9
+    assert not np.array_equal(a, bench.dump_sample(10**9, 1000, 2))
+
+
+def test_dump_outputs_writes_the_last_step_as_float64(tmp_path):
+    """the files --dump-outputs writes, from host tensors of the layout bench.py allocates on the device
+    (nrows * ncols matrix words + one, occupancy per column; a skipped interval has no tensors)"""
+    import numpy as np
+    import torch
+
+    from modle_amd.params import CellResult
+
+    c0 = torch.arange(7, dtype=torch.int32)
+    c0[2] = -1  # a uint32 word above 2^31
+    o0 = torch.tensor([4, 0, 2], dtype=torch.int64)
+    c1 = torch.tensor([9, 8, 0], dtype=torch.int32)
+    o1 = torch.tensor([6], dtype=torch.int64)
+    r = CellResult(epochs=10, burnin_epochs=3, num_contacts=5, raws_consumed=99, sum_active_lefs=70,
+                   sampling_events=8, sim_epochs=7)
+    r.prng_final[0] = (1 << 63) | 5
+    bench.dump_outputs(str(tmp_path / "out"), [(c0, o0), None, (c1, o1)], [[r], [r, r]])
+    got = {n: np.load(tmp_path / "out" / f"{n}.npy") for n in ("contacts", "occupancy", "cells")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["contacts"].tolist() == [0, 1, 2**32 - 1, 3, 4, 5, 9, 8]
+    assert got["occupancy"].tolist() == [4, 0, 2, 6]
+    assert got["cells"].shape == (3, len(bench.CELL_FIELDS) + 8)
+    assert got["cells"][0, :7].tolist() == [10, 3, 5, 99, 70, 8, 7]
+    assert got["cells"][0, 7:9].tolist() == [2**31, 5] and got["cells"][0, 9:].tolist() == [0] * 6

@@ -249,7 +249,7 @@ def test_bench_runs_under_torch_distributed_run_with_one_rank(tmp_path):
     out = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
          "--master-addr", "127.0.0.1", "--master-port", "29517", os.path.join(root, "bench.py"),
-         "--gpus", "1", "--steps", "2", "--warmup", "1", "--cells", "16", "--no-cpu-baseline"],
+         "--gpus", "1", "--steps", "2", "--warmup", "1", "--cells", "16", "--full", "--no-cpu-baseline"],
         capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -280,12 +280,53 @@ def _bench(tmp_path, nproc, port, extra):
         cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc),
                 "--master-addr", "127.0.0.1", "--master-port", str(port)]
     cmd += [os.path.join(root, "bench.py"), "--gpus", str(nproc), "--steps", "2", "--warmup", "1",
-            "--no-cpu-baseline", "--checksum-out", sums] + extra
+            "--full", "--no-cpu-baseline", "--checksum-out", sums] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
     with open(sums) as f:
         return json.loads(line), json.load(f)
+
+
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path):
+    """A plain bench.py run (no --full) times its steps and prints the headline without the self-check or the
+    CPU baseline; --dump-outputs writes the last step's outputs, the same in two runs with the same arguments,
+    and they agree with the --checksum-out sums of the same step."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for i in range(2):
+        dump, sums = tmp_path / f"dump{i}", tmp_path / f"sums{i}.json"
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2",
+                              "--warmup", "1", "--cells", "16", "--dump-outputs", str(dump), "--checksum-out",
+                              str(sums)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = out.stdout.splitlines()
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        with open(sums) as f:
+            runs.append((d, {n: np.load(dump / f"{n}.npy") for n in ("contacts", "occupancy", "cells")},
+                         json.load(f)))
+    d, arrays, sums = runs[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 16 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert "cpu_baseline" not in d and d["checked"] is False
+    assert all(a.dtype == np.float64 for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert arrays["cells"].shape == (24 * 16, 15)
+    assert arrays["occupancy"].sum() == sum(v[2] for v in sums.values()) > 0
+    assert 0 < arrays["contacts"].size <= 1 << 22 and arrays["contacts"].sum() > 0
+    for k in ("contacts", "occupancy", "cells"):
+        assert np.array_equal(arrays[k], runs[1][1][k]), k
+    assert sums == runs[1][2]
 
 
 def test_bench_with_two_real_ranks_reduces_to_the_single_rank_matrices(tmp_path):

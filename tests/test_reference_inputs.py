@@ -1,9 +1,8 @@
 """The importer and the task generation on the reference's REAL inputs.
 
-`/root/reference/examples/data/hg38.chrom.sizes` and `hg38_extrusion_barriers.bed.xz` (the inputs of
-the reference's README run and of BASELINE configs 1-4) exist in the build container only and are
-never copied: these tests read them where they lie and skip everywhere else (the GPU box has no
-/root/reference).  They pin
+`tests/golden/hg38.chrom.sizes` and `tests/golden/hg38_extrusion_barriers.bed.xz` are the reference's
+example data, unchanged (examples/data/: the inputs of the reference's README run and of BASELINE
+configs 1-4).  These tests pin
 
 * `modle_genome_import` on the real files: 24 chromosomes, 38 815 barriers (19 666 `+` / 19 149 `-`),
   chr1 3 518, occupancies within [0.60, 1.00], sum of `compute_num_lefs` 61 766 -- the figures
@@ -24,12 +23,9 @@ import pytest
 from modle_amd import api, driver, genome, synthetic
 from modle_amd.params import DIR_FWD, DIR_REV
 
-DATA = "/root/reference/examples/data"
+DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 SIZES = os.path.join(DATA, "hg38.chrom.sizes")
 BARRIERS = os.path.join(DATA, "hg38_extrusion_barriers.bed.xz")
-
-pytestmark = pytest.mark.skipif(not (os.path.exists(SIZES) and os.path.exists(BARRIERS)),
-                                reason="the reference's example data is not here (build container only)")
 
 
 @pytest.fixture(scope="module")

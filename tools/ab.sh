@@ -4,6 +4,7 @@
 # per cent or two slower than the first whatever it runs (clocks), which is more than most of the
 # differences this script is asked about.
 R=$GRAFT_REPO_ROOT; N=$1; shift
+AB_BENCH_ARGS="--full $AB_BENCH_ARGS"  # (the `checked` column: the self-check runs with --full only)
 for r in $(seq 1 $N); do
   if [ $((r % 2)) -eq 1 ]; then order="$@"; else order=$(echo "$@" | tr ' ' '\n' | tac | tr '\n' ' '); fi
   for v in $order; do
