@@ -15,15 +15,15 @@ u32p = np.ctypeslib.ndpointer(dtype=np.uint32, flags="C_CONTIGUOUS")
 
 def simulate_interval(cfg, start, end, bar_pos, bar_dir, stp_active, stp_inactive, tasks, nrows,
                       ncols, track_occupancy=True, variant=None):
-    from phase_backend import emu_size_class
+    from phase_backend import WIDE_VARIANT, emu_size_class
 
     # MODLE_EMU_VARIANT=w12: campaigns on the geometry of the 12-wave kernels (tools/emu_fuzz_campaign.py)
     if variant is None and os.environ.get("MODLE_EMU_VARIANT"):
         variant = os.environ["MODLE_EMU_VARIANT"]
 
     # the size class the product would run these cells in (NARROW builds refuse WIDE set-ups)
-    if variant in (None, "philox") and emu_size_class(cfg, max(int(t.num_lefs) for t in tasks)) != 0:
-        variant = "wide" if variant is None else "philox_wide"
+    if variant in WIDE_VARIANT and emu_size_class(cfg, max(int(t.num_lefs) for t in tasks)) != 0:
+        variant = WIDE_VARIANT[variant]
     L = emu_lib(variant)
     L.emu_simulate_interval.argtypes = [C.POINTER(Config), C.c_uint64, C.c_uint64, u64p, u8p,
                                         f64p, f64p, C.c_size_t, C.POINTER(Task), C.c_size_t,

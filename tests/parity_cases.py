@@ -111,9 +111,15 @@ CASES = {
 }
 
 
-def build_case(name):
+def build_case(name, num_cells=None):
+    """`num_cells`: the case with that many cells of the same kind (the target contact density, which the cells
+    share, grows with their number: every cell keeps the share of contacts, and so the length, it has in CASES)"""
     spec = CASES[name]
-    cfg = api.make_config(**spec["cfg"])
+    kw = dict(spec["cfg"])
+    if num_cells is not None and num_cells != kw["num_cells"]:
+        kw["target_contact_density"] = kw["target_contact_density"] * num_cells / kw["num_cells"]
+        kw["num_cells"] = num_cells
+    cfg = api.make_config(**kw)
     if "window" in spec:
         # barriers only where the window is (a genome-scale barrier set is not needed)
         start, end = spec["window"]
@@ -154,20 +160,75 @@ def assert_same_outputs(a, b, what):
         assert np.array_equal(oa, ob), f"{what}: 1-D occupancy differs"
 
 
-def launch_modes():
-    """The two ways the kernel runs a cell (MODLE_HIP_PAIRED, read at every launch): "0" one wave
-    per cell, "1" a main wave and its helper (modle_amd/csrc/sim_pair.h).  Left alone the library
-    picks by the number of tasks, so a parity test states the mode and runs both: yields the mode
-    with the variable set, and restores it."""
+_MODE_VARIABLES = ("MODLE_HIP_PAIRED", "MODLE_HIP_WAVES", "MODLE_HIP_GRID")
+
+
+def launch_modes(n_tasks=None):
+    """The ways the library runs a cell that a parity test states by name (the variables are read at every
+    launch; left alone the library picks by the number of tasks, and every launch these tests make is small
+    enough for it to pick the same thing):
+
+    "0"         one wave per cell                                       MODLE_HIP_PAIRED=0
+    "1"         a main wave and its helper (modle_amd/csrc/sim_pair.h)  MODLE_HIP_PAIRED=1 (the 8-wave kernels)
+    "12"        the 12-wave kernels, one workgroup per CU               MODLE_HIP_PAIRED=0 MODLE_HIP_WAVES=12
+    "12packed"  the 12-wave kernels the way a launch that fills the     ... and MODLE_HIP_GRID=max(1, n_tasks // 12)
+                GPU runs them: every one of a workgroup's twelve waves
+                simulates a cell at once, side by side in one LDS block
+
+    "12packed" needs the number of tasks of the launch: without `n_tasks`, or with fewer than 12 tasks (no
+    workgroup could be filled), the first three modes are yielded.
+    Yields the label with the variables set, and restores every one of them.  The caller reads
+    `Simulator.launch_info()` after the launch and hands it to `assert_launch_mode`."""
     import os
 
-    old = os.environ.get("MODLE_HIP_PAIRED")
+    modes = [("0", {"MODLE_HIP_PAIRED": "0"}),
+             ("1", {"MODLE_HIP_PAIRED": "1"}),
+             ("12", {"MODLE_HIP_PAIRED": "0", "MODLE_HIP_WAVES": "12"})]
+    if n_tasks is not None and int(n_tasks) >= 12:
+        modes.append(("12packed", {"MODLE_HIP_PAIRED": "0", "MODLE_HIP_WAVES": "12",
+                                   "MODLE_HIP_GRID": str(max(1, int(n_tasks) // 12))}))
+    old = {name: os.environ.get(name) for name in _MODE_VARIABLES}
+
+    def restore(names):
+        for name in names:
+            if old[name] is None:
+                os.environ.pop(name, None)
+            else:
+                os.environ[name] = old[name]
+
     try:
-        for mode in ("0", "1"):
-            os.environ["MODLE_HIP_PAIRED"] = mode
-            yield mode
+        for label, env in modes:
+            # a variable the mode does not name keeps the value the run was started with
+            restore(name for name in _MODE_VARIABLES if name not in env)
+            os.environ.update(env)
+            yield label
     finally:
-        if old is None:
-            os.environ.pop("MODLE_HIP_PAIRED", None)
-        else:
-            os.environ["MODLE_HIP_PAIRED"] = old
+        restore(_MODE_VARIABLES)
+
+
+def describe_launch(info):
+    """one line of a test's output that names the kernel of a launch (`pytest -s` / `-rP` shows it)"""
+    return (f"modle_simulate_cells_{'wide' if info['size_class'] else 'narrow'}"
+            f"{'12' if info['waves_per_workgroup'] == 12 else ''}: {info['n_tasks']} tasks, {info['workgroups']} workgroups "
+            f"x {info['main_waves_per_workgroup']} main waves of {info['waves_per_workgroup']}, helper waves "
+            f"{info['helper_waves']}")
+
+
+def assert_launch_mode(info, label, n_tasks):
+    """`Simulator.launch_info()` of a launch made under mode `label` of `launch_modes`: the kernel the label names
+    is the kernel that ran (a variable the library ignores must not let the comparison pass on another one)"""
+    what = f"launch mode {label}, {n_tasks} tasks: {info}"
+    assert info["n_tasks"] == n_tasks, what
+    if label == "0":
+        assert info["helper_waves"] == 0, what
+    elif label == "1":
+        assert info["helper_waves"] == 1 and info["waves_per_workgroup"] == 8, what
+    elif label in ("12", "12packed"):
+        assert info["waves_per_workgroup"] == 12 and info["helper_waves"] == 0, what
+        assert info["main_waves_per_workgroup"] == 12, what
+        if label == "12packed":
+            # every workgroup has a cell for each of its twelve waves when the launch starts
+            assert info["workgroups"] == min(info["num_cus"], n_tasks // 12), what
+            assert info["workgroups"] * 12 <= n_tasks, what
+    else:
+        raise AssertionError(f"unknown launch mode {label!r}")

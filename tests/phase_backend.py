@@ -112,6 +112,9 @@ def _advance(state, n):
 
 _emu = None
 _emu_variants = {}
+# NARROW build -> the build of the same geometry / generator policy in the WIDE size class (None: the default
+# build, the geometry of the 8-wave kernels; "w12": that of the 12-wave kernels)
+WIDE_VARIANT = {None: "wide", "philox": "philox_wide", "w12": "w12_wide"}
 
 
 def emu_lib(variant=None):
@@ -159,10 +162,14 @@ def _declare_phases(L):
     return L
 
 
-def emu_phases(cfg, mask, st, state, skip):
-    L = emu_lib()
+def emu_phases(cfg, mask, st, state, skip, geometry=None):
+    """geometry: None = the build with the geometry of the 8-wave kernels, "w12" = of the 12-wave kernels
+    (functools.partial(emu_phases, geometry="w12") is a backend like emu_phases itself)"""
+    assert geometry in (None, "w12"), geometry
     if emu_size_class(cfg, st.n, (st.rev_moves, st.fwd_moves)) != 0:
-        L = _declare_phases(emu_lib("wide"))
+        L = _declare_phases(emu_lib(WIDE_VARIANT[geometry]))
+    else:
+        L = emu_lib() if geometry is None else _declare_phases(emu_lib(geometry))
     prng = (C.c_uint64 * 4)(*_advance(state, skip))
     consumed = C.c_uint64(0)
     rc = L.emu_test_phases(C.byref(cfg), mask, st.start, st.end, st.n, st.rev_pos, st.fwd_pos,

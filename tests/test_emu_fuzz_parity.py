@@ -1,5 +1,7 @@
 """The same differential test as tests/test_gpu_fuzz_parity.py with the device code running under
-the CPU lane emulator (one cell per set-up: the emulator is slow)."""
+the CPU lane emulator (one cell per set-up: the emulator is slow), in the emulator builds with the
+geometry of the 8-wave kernels and with that of the 12-wave ones (a set-up of the WIDE size class
+resolves to the WIDE build of the same geometry, emu_sim.simulate_interval)."""
 import pytest
 
 import emu_sim
@@ -12,28 +14,55 @@ from parity_cases import assert_same_outputs, assert_same_results
 # initialise their counts: a read-modify-write of LDS across lanes without a barrier in between.  The GPU
 # executes a wave's LDS operations in order and never saw it; the emulator runs the lanes one after the
 # other and crashed in the release that followed the broken rank order)
-@pytest.mark.parametrize("seed", [100, 101, 105, 108, 1148, 790172])
+SEEDS_V1 = [100, 101, 105, 108, 1148, 790172]
+SEEDS_V2 = [4, 5, 6, 8]
+SEEDS_V3 = [1, 2, 3, 4, 5, 6]
+SEEDS_V4 = [3, 7, 11, 36, 52]
+
+
+@pytest.mark.parametrize("seed", SEEDS_V1)
 def test_emulated_device_code_matches_oracle_on_random_setups(oracle, seed):
     _compare(oracle, random_case(seed), f"seed {seed}")
 
 
-@pytest.mark.parametrize("seed", [4, 5, 6, 8])
+@pytest.mark.parametrize("seed", SEEDS_V2)
 def test_emulated_device_code_matches_oracle_on_random_setups_v2(oracle, seed):
     _compare(oracle, random_case_v2(seed), f"v2 seed {seed}")
 
 
-@pytest.mark.parametrize("seed", [1, 2, 3, 4, 5, 6])
+@pytest.mark.parametrize("seed", SEEDS_V3)
 def test_emulated_device_code_matches_oracle_on_random_setups_v3(oracle, seed):
     _compare(oracle, random_case_v3(seed), f"v3 seed {seed}")
 
 
-@pytest.mark.parametrize("seed", [3, 7, 11, 36, 52])
+@pytest.mark.parametrize("seed", SEEDS_V4)
 def test_emulated_device_code_matches_oracle_on_random_setups_v4(oracle, seed):
     """burn-in parameters, stopping rules, zero release probabilities (fuzz_cases.random_case_v4)"""
     _compare(oracle, random_case_v4(seed), f"v4 seed {seed}")
 
 
-def _compare(oracle, case, label):
+# --- the same seeds with the geometry of the 12-wave kernels ------------------------------------
+@pytest.mark.parametrize("seed", SEEDS_V1)
+def test_emulated_12_wave_geometry_matches_oracle_on_random_setups(oracle, seed):
+    _compare(oracle, random_case(seed), f"12-wave geometry, seed {seed}", variant="w12")
+
+
+@pytest.mark.parametrize("seed", SEEDS_V2)
+def test_emulated_12_wave_geometry_matches_oracle_on_random_setups_v2(oracle, seed):
+    _compare(oracle, random_case_v2(seed), f"12-wave geometry, v2 seed {seed}", variant="w12")
+
+
+@pytest.mark.parametrize("seed", SEEDS_V3)
+def test_emulated_12_wave_geometry_matches_oracle_on_random_setups_v3(oracle, seed):
+    _compare(oracle, random_case_v3(seed), f"12-wave geometry, v3 seed {seed}", variant="w12")
+
+
+@pytest.mark.parametrize("seed", SEEDS_V4)
+def test_emulated_12_wave_geometry_matches_oracle_on_random_setups_v4(oracle, seed):
+    _compare(oracle, random_case_v4(seed), f"12-wave geometry, v4 seed {seed}", variant="w12")
+
+
+def _compare(oracle, case, label, variant=None):
     cfg, chrom = case["cfg"], case["chrom"]
     tasks = api.slice_tasks(case["tasks"], 0, 1)
     track = bool(cfg.track_1d_lef_position)
@@ -42,7 +71,7 @@ def _compare(oracle, case, label):
         case["stp_active"], case["stp_inactive"], tasks, nthreads=1, track_occupancy=track)
     ec, em, eo, eres = emu_sim.simulate_interval(
         cfg, chrom["start"], chrom["end"], chrom["bar_pos"], chrom["bar_dir"], case["stp_active"],
-        case["stp_inactive"], tasks, case["nrows"], case["ncols"], track_occupancy=track)
+        case["stp_inactive"], tasks, case["nrows"], case["ncols"], track_occupancy=track, variant=variant)
     what = f"{label}: {case['kw']}, size {case['size']}"
     assert_same_results(ores, eres, what)
     assert_same_outputs((oc, om, oo), (ec, em, eo), what)

@@ -25,7 +25,7 @@ REGIMES = (["120000000", "1", "1", "20", "25000", "0", "0.002"],
 def builds():
     """the sanitizer builds, side by side (a minute each)"""
     procs = {t: subprocess.Popen(["make", "-C", EMU, t], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-             for t in ("msan_emu", "asan_emu", "tsan_emu", "tsan_emu_philox", "tsan_emu_w12")}
+             for t in ("msan_emu", "asan_emu", "asan_emu_w12", "tsan_emu", "tsan_emu_philox", "tsan_emu_w12")}
     return {t: (p.communicate()[0], p.returncode) for t, p in procs.items()}
 
 
@@ -49,6 +49,14 @@ def test_whole_cells_under_address_and_undefined_behaviour_sanitizers(builds):
     out, rc = builds["asan_emu"]
     assert rc == 0, out[-2000:]
     run_regimes(os.path.join(EMU, "asan_emu"), ("Sanitizer", "runtime error"))
+
+
+def test_whole_cells_with_the_geometry_of_the_12_wave_kernels_under_address_sanitizer(builds):
+    """the same regimes with -DMODLE_WAVES_PER_CU=12: the halved LDS key buffers and PRNG blocks of the 12-wave
+    kernels (the first regime re-inserts more units per epoch than they hold)"""
+    out, rc = builds["asan_emu_w12"]
+    assert rc == 0, out[-2000:]
+    run_regimes(os.path.join(EMU, "asan_emu_w12"), ("Sanitizer", "runtime error"))
 
 
 @pytest.mark.skipif(not os.path.exists(CLANG), reason="needs clang++ with ThreadSanitizer")

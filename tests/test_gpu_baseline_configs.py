@@ -19,6 +19,10 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+# deadline of every launch of this file (the full launches take seconds): a kernel that stops making
+# progress ends with MODLE_HIP_ERR_TIMEOUT instead of holding the GPU
+WAIT_TIMEOUT_S = 300.0
+
 CONFIGS = {
     # configs[2]: whole GRCh38 + default barriers, 2048 cells, defaults, 1 GPU
     "config2_grch38_2048": dict(cfg=dict(num_cells=2048, seed=0), world=1),
@@ -52,6 +56,7 @@ def _launch(cfg, plan):
     sim = api.Simulator(cfg, 0)
     ids = driver.enqueue_plan(sim, cfg, plan, buffers)
     torch.cuda.synchronize(dev)
+    sim.set_wait_timeout(WAIT_TIMEOUT_S)
     sim.launch(torch.cuda.current_stream(dev).cuda_stream)
     sim.wait()  # raises if any task reports a non-zero device status
     return sim, ids, tensors, driver.read_missed(sim, ids)
@@ -100,9 +105,15 @@ def test_whole_genome_sample_matches_oracle(oracle, name, k):
     for e in plan:
         n = len(e["tasks"])
         e["tasks"] = api.slice_tasks(e["tasks"], n - k, n)
-    # the oracle once, the launch in both modes (one wave per cell / main wave + helper: a launch
-    # this small would otherwise always take the second)
-    from parity_cases import launch_modes
+    # the oracle once, the launch in every mode of parity_cases.launch_modes: one wave per cell, main
+    # wave + helper (what the library picks for a launch this small), the 12-wave kernels that run
+    # the full launches of configs[2] / [3], and those with 12 cells to a workgroup (24 k tasks in
+    # 2 k workgroups: chromosome-sized cells with a full burn-in side by side in one LDS block).
+    # configs[4] forced to 12 waves re-inserts 600 - 800 units per epoch: the overflow paths of the
+    # halved LDS buffers, which the library's own choice keeps production away from.
+    from parity_cases import assert_launch_mode, describe_launch, launch_modes
+
+    n_tasks = sum(len(e["tasks"]) for e in plan)
 
     expected = []
     for entry in plan:
@@ -111,14 +122,16 @@ def test_whole_genome_sample_matches_oracle(oracle, name, k):
         expected.append(oracle.simulate_interval(cfg, iv["start"], iv["end"], iv["bar_pos"],
                                                  iv["bar_dir"], stp_a, stp_i, entry["tasks"],
                                                  nthreads=k))
-    for mode in launch_modes():
+    for mode in launch_modes(n_tasks):
         sim, ids, tensors, missed = _launch(cfg, plan)
         try:
+            print(f"{name}: launch mode {mode}: {describe_launch(sim.launch_info())}")
+            assert_launch_mode(sim.launch_info(), mode, n_tasks)
             for entry, iid, t, m, (oc, om, oo, ores) in zip(plan, ids, tensors, missed, expected):
                 iv = entry["interval"]
                 gc = t[0].cpu().numpy().view(np.uint32)
                 go = t[1].cpu().numpy().view(np.uint64)
-                what = f"{name}/{iv['name']}, helper waves {mode}"
+                what = f"{name}/{iv['name']}, launch mode {mode}"
                 assert_same_results(ores, sim.results(iid), what)
                 assert_same_outputs((oc, om, oo), (gc, m, go), what)
         finally:

@@ -4,7 +4,7 @@ per-cell counter of the HIP path must equal the oracle's."""
 import pytest
 
 from fuzz_cases import random_case, random_case_v2, random_case_v3, random_case_v4
-from parity_cases import assert_same_outputs, assert_same_results, launch_modes
+from parity_cases import assert_launch_mode, assert_same_outputs, assert_same_results, launch_modes
 
 pytestmark = pytest.mark.gpu
 
@@ -33,7 +33,9 @@ def test_gpu_matches_oracle_on_random_setups_v4(oracle, seed):
     _compare(oracle, random_case_v4(seed), f"v4 seed {seed}")
 
 
-def _compare(oracle, case, label):
+def _compare(oracle, case, label, modes=None):
+    """the oracle once, the launch in every mode of parity_cases.launch_modes (12 cells: also with the twelve of them
+    side by side in one 12-wave workgroup), or in those of them that `modes` names"""
     from modle_amd import api
 
     cfg, chrom = case["cfg"], case["chrom"]
@@ -42,15 +44,20 @@ def _compare(oracle, case, label):
     oc, om, oo, ores = oracle.simulate_interval(
         cfg, chrom["start"], chrom["end"], chrom["bar_pos"], chrom["bar_dir"],
         case["stp_active"], case["stp_inactive"], tasks, nthreads=8, track_occupancy=track)
-    for mode in launch_modes():
+    for mode in launch_modes(len(tasks)):
+        if modes is not None and mode not in modes:
+            continue
         sim = api.Simulator(cfg, 0)
         try:
+            sim.set_wait_timeout(300.0)
             gc, gm, go, gres = sim.simulate_interval(
                 chrom["start"], chrom["end"], chrom["bar_pos"], chrom["bar_dir"], case["stp_active"],
                 case["stp_inactive"], tasks)
+            info = sim.launch_info()
         finally:
             sim.close()
-        what = f"{label} (helper waves {mode}): {case['kw']}, size {case['size']}"
+        what = f"{label} (launch mode {mode}): {case['kw']}, size {case['size']}"
+        assert_launch_mode(info, mode, len(tasks))
         assert_same_results(ores, gres, what)
         assert_same_outputs((oc, om, oo), (gc, gm, go if track else None), what)
 
@@ -93,8 +100,12 @@ def test_gpu_matches_oracle_on_seeds_of_the_day(oracle, name):
         if cfg.target_contact_density >= 0 and case["tasks"][0].num_target_contacts / per_epoch > 3000:
             skipped += 1
             continue
-        _compare(oracle, case, f"{name} seed of the day {seed} (MODLE_FUZZ_DATE={base // 1000})")
+        # (both modes of the 8-wave kernels for every seed, the 12-wave kernels for every other one: one more
+        # small launch against an oracle run per seed)
+        _compare(oracle, case, f"{name} seed of the day {seed} (MODLE_FUZZ_DATE={base // 1000})",
+                 modes=("0", "1", "12") if seed % 2 == 1 else ("0", "1"))
         done += 1
-    print(f"{name}: {done} fresh seeds from {base} compared in both launch modes, {skipped} skipped (long cells), "
+    print(f"{name}: {done} fresh seeds from {base} compared in both launch modes (odd seeds: with the 12-wave kernels "
+          f"too), {skipped} skipped (long cells), "
           f"{time.time() - t0:.0f} s")
     assert done >= 8, f"only {done} fresh seeds fitted the time budget"

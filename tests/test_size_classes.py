@@ -47,6 +47,8 @@ def test_the_rule_at_its_borders(monkeypatch):
 
 @pytest.mark.parametrize("name", ["chr20mb_barriers", "many_rebinds_per_epoch"])
 def test_emulated_cells_are_identical_in_both_classes(oracle, monkeypatch, name):
+    """(both classes in both geometries: the emulator builds with the LDS buffers and PRNG blocks of the 8-wave and
+    of the 12-wave kernels; a forced WIDE class resolves to libmodle_emu_wide.so / libmodle_emu_w12_wide.so)"""
     import emu_sim
     from modle_amd import api
 
@@ -56,13 +58,15 @@ def test_emulated_cells_are_identical_in_both_classes(oracle, monkeypatch, name)
     track = bool(cfg.track_1d_lef_position)
     ref = oracle.simulate_interval(cfg, ch["start"], ch["end"], ch["bar_pos"], ch["bar_dir"], case["stp_active"],
                                    case["stp_inactive"], tasks, nthreads=2, track_occupancy=track)
-    for forced in (None, "wide"):
+    for geometry, forced in ((None, None), ("w12", None), (None, "wide"), ("w12", "wide")):
         if forced:
             monkeypatch.setenv("MODLE_HIP_SIZE_CLASS", forced)
         got = emu_sim.simulate_interval(cfg, ch["start"], ch["end"], ch["bar_pos"], ch["bar_dir"], case["stp_active"],
-                                        case["stp_inactive"], tasks, case["nrows"], case["ncols"], track_occupancy=track)
-        assert_same_results(ref[3], got[3], f"{name}, emulator, class {forced or 'as classed'}")
-        assert_same_outputs(ref[:3], got[:3], f"{name}, emulator, class {forced or 'as classed'}")
+                                        case["stp_inactive"], tasks, case["nrows"], case["ncols"], track_occupancy=track,
+                                        variant=geometry)
+        what = f"{name}, emulator, {12 if geometry else 8}-wave geometry, class {forced or 'as classed'}"
+        assert_same_results(ref[3], got[3], what)
+        assert_same_outputs(ref[:3], got[:3], what)
 
 
 def test_a_move_the_narrow_class_cannot_hold_ends_the_cell_with_an_error(monkeypatch):
@@ -183,12 +187,13 @@ def test_gpu_all_four_kernels_agree_with_the_oracle(oracle, monkeypatch, waves, 
         assert_same_outputs(ref[:3], (gc, gm, go if track else None), f"{name}, {waves} waves, class {klass}")
 
 
-@pytest.mark.gpu
-def test_gpu_a_fast_extrusion_speed_is_classed_wide_by_itself(oracle, monkeypatch):
-    """moves of 70 kb per epoch do not fit 16 bits: the library runs the 32-bit kernels without being told"""
+def _fast_extrusion_cells_on_the_gpu(oracle, monkeypatch, waves):
     from modle_amd import api, synthetic
 
     monkeypatch.delenv("MODLE_HIP_SIZE_CLASS", raising=False)
+    if waves:
+        monkeypatch.setenv("MODLE_HIP_WAVES", waves)
+        monkeypatch.setenv("MODLE_HIP_PAIRED", "0")
     cfg = api.make_config(num_cells=8, rev_extrusion_speed=70000, fwd_extrusion_speed=70000,
                           rev_extrusion_speed_set=1, fwd_extrusion_speed_set=1,
                           target_contact_density=0.05, max_burnin_epochs=300)
@@ -197,11 +202,58 @@ def test_gpu_a_fast_extrusion_speed_is_classed_wide_by_itself(oracle, monkeypatc
     tasks = api.slice_tasks(api.make_tasks(cfg, ch["name"], ch["size"], 0, ch["size"]), 0, 4)
     sim = api.Simulator(cfg, 0)
     try:
+        sim.set_wait_timeout(300.0)
         gc, gm, go, gres = sim.simulate_interval(0, ch["size"], ch["bar_pos"], ch["bar_dir"], stp_a, stp_i, tasks)
-        assert sim.launch_info()["size_class"] == 1
+        info = sim.launch_info()
     finally:
         sim.close()
+    assert info["size_class"] == 1, info
+    if waves:
+        assert info["size_class"] == 1 and info["waves_per_workgroup"] == int(waves), info
     oc, om, oo, ores = oracle.simulate_interval(cfg, 0, ch["size"], ch["bar_pos"], ch["bar_dir"], stp_a, stp_i, tasks,
                                                 nthreads=4)
     assert np.array_equal(gc, oc) and gm == om and np.array_equal(go, oo)
-    assert_same_results(ores, gres, "70 kb per epoch")
+    assert_same_results(ores, gres, f"70 kb per epoch, MODLE_HIP_WAVES={waves}")
+
+
+@pytest.mark.gpu
+def test_gpu_a_fast_extrusion_speed_is_classed_wide_by_itself(oracle, monkeypatch):
+    """moves of 70 kb per epoch do not fit 16 bits: the library runs the 32-bit kernels without being told"""
+    _fast_extrusion_cells_on_the_gpu(oracle, monkeypatch, None)
+
+
+@pytest.mark.gpu
+def test_gpu_a_fast_extrusion_speed_is_classed_wide_by_itself_with_12_waves(oracle, monkeypatch):
+    """... and MODLE_HIP_WAVES=12 then means `modle_simulate_cells_wide12`: the only set-up of the suite that is
+    WIDE by its own parameters (everywhere else the class is forced) on the 12-wave build of the 32-bit kernels"""
+    _fast_extrusion_cells_on_the_gpu(oracle, monkeypatch, "12")
+
+
+@pytest.mark.gpu
+def test_gpu_the_library_picks_the_12_wave_kernel_for_a_launch_that_fills_its_workgroups(oracle, monkeypatch):
+    """What production runs: a launch with at least 12 tasks per workgroup whose epochs re-insert few units gets the
+    12-wave kernel by the library's own rule, nothing forced (modle_hip.hip: `tasks >= grid * 12`).  48 cells of
+    chr20mb_barriers in 4 workgroups (MODLE_HIP_GRID, the diagnostic switch that launch mode "12packed" of
+    parity_cases.launch_modes uses too): twelve main waves per workgroup, and every word equals the oracle's."""
+    from modle_amd import api
+
+    for name in ("MODLE_HIP_WAVES", "MODLE_HIP_PAIRED", "MODLE_HIP_SIZE_CLASS", "MODLE_HIP_ACTIVE_WAVES"):
+        monkeypatch.delenv(name, raising=False)
+    monkeypatch.setenv("MODLE_HIP_GRID", "4")
+    case = build_case("chr20mb_barriers")
+    cfg, ch = case["cfg"], case["chrom"]
+    tasks = api.slice_tasks(case["tasks"], 0, 48)
+    ref = oracle.simulate_interval(cfg, ch["start"], ch["end"], ch["bar_pos"], ch["bar_dir"], case["stp_active"],
+                                   case["stp_inactive"], tasks, nthreads=8)
+    sim = api.Simulator(cfg, 0)
+    try:
+        sim.set_wait_timeout(300.0)
+        gc, gm, go, gres = sim.simulate_interval(ch["start"], ch["end"], ch["bar_pos"], ch["bar_dir"],
+                                                 case["stp_active"], case["stp_inactive"], tasks)
+        info = sim.launch_info()
+    finally:
+        sim.close()
+    assert info["waves_per_workgroup"] == 12 and info["workgroups"] == 4 and info["n_tasks"] == 48, info
+    assert info["main_waves_per_workgroup"] == 12 and info["helper_waves"] == 0 and info["size_class"] == 0, info
+    assert_same_results(ref[3], gres, "48 cells in 4 workgroups, the library's choice")
+    assert_same_outputs(ref[:3], (gc, gm, go), "48 cells in 4 workgroups, the library's choice")
