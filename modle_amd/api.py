@@ -143,6 +143,7 @@ class Simulator:
         err = _errbuf()
         self._L = lib()
         self.cfg = cfg
+        self.device = int(device)
         self._h = self._L.modle_hip_create(C.byref(cfg), device, err, len(err))
         if not self._h:
             raise ModleHipError(f"modle_hip_create failed: {err.value.decode(errors='replace')}")
@@ -262,6 +263,15 @@ class Simulator:
             self._h, interval_id, contacts.ctypes.data if contacts is not None else None,
             C.byref(missed), occ.ctypes.data if occ is not None else None, err, len(err)), err)
         return contacts, missed.value, occ
+
+    def pixels(self, interval_id, bin_offset=0, stream=None):
+        """The interval's non-zero pixels in cooler order, extracted on the device from the band
+        matrix where it lies (pixels.py): bin1, bin2, count, bin1_offset, stats.  Call it after
+        wait(); the dense matrix is not copied to the host."""
+        from . import pixels
+
+        d_contacts, _, nrows, ncols = self.outputs(interval_id)
+        return pixels.extract(d_contacts, nrows, ncols, bin_offset, stream, device=self.device)
 
     def simulate_interval(self, start, end, bar_pos, bar_dir, stp_active, stp_inactive, tasks):
         """One-call seam (modle_hip_simulate_interval): returns contacts, missed, occupancy,

@@ -224,7 +224,17 @@ def simulate(a, log=print):
             # (with --skip-output the log would not be written: nothing is recorded, and the
             # default build of the library serves, like the reference accepts the combination)
             sim.enable_state_log(a.internal_state_max_epochs)
-        ids = driver.enqueue_plan(sim, cfg, plan)
+        tensors = None
+        if use_dist:
+            # the matrices are torch tensors the kernel accumulates into: they are reduced in
+            # place and rank 0 extracts its pixels from the reduced tensor, without a host copy
+            dev = torch.device("cuda", device)
+            tensors = [None if e["skipped"] else
+                       (torch.zeros(e["nrows"] * e["ncols"] + 1, dtype=torch.int32, device=dev),
+                        torch.zeros(e["ncols"], dtype=torch.int64, device=dev)) for e in plan]
+            torch.cuda.synchronize(dev)
+        ids = driver.enqueue_plan(sim, cfg, plan, device_buffers=None if tensors is None else [
+            (None, None) if t is None else (t[0].data_ptr(), t[1].data_ptr()) for t in tensors])
         n_tasks = sum(len(e["tasks"]) for e in plan if not e["skipped"])
         log(f"simulating {n_tasks} (interval, cell) tasks on device {device} (rank {rank} of {world})")
         sim.launch()
@@ -245,45 +255,58 @@ def simulate(a, log=print):
                         fh.writelines(driver.format_state_log(task, iv, len(iv["bar_pos"]),
                                                               sim.state_log(iid, k)))
             log(f"written {path}")
-        matrices, occupancies = [], []
-        for entry, iid in zip(plan, ids):
-            if iid is None:
-                matrices.append(None)
-                occupancies.append(None)
-                continue
-            c, missed, occ = sim.copy_outputs(iid)
-            if use_dist:
-                import torch
+        # The contact matrices stay on the device: the cooler is written from their non-zero
+        # pixels, extracted there (libmodle_pixels.so), and the warning uses the extraction's sum.
+        from . import pixels
 
-                dev = torch.device("cuda", device)
-                tc = torch.from_numpy(c.view(np.int32)).to(dev)
-                to = torch.from_numpy(occ.view(np.int64)).to(dev) if occ is not None else None
+        occupancies, missed_updates = [], []
+        for k, iid in enumerate(ids):
+            if iid is None:
+                occupancies.append(None)
+                missed_updates.append(0)
+                continue
+            _, missed, occ = sim.copy_outputs(iid, want_contacts=False)
+            if use_dist:
+                tc, to = tensors[k]
                 dist.reduce(tc, dst=0, op=dist.ReduceOp.SUM)
-                if to is not None:
-                    dist.reduce(to, dst=0, op=dist.ReduceOp.SUM)
-                c = tc.cpu().numpy().view(np.uint32)
-                occ = to.cpu().numpy().view(np.uint64) if to is not None else None
-            total = int(c[:entry["nrows"] * entry["ncols"]].astype(np.int64).sum())
-            if rank == 0 and total + missed > 0 and missed / (total + missed) >= 0.01:
-                log(f"warning: {100.0 * missed / (total + missed):.2f}% missing interactions for "
-                    f"{entry['interval']['name']}")  # simulation.cpp:153-157
-            matrices.append(c)
+                dist.reduce(to, dst=0, op=dist.ReduceOp.SUM)
+                occ = to.cpu().numpy().view(np.uint64) if occ is not None else None
             occupancies.append(occ)
+            missed_updates.append(missed)
+        if use_dist:
+            torch.cuda.synchronize(torch.device("cuda", device))
+
+        def warn_missing(k, stats):
+            total, missed = int(stats.sum), missed_updates[k]
+            if total + missed > 0 and missed / (total + missed) >= 0.01:
+                log(f"warning: {100.0 * missed / (total + missed):.2f}% missing interactions for "
+                    f"{plan[k]['interval']['name']}")  # simulation.cpp:153-157
+
+        def extract(k, bin_offset):
+            if ids[k] is None:
+                return None
+            px = sim.pixels(ids[k], bin_offset)
+            warn_missing(k, px[4])
+            return px
+
+        if rank == 0 and not a.skip_output:
+            meta = json.dumps({k: v for k, v in vars(a).items() if v is not None and k != "command"},
+                              sort_keys=True)
+            driver.write_cooler_pixels(cool_path, cfg, plan, extract, assembly=a.assembly_name,
+                                       generated_by="modle_amd (MI355X)", metadata_json=meta,
+                                       force_overwrite=a.force, chroms=chroms)
+            log(f"written {cool_path}")
+        elif rank == 0:
+            for k, iid in enumerate(ids):  # --skip-output: nothing is extracted, only summed
+                if iid is not None:
+                    d_contacts, _, nrows, ncols = sim.outputs(iid)
+                    warn_missing(k, pixels.extractor(device).count(d_contacts, nrows, ncols))
     finally:
         sim.close()
-    if rank == 0 and not a.skip_output:
-        meta = json.dumps({k: v for k, v in vars(a).items() if v is not None and k != "command"},
-                          sort_keys=True)
-        driver.write_cooler(cool_path, cfg, plan, matrices, assembly=a.assembly_name,
-                            generated_by="modle_amd (MI355X)", metadata_json=meta,
-                            force_overwrite=a.force, chroms=chroms)
-        log(f"written {cool_path}")
-        if cfg.track_1d_lef_position:
-            driver.write_bigwig(bw_path, cfg, plan, occupancies, chroms, force_overwrite=a.force)
-            log(f"written {bw_path}")
+    if rank == 0 and not a.skip_output and cfg.track_1d_lef_position:
+        driver.write_bigwig(bw_path, cfg, plan, occupancies, chroms, force_overwrite=a.force)
+        log(f"written {bw_path}")
     if use_dist:
-        import torch.distributed as dist
-
         dist.destroy_process_group()
     log(f"done in {time.time() - t0:.1f} s")
     return 0

@@ -27,6 +27,15 @@ def lib():
         lb.modle_cool_append_matrix.argtypes = [
             ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
             ctypes.c_uint64, ctypes.c_char_p, ctypes.c_size_t]
+        lb.modle_cool_bin_offset.restype = ctypes.c_int  # include/modle_cooler_pixels.h
+        lb.modle_cool_bin_offset.argtypes = [
+            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.POINTER(ctypes.c_int64),
+            ctypes.c_char_p, ctypes.c_size_t]
+        lb.modle_cool_append_pixels.restype = ctypes.c_int
+        lb.modle_cool_append_pixels.argtypes = [
+            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_char_p,
+            ctypes.c_size_t]
         lb.modle_cool_close.restype = ctypes.c_int
         lb.modle_cool_close.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
         _LIB = lb
@@ -66,6 +75,40 @@ class CoolerWriter:
         cid = self._index[chrom] if isinstance(chrom, str) else int(chrom)
         rc = lib().modle_cool_append_matrix(self._h, cid, int(offset_bp), band.ctypes.data,
                                             int(nrows), int(ncols), self._err, len(self._err))
+        if rc != 0:
+            raise CoolerError(rc, self._err.value.decode())
+
+    def bin_offset(self, chrom, offset_bp=0):
+        """first bin id, within the file, of the interval of `chrom` that starts at `offset_bp`:
+        what the pixels of that interval are extracted with (pixels.extract(bin_offset=...))"""
+        cid = self._index[chrom] if isinstance(chrom, str) else int(chrom)
+        out = ctypes.c_int64(0)
+        rc = lib().modle_cool_bin_offset(self._h, cid, int(offset_bp), ctypes.byref(out), self._err,
+                                         len(self._err))
+        if rc != 0:
+            raise CoolerError(rc, self._err.value.decode())
+        return out.value
+
+    def append_pixels(self, chrom, ncols, bin1, bin2, count, bin1_offset=None, offset_bp=0):
+        """the sorted non-zero pixels of one interval of `ncols` bins (modle_cool_append_pixels):
+        int64 file-wide bin ids, int32 counts, and optionally the interval's bin1_offset index
+        (ncols + 1 entries), which is then checked against the pixels"""
+        import numpy as np
+        bin1 = np.ascontiguousarray(bin1, dtype=np.int64)
+        bin2 = np.ascontiguousarray(bin2, dtype=np.int64)
+        count = np.ascontiguousarray(count, dtype=np.int32)
+        if not (bin1.ndim == bin2.ndim == count.ndim == 1 and len(bin1) == len(bin2) == len(count)):
+            raise ValueError("bin1, bin2 and count must be 1-D arrays of one length")
+        off = None
+        if bin1_offset is not None:
+            off = np.ascontiguousarray(bin1_offset, dtype=np.int64)
+            if off.shape != (int(ncols) + 1,):
+                raise ValueError("bin1_offset must hold ncols + 1 entries")
+        cid = self._index[chrom] if isinstance(chrom, str) else int(chrom)
+        rc = lib().modle_cool_append_pixels(self._h, cid, int(offset_bp), int(ncols), bin1.ctypes.data,
+                                            bin2.ctypes.data, count.ctypes.data, len(bin1),
+                                            off.ctypes.data if off is not None else None, self._err,
+                                            len(self._err))
         if rc != 0:
             raise CoolerError(rc, self._err.value.decode())
 

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "modle_cooler.h"
+#include "modle_cooler_pixels.h"
 
 namespace {
 
@@ -245,6 +246,88 @@ extern "C" int modle_cool_append_matrix(modle_cool_file* f, size_t chrom_id, uin
     set_err(err, errlen, "HDF5 error while appending pixels");
     return MODLE_COOL_ERR_IO;
   }
+  f->n_pixels = s1;
+  return MODLE_COOL_OK;
+}
+
+extern "C" int modle_cool_bin_offset(const modle_cool_file* f, size_t chrom_id, uint64_t offset_bp,
+                                     int64_t* bin_offset, char* err, size_t errlen) {
+  if (f == nullptr || bin_offset == nullptr || chrom_id >= f->chrom_sizes.size()) {
+    set_err(err, errlen, "modle_cool_bin_offset: invalid argument");
+    return MODLE_COOL_ERR_ARG;
+  }
+  *bin_offset = f->chrom_offset[chrom_id] + static_cast<int64_t>(offset_bp / f->bin_size);
+  return MODLE_COOL_OK;
+}
+
+extern "C" int modle_cool_append_pixels(modle_cool_file* f, size_t chrom_id, uint64_t offset_bp,
+                                        uint64_t ncols, const int64_t* bin1, const int64_t* bin2,
+                                        const int32_t* count, uint64_t n, const int64_t* bin1_offset,
+                                        char* err, size_t errlen) {
+  if (f == nullptr || chrom_id >= f->chrom_sizes.size() ||
+      (n != 0 && (bin1 == nullptr || bin2 == nullptr || count == nullptr))) {
+    set_err(err, errlen, "modle_cool_append_pixels: invalid argument");
+    return MODLE_COOL_ERR_ARG;
+  }
+  const int64_t chrom_last = f->chrom_offset[chrom_id + 1];
+  const int64_t bin_offset = f->chrom_offset[chrom_id] + static_cast<int64_t>(offset_bp / f->bin_size);
+  // the ordering rules of modle_cool_append_matrix
+  if (chrom_id + 1 < f->next_chrom || bin_offset < f->next_bin1) {
+    set_err(err, errlen, "modle_cool_append_pixels: intervals must be appended in genome order and must not overlap");
+    return MODLE_COOL_ERR_ARG;
+  }
+  if (ncols > static_cast<uint64_t>(chrom_last - bin_offset) || bin_offset > chrom_last) {
+    set_err(err, errlen, "modle_cool_append_pixels: the interval does not fit the chromosome's bins");
+    return MODLE_COOL_ERR_RANGE;
+  }
+  const int64_t bin_end = bin_offset + static_cast<int64_t>(ncols);
+  // Everything is checked before the handle or the file changes.
+  std::vector<int64_t> rel(static_cast<size_t>(ncols) + 1, static_cast<int64_t>(n));  // rows' first pixels
+  int64_t sum = 0;
+  uint64_t next_row = 0;  // rows below it have their offset
+  for (uint64_t k = 0; k < n; ++k) {
+    if (bin1[k] < bin_offset || bin1[k] >= bin_end || bin2[k] >= bin_end) {
+      set_err(err, errlen, "modle_cool_append_pixels: a bin id lies outside the interval");
+      return MODLE_COOL_ERR_RANGE;
+    }
+    if (bin2[k] < bin1[k]) {
+      set_err(err, errlen, "modle_cool_append_pixels: bin2 < bin1 (storage is symmetric-upper)");
+      return MODLE_COOL_ERR_ARG;
+    }
+    if (k != 0 && (bin1[k] < bin1[k - 1] || (bin1[k] == bin1[k - 1] && bin2[k] <= bin2[k - 1]))) {
+      set_err(err, errlen, "modle_cool_append_pixels: the pixels are not sorted by (bin1, bin2)");
+      return MODLE_COOL_ERR_ARG;
+    }
+    if (count[k] == 0) {
+      set_err(err, errlen, "modle_cool_append_pixels: a pixel with a count of 0");
+      return MODLE_COOL_ERR_ARG;
+    }
+    if (count[k] < 0) {
+      set_err(err, errlen, "modle_cool_append_pixels: a count does not fit the int32 pixel type");
+      return MODLE_COOL_ERR_RANGE;
+    }
+    for (const uint64_t row = static_cast<uint64_t>(bin1[k] - bin_offset); next_row <= row; ++next_row)
+      rel[next_row] = static_cast<int64_t>(k);
+    sum += count[k];
+  }
+  if (bin1_offset != nullptr && !std::equal(rel.begin(), rel.end(), bin1_offset)) {
+    set_err(err, errlen, "modle_cool_append_pixels: bin1_offset does not index the pixels");
+    return MODLE_COOL_ERR_ARG;
+  }
+  hsize_t s1 = f->n_pixels, s2 = f->n_pixels, s3 = f->n_pixels;
+  if (!append(f->d_bin1, H5T_NATIVE_INT64, bin1, n, s1) || !append(f->d_bin2, H5T_NATIVE_INT64, bin2, n, s2) ||
+      !append(f->d_count, H5T_NATIVE_INT32, count, n, s3)) {
+    set_err(err, errlen, "HDF5 error while appending pixels");
+    return MODLE_COOL_ERR_IO;
+  }
+  // bins before this interval's first row have no pixels
+  for (int64_t b = f->next_bin1; b < bin_offset; ++b) f->bin1_offset[static_cast<size_t>(b)] = static_cast<int64_t>(f->n_pixels);
+  for (uint64_t i = 0; i < ncols; ++i)
+    f->bin1_offset[static_cast<size_t>(bin_offset) + i] = static_cast<int64_t>(f->n_pixels) + rel[i];
+  f->sum += sum;
+  f->cis = f->sum;  // every pixel joins two bins of one chromosome
+  f->next_bin1 = bin_end;
+  f->next_chrom = chrom_id + 1;
   f->n_pixels = s1;
   return MODLE_COOL_OK;
 }

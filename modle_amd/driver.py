@@ -162,6 +162,33 @@ def write_cooler(path, cfg, plan, matrices, assembly="unknown", generated_by="mo
             w.append(iv["name"], m, entry["nrows"], entry["ncols"], offset_bp=int(iv["start"]))
 
 
+def write_cooler_pixels(path, cfg, plan, extract, assembly="unknown", generated_by="modle-hip",
+                        metadata_json="", force_overwrite=False, chroms=None):
+    """write_cooler from sparse pixels: the same file (dataset for dataset, attribute for
+    attribute), without a dense matrix on the host.  `extract(k, bin_offset)` returns the sorted
+    non-zero pixels of plan entry k with `bin_offset` (the interval's first bin within the file)
+    added to the bin ids, as (bin1, bin2, count, bin1_offset[, stats]) -- what
+    api.Simulator.pixels / pixels.extract return -- or None for an entry without a matrix.  It is
+    called once per entry that is not skipped, in genome order, so that one interval's pixels are
+    on the host at a time."""
+    from . import cooler
+
+    if chroms is None:
+        chroms = _chroms_of_plan(plan)
+    with cooler.CoolerWriter(path, chroms, int(cfg.bin_size), assembly=assembly,
+                             generated_by=generated_by, metadata_json=metadata_json,
+                             force_overwrite=force_overwrite) as w:
+        for k, entry in enumerate(plan):
+            if entry["skipped"]:
+                continue
+            iv = entry["interval"]
+            px = extract(k, w.bin_offset(iv["name"], int(iv["start"])))
+            if px is None:
+                continue
+            w.append_pixels(iv["name"], entry["ncols"], px[0], px[1], px[2], bin1_offset=px[3],
+                            offset_bp=int(iv["start"]))
+
+
 def write_bigwig(path, cfg, plan, occupancies, chroms=None, force_overwrite=False):
     """Writes the 1-D LEF occupancy of every simulated interval the way the reference's IO thread
     does (simulation.cpp:130-141, 170-197): every chromosome of the genome in the header, one

@@ -1,0 +1,154 @@
+"""ctypes view of the sparse-pixel extraction, include/modle_pixels.h (modle_amd/libmodle_pixels.so,
+built by `make -C modle_amd/pixels`): the non-zero pixels of a band matrix that lies in device
+memory, in cooler order, found on the GPU.  There is no host fallback: without the library or
+without a device the calls fail."""
+import ctypes as C
+import os
+from collections import namedtuple
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+SO_PATH = os.path.join(_HERE, "libmodle_pixels.so")
+ERR_ARG, ERR_DEVICE, ERR_RANGE = -1, -2, -3
+EXPORTS = ["modle_pixels_create", "modle_pixels_destroy", "modle_pixels_count", "modle_pixels_extract",
+           "modle_pixels_to_host"]  # every symbol include/modle_pixels.h declares
+
+_LIB = None
+_EXTRACTORS = {}
+
+Stats = namedtuple("Stats", "nnz sum max_count")
+
+
+class _CStats(C.Structure):  # modle_pixels_stats
+    _fields_ = [("nnz", C.c_uint64), ("sum", C.c_uint64), ("max_count", C.c_uint32),
+                ("reserved_", C.c_uint32)]
+
+
+class PixelsError(RuntimeError):
+    def __init__(self, code, message):
+        super().__init__(f"modle_pixels error {code}: {message}")
+        self.code = code
+
+
+def lib():
+    global _LIB
+    if _LIB is None:
+        if not os.path.exists(SO_PATH):
+            raise ImportError(f"{SO_PATH} is missing: run `make -C modle_amd/pixels` "
+                              "(python -c 'import __graft_entry__ as g; g.build()')")
+        from ._lib import _share_the_hip_runtime_with_torch
+
+        _share_the_hip_runtime_with_torch()  # one HIP runtime per process (see _lib.py)
+        lb = C.CDLL(SO_PATH)
+        err = [C.c_char_p, C.c_size_t]
+        shape = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]  # handle, d_band, nrows, ncols
+        lb.modle_pixels_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)] + err
+        lb.modle_pixels_destroy.argtypes = [C.c_void_p]
+        lb.modle_pixels_destroy.restype = None
+        lb.modle_pixels_count.argtypes = shape + [C.c_void_p, C.POINTER(_CStats), C.c_void_p] + err
+        lb.modle_pixels_extract.argtypes = shape + [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_uint64, C.c_void_p] + err
+        lb.modle_pixels_to_host.argtypes = shape + [C.c_int64] + [C.POINTER(C.c_void_p)] * 4 + \
+            [C.POINTER(_CStats), C.c_void_p] + err
+        for name in EXPORTS:
+            getattr(lb, name)  # raises AttributeError if a declared symbol is not exported
+        _LIB = lb
+    return _LIB
+
+
+def _stream_ptr(stream):
+    """None, a raw hipStream_t value, or a torch.cuda.Stream"""
+    if stream is None:
+        return None
+    return int(getattr(stream, "cuda_stream", stream)) or None
+
+
+def _host_array(ptr, n, dtype):
+    if n == 0 or not ptr:
+        return np.zeros(0, dtype=dtype)
+    ctype = C.c_int64 if dtype == np.int64 else C.c_int32
+    return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(n,)).copy()
+
+
+class Extractor:
+    """One context of the library on one device (modle_pixels_create)."""
+
+    def __init__(self, device=0):
+        self._L = lib()
+        self._h = C.c_void_p()
+        err = C.create_string_buffer(512)
+        rc = self._L.modle_pixels_create(int(device), C.byref(self._h), err, len(err))
+        if rc != 0:
+            self._h = None
+            raise PixelsError(rc, err.value.decode(errors="replace"))
+        self.device = int(device)
+
+    def close(self):
+        if self._h:
+            h, self._h = self._h, None
+            self._L.modle_pixels_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def count(self, d_band, nrows, ncols, d_bin1_offset=None, stream=None):
+        """step 1: fills the device array `d_bin1_offset` (int64[ncols + 1], a device pointer; None
+        when only the statistics are wanted) and returns Stats; waits for the stream"""
+        st = _CStats()
+        err = C.create_string_buffer(512)
+        rc = self._L.modle_pixels_count(self._h, d_band, int(nrows), int(ncols), d_bin1_offset,
+                                        C.byref(st), _stream_ptr(stream), err, len(err))
+        if rc != 0:
+            raise PixelsError(rc, err.value.decode(errors="replace"))
+        return Stats(st.nnz, st.sum, st.max_count)
+
+    def extract_into(self, d_band, nrows, ncols, bin_offset, d_bin1_offset, d_bin1, d_bin2, d_count,
+                     nnz, stream=None):
+        """step 2: enqueues the extraction into caller-owned device arrays of `nnz` entries"""
+        err = C.create_string_buffer(512)
+        rc = self._L.modle_pixels_extract(self._h, d_band, int(nrows), int(ncols), int(bin_offset),
+                                          d_bin1_offset, d_bin1, d_bin2, d_count, int(nnz),
+                                          _stream_ptr(stream), err, len(err))
+        if rc != 0:
+            raise PixelsError(rc, err.value.decode(errors="replace"))
+
+    def extract(self, d_band, nrows, ncols, bin_offset=0, stream=None):
+        """one-call form: numpy bin1, bin2 (int64), count (int32), bin1_offset (int64[ncols + 1])
+        and Stats(nnz, sum, max_count).  A count above INT32_MAX raises PixelsError(ERR_RANGE)."""
+        p1, p2, pc, po = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        st = _CStats()
+        err = C.create_string_buffer(512)
+        rc = self._L.modle_pixels_to_host(self._h, d_band, int(nrows), int(ncols), int(bin_offset),
+                                          C.byref(p1), C.byref(p2), C.byref(pc), C.byref(po),
+                                          C.byref(st), _stream_ptr(stream), err, len(err))
+        if rc != 0:
+            raise PixelsError(rc, err.value.decode(errors="replace"))
+        n = int(st.nnz)
+        return (_host_array(p1.value, n, np.int64), _host_array(p2.value, n, np.int64),
+                _host_array(pc.value, n, np.int32), _host_array(po.value, int(ncols) + 1, np.int64),
+                Stats(st.nnz, st.sum, st.max_count))
+
+
+def extractor(device=0):
+    """the process-wide context of `device`"""
+    ex = _EXTRACTORS.get(int(device))
+    if ex is None or not ex._h:
+        ex = _EXTRACTORS[int(device)] = Extractor(device)
+    return ex
+
+
+def extract(d_band, nrows, ncols, bin_offset=0, stream=None, device=0):
+    """Pixels of the band at device pointer `d_band` (uint32, layout of modle_hip_interval_outputs;
+    e.g. a torch tensor's data_ptr()): returns bin1, bin2, count, bin1_offset, stats."""
+    return extractor(device).extract(d_band, nrows, ncols, bin_offset, stream)

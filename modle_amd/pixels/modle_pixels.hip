@@ -1,0 +1,386 @@
+// modle_pixels.hip -- sparse cooler pixels from a dense band matrix on the MI355X
+// (include/modle_pixels.h).  Three kernels:
+//
+//   pixels_count    reads the band the way it lies in memory (d contiguous within a column, so a
+//                   wave reads 256 contiguous bytes), counts the non-zero pixels per row in LDS
+//                   counters, adds them to the global row counts, and reduces sum and max;
+//   pixels_scan     one workgroup: exclusive scan of the row counts -> bin1_offset, nnz;
+//   pixels_extract  one wave per 16 consecutive rows.  A row's pixels are nrows + 1 words apart,
+//                   but pixel (i, d) and pixel (i - 1, d + 1) are neighbours in memory: lane
+//                   (r, c) of a wave reads row i0 + r at d = t - r with t = 4 * step + c, so the 16
+//                   lanes of one c read 16 contiguous words of column i0 + t.  The ranks within a
+//                   row come from a ballot masked to the row's four lanes, the running base of a
+//                   row from the popcount of the same mask.
+//
+// Only vector loads / stores and atomics; wave64 throughout.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <limits>
+#include <new>
+#include <string>
+
+#include "modle_pixels.h"
+
+namespace {
+
+constexpr unsigned kCountCols = 64;     // columns of one pixels_count tile
+constexpr unsigned kCountDepth = 256;  // band words (d) of one pixels_count tile
+constexpr unsigned kCountThreads = 256;
+constexpr unsigned kScanThreads = 1024;
+constexpr unsigned kExtractThreads = 256;  // 4 waves
+constexpr unsigned kRowsPerWave = 16;
+constexpr unsigned kRowsPerBlock = kRowsPerWave * (kExtractThreads / 64);
+
+struct DeviceStats {
+  unsigned long long nnz;
+  unsigned long long sum;
+  unsigned int max_count;
+  unsigned int pad_;
+};
+
+// Tile (bx, by): columns [j0, j0 + cn), band words [d0, d0 + dn).  Its pixels belong to the rows
+// j - d, a range of cn + dn - 1 rows: slot = (j - j0) + (d0 + dn - 1 - d).
+__global__ __launch_bounds__(kCountThreads) void pixels_count(const uint32_t* __restrict__ band,
+                                                              uint64_t nrows, uint64_t ncols,
+                                                              unsigned long long* __restrict__ row_count,
+                                                              DeviceStats* __restrict__ stats) {
+  __shared__ unsigned int slots[kCountCols + kCountDepth - 1];
+  const uint64_t j0 = static_cast<uint64_t>(blockIdx.x) * kCountCols;
+  const uint64_t d0 = static_cast<uint64_t>(blockIdx.y) * kCountDepth;
+  const unsigned cn = static_cast<unsigned>(min(static_cast<uint64_t>(kCountCols), ncols - j0));
+  const unsigned dn = static_cast<unsigned>(min(static_cast<uint64_t>(kCountDepth), nrows - d0));
+  const unsigned nslots = cn + dn - 1;
+  for (unsigned s = threadIdx.x; s < nslots; s += kCountThreads) slots[s] = 0;
+  __syncthreads();
+
+  unsigned long long sum = 0;
+  unsigned int mx = 0;
+  for (unsigned jj = 0; jj < cn; ++jj) {
+    const uint64_t j = j0 + jj;
+    const uint32_t* col = band + j * nrows;
+    for (unsigned dd = threadIdx.x; dd < dn; dd += kCountThreads) {
+      const uint64_t d = d0 + dd;
+      if (d > j) break;  // left-edge triangle: no pixel (and none further down this column)
+      const uint32_t v = col[d];
+      sum += v;
+      mx = max(mx, v);
+      if (v != 0) atomicAdd(&slots[jj + (dn - 1 - dd)], 1u);
+    }
+  }
+  __syncthreads();
+  // row of slot s: j0 - (d0 + dn - 1) + s; slots of rows below 0 hold nothing
+  const int64_t row0 = static_cast<int64_t>(j0) - static_cast<int64_t>(d0 + dn - 1);
+  for (unsigned s = threadIdx.x; s < nslots; s += kCountThreads) {
+    const unsigned int c = slots[s];
+    if (c != 0) atomicAdd(&row_count[row0 + static_cast<int64_t>(s)], static_cast<unsigned long long>(c));
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    sum += __shfl_down(sum, o);
+    mx = max(mx, __shfl_down(mx, o));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (sum != 0) atomicAdd(&stats->sum, sum);
+    if (mx != 0) atomicMax(&stats->max_count, mx);
+  }
+}
+
+// In place: offsets[i] = sum of the counts of the rows below i; offsets[ncols] = nnz.
+__global__ __launch_bounds__(kScanThreads) void pixels_scan(unsigned long long* __restrict__ offsets,
+                                                            uint64_t ncols,
+                                                            DeviceStats* __restrict__ stats) {
+  __shared__ unsigned long long wave_sum[kScanThreads / 64];
+  const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned long long carry = 0;
+  for (uint64_t base = 0; base < ncols; base += kScanThreads) {
+    const uint64_t idx = base + threadIdx.x;
+    const unsigned long long v = idx < ncols ? offsets[idx] : 0;
+    unsigned long long x = v;
+    for (unsigned o = 1; o < 64; o <<= 1) {
+      const unsigned long long y = __shfl_up(x, o);
+      if (lane >= o) x += y;
+    }
+    if (lane == 63) wave_sum[wave] = x;
+    __syncthreads();
+    unsigned long long before = 0, total = 0;
+    for (unsigned w = 0; w < kScanThreads / 64; ++w) {
+      const unsigned long long s = wave_sum[w];
+      if (w < wave) before += s;
+      total += s;
+    }
+    if (idx < ncols) offsets[idx] = carry + before + x - v;
+    carry += total;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    offsets[ncols] = carry;
+    stats->nnz = carry;
+  }
+}
+
+__global__ __launch_bounds__(kExtractThreads) void pixels_extract(
+    const uint32_t* __restrict__ band, uint64_t nrows, uint64_t ncols, int64_t bin_offset,
+    const int64_t* __restrict__ offsets, int64_t* __restrict__ bin1, int64_t* __restrict__ bin2,
+    int32_t* __restrict__ count, uint64_t nnz) {
+  const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned r = lane & (kRowsPerWave - 1), c = lane >> 4;
+  const uint64_t i = (static_cast<uint64_t>(blockIdx.x) * (kExtractThreads / 64) + wave) * kRowsPerWave + r;
+  uint64_t len = 0, base = 0;  // pixels of row i: d < len; a row beyond the matrix has none
+  if (i < ncols) {
+    len = ncols - i < nrows ? ncols - i : nrows;
+    base = static_cast<uint64_t>(offsets[i]);
+  }
+  const unsigned long long row_lanes = 0x0001000100010001ULL << r;  // lanes (r, 0..3)
+  const unsigned long long below = (1ULL << lane) - 1;
+  const int64_t id1 = bin_offset + static_cast<int64_t>(i);
+  // t runs over [0, nrows - 1 + 15], kUnroll steps at a time: the loads of a group are issued
+  // together (a step beyond the last has no pixel); the trip count is the same for every wave
+  constexpr unsigned kUnroll = 4;
+  const uint64_t steps = (nrows + kRowsPerWave - 1 + 3) / 4;
+  for (uint64_t s0 = 0; s0 < steps; s0 += kUnroll) {
+    uint32_t v[kUnroll];
+#pragma unroll
+    for (unsigned u = 0; u < kUnroll; ++u) {
+      const uint64_t t = 4 * (s0 + u) + c;
+      const uint64_t d = t - r;
+      v[u] = (i < ncols && t >= r && d < len) ? band[(i + d) * nrows + d] : 0u;
+    }
+#pragma unroll
+    for (unsigned u = 0; u < kUnroll; ++u) {
+      const uint64_t d = 4 * (s0 + u) + c - r;
+      const unsigned long long mine = __ballot(v[u] != 0) & row_lanes;
+      if (v[u] != 0) {
+        const uint64_t pos = base + __popcll(mine & below);
+        if (pos < nnz) {
+          bin1[pos] = id1;
+          bin2[pos] = id1 + static_cast<int64_t>(d);
+          count[pos] = static_cast<int32_t>(v[u]);
+        }
+      }
+      base += __popcll(mine);
+    }
+  }
+}
+
+void set_err(char* err, size_t errlen, const std::string& msg) {
+  if (err != nullptr && errlen != 0) std::snprintf(err, errlen, "%s", msg.c_str());
+}
+
+}  // namespace
+
+struct modle_pixels_handle {
+  int device = 0;
+  DeviceStats* d_stats = nullptr;
+  DeviceStats* h_stats = nullptr;  // pinned
+  // one-call form: device arrays and their pinned host mirrors, grown on demand
+  void *d_bin1 = nullptr, *d_bin2 = nullptr, *d_count = nullptr, *d_offsets = nullptr;
+  void *h_bin1 = nullptr, *h_bin2 = nullptr, *h_count = nullptr, *h_offsets = nullptr;
+  uint64_t cap_pixels = 0, cap_offsets = 0;
+};
+
+namespace {
+
+#define PIX_TRY(call)                                                                           \
+  do {                                                                                          \
+    const hipError_t e_ = (call);                                                               \
+    if (e_ != hipSuccess) {                                                                     \
+      set_err(err, errlen, std::string(#call) + ": " + hipGetErrorString(e_));                  \
+      return MODLE_PIXELS_ERR_DEVICE;                                                           \
+    }                                                                                           \
+  } while (0)
+
+bool bad_shape(uint64_t nrows, uint64_t ncols) {
+  // (the last two: the grid of pixels_count, x < 2^31 and y < 2^16 blocks)
+  return nrows > ncols || (nrows == 0) != (ncols == 0) ||
+         ncols > static_cast<uint64_t>(std::numeric_limits<int32_t>::max()) * kCountCols ||
+         nrows > 65535ull * kCountDepth;
+}
+
+void free_buffers(modle_pixels_handle* h, bool pixels, bool offsets) {
+  if (pixels) {
+    for (void** p : {&h->d_bin1, &h->d_bin2, &h->d_count}) (void)hipFree(*p), *p = nullptr;
+    for (void** p : {&h->h_bin1, &h->h_bin2, &h->h_count}) (void)hipHostFree(*p), *p = nullptr;
+    h->cap_pixels = 0;
+  }
+  if (offsets) {
+    (void)hipFree(h->d_offsets), h->d_offsets = nullptr;
+    (void)hipHostFree(h->h_offsets), h->h_offsets = nullptr;
+    h->cap_offsets = 0;
+  }
+}
+
+int reserve(modle_pixels_handle* h, uint64_t n_pixels, uint64_t n_offsets, char* err, size_t errlen) {
+  if (n_offsets > h->cap_offsets) {
+    free_buffers(h, false, true);
+    PIX_TRY(hipMalloc(&h->d_offsets, n_offsets * 8));
+    PIX_TRY(hipHostMalloc(&h->h_offsets, n_offsets * 8, hipHostMallocDefault));
+    h->cap_offsets = n_offsets;
+  }
+  if (n_pixels > h->cap_pixels) {
+    free_buffers(h, true, false);
+    const uint64_t n = n_pixels + n_pixels / 8;  // some room: the next interval is rarely the same size
+    PIX_TRY(hipMalloc(&h->d_bin1, n * 8));
+    PIX_TRY(hipMalloc(&h->d_bin2, n * 8));
+    PIX_TRY(hipMalloc(&h->d_count, n * 4));
+    PIX_TRY(hipHostMalloc(&h->h_bin1, n * 8, hipHostMallocDefault));
+    PIX_TRY(hipHostMalloc(&h->h_bin2, n * 8, hipHostMallocDefault));
+    PIX_TRY(hipHostMalloc(&h->h_count, n * 4, hipHostMallocDefault));
+    h->cap_pixels = n;
+  }
+  return MODLE_PIXELS_OK;
+}
+
+int count_impl(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols,
+               int64_t* d_bin1_offset, modle_pixels_stats* stats, hipStream_t stream, char* err,
+               size_t errlen) {
+  PIX_TRY(hipSetDevice(h->device));
+  PIX_TRY(hipMemsetAsync(h->d_stats, 0, sizeof(DeviceStats), stream));
+  PIX_TRY(hipMemsetAsync(d_bin1_offset, 0, (ncols + 1) * 8, stream));
+  auto* offsets = reinterpret_cast<unsigned long long*>(d_bin1_offset);
+  if (ncols != 0) {
+    const dim3 grid(static_cast<unsigned>((ncols + kCountCols - 1) / kCountCols),
+                    static_cast<unsigned>((nrows + kCountDepth - 1) / kCountDepth));
+    hipLaunchKernelGGL(pixels_count, grid, dim3(kCountThreads), 0, stream, d_band, nrows, ncols, offsets,
+                       h->d_stats);
+    PIX_TRY(hipGetLastError());
+    hipLaunchKernelGGL(pixels_scan, dim3(1), dim3(kScanThreads), 0, stream, offsets, ncols, h->d_stats);
+    PIX_TRY(hipGetLastError());
+  }
+  PIX_TRY(hipMemcpyAsync(h->h_stats, h->d_stats, sizeof(DeviceStats), hipMemcpyDeviceToHost, stream));
+  PIX_TRY(hipStreamSynchronize(stream));
+  stats->nnz = h->h_stats->nnz;
+  stats->sum = h->h_stats->sum;
+  stats->max_count = h->h_stats->max_count;
+  stats->reserved_ = 0;
+  if (stats->max_count > static_cast<uint32_t>(std::numeric_limits<int32_t>::max())) {
+    set_err(err, errlen, "modle_pixels: a count does not fit the int32 pixel type");
+    return MODLE_PIXELS_ERR_RANGE;
+  }
+  return MODLE_PIXELS_OK;
+}
+
+int extract_impl(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols,
+                 int64_t bin_offset, const int64_t* d_bin1_offset, int64_t* d_bin1, int64_t* d_bin2,
+                 int32_t* d_count, uint64_t nnz, hipStream_t stream, char* err, size_t errlen) {
+  PIX_TRY(hipSetDevice(h->device));
+  if (nnz == 0 || ncols == 0) return MODLE_PIXELS_OK;
+  const dim3 grid(static_cast<unsigned>((ncols + kRowsPerBlock - 1) / kRowsPerBlock));
+  hipLaunchKernelGGL(pixels_extract, grid, dim3(kExtractThreads), 0, stream, d_band, nrows, ncols, bin_offset,
+                     d_bin1_offset, d_bin1, d_bin2, d_count, nnz);
+  PIX_TRY(hipGetLastError());
+  return MODLE_PIXELS_OK;
+}
+
+}  // namespace
+
+extern "C" int modle_pixels_create(int device, modle_pixels_handle** out, char* err, size_t errlen) {
+  if (out == nullptr || device < 0) {
+    set_err(err, errlen, "modle_pixels_create: invalid argument");
+    return MODLE_PIXELS_ERR_ARG;
+  }
+  *out = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
+    set_err(err, errlen, "modle_pixels_create: no such HIP device (there is no CPU fallback)");
+    return MODLE_PIXELS_ERR_DEVICE;
+  }
+  PIX_TRY(hipSetDevice(device));
+  auto* h = new (std::nothrow) modle_pixels_handle;
+  if (h == nullptr) {
+    set_err(err, errlen, "modle_pixels_create: out of memory");
+    return MODLE_PIXELS_ERR_DEVICE;
+  }
+  h->device = device;
+  if (hipMalloc(reinterpret_cast<void**>(&h->d_stats), sizeof(DeviceStats)) != hipSuccess ||
+      hipHostMalloc(reinterpret_cast<void**>(&h->h_stats), sizeof(DeviceStats), hipHostMallocDefault) !=
+          hipSuccess) {
+    set_err(err, errlen, "modle_pixels_create: cannot allocate the statistics words");
+    modle_pixels_destroy(h);
+    return MODLE_PIXELS_ERR_DEVICE;
+  }
+  *out = h;
+  return MODLE_PIXELS_OK;
+}
+
+extern "C" void modle_pixels_destroy(modle_pixels_handle* h) {
+  if (h == nullptr) return;
+  (void)hipSetDevice(h->device);
+  free_buffers(h, true, true);
+  (void)hipFree(h->d_stats);
+  (void)hipHostFree(h->h_stats);
+  delete h;
+}
+
+extern "C" int modle_pixels_count(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                                  uint64_t ncols, int64_t* d_bin1_offset, modle_pixels_stats* stats,
+                                  void* stream, char* err, size_t errlen) {
+  if (h == nullptr || stats == nullptr || (d_band == nullptr && ncols != 0) || bad_shape(nrows, ncols)) {
+    set_err(err, errlen, "modle_pixels_count: invalid argument (0 < nrows <= ncols, or both 0)");
+    return MODLE_PIXELS_ERR_ARG;
+  }
+  if (d_bin1_offset == nullptr) {  // statistics only: the index goes to the context's own array
+    PIX_TRY(hipSetDevice(h->device));
+    const int rc = reserve(h, 0, ncols + 1, err, errlen);
+    if (rc != MODLE_PIXELS_OK) return rc;
+    d_bin1_offset = static_cast<int64_t*>(h->d_offsets);
+  }
+  return count_impl(h, d_band, nrows, ncols, d_bin1_offset, stats, static_cast<hipStream_t>(stream), err,
+                    errlen);
+}
+
+extern "C" int modle_pixels_extract(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                                    uint64_t ncols, int64_t bin_offset, const int64_t* d_bin1_offset,
+                                    int64_t* d_bin1, int64_t* d_bin2, int32_t* d_count, uint64_t nnz,
+                                    void* stream, char* err, size_t errlen) {
+  if (h == nullptr || d_bin1_offset == nullptr || (d_band == nullptr && ncols != 0) ||
+      bad_shape(nrows, ncols) || bin_offset < 0 ||
+      (nnz != 0 && (d_bin1 == nullptr || d_bin2 == nullptr || d_count == nullptr))) {
+    set_err(err, errlen, "modle_pixels_extract: invalid argument");
+    return MODLE_PIXELS_ERR_ARG;
+  }
+  return extract_impl(h, d_band, nrows, ncols, bin_offset, d_bin1_offset, d_bin1, d_bin2, d_count, nnz,
+                      static_cast<hipStream_t>(stream), err, errlen);
+}
+
+extern "C" int modle_pixels_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                                    uint64_t ncols, int64_t bin_offset, const int64_t** bin1,
+                                    const int64_t** bin2, const int32_t** count,
+                                    const int64_t** bin1_offset, modle_pixels_stats* stats, void* stream,
+                                    char* err, size_t errlen) {
+  if (h == nullptr || bin1 == nullptr || bin2 == nullptr || count == nullptr || bin1_offset == nullptr ||
+      stats == nullptr || (d_band == nullptr && ncols != 0) || bad_shape(nrows, ncols) || bin_offset < 0) {
+    set_err(err, errlen, "modle_pixels_to_host: invalid argument (0 < nrows <= ncols, or both 0)");
+    return MODLE_PIXELS_ERR_ARG;
+  }
+  *bin1 = *bin2 = nullptr;
+  *count = nullptr;
+  *bin1_offset = nullptr;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  PIX_TRY(hipSetDevice(h->device));
+  int rc = reserve(h, 0, ncols + 1, err, errlen);
+  if (rc != MODLE_PIXELS_OK) return rc;
+  rc = count_impl(h, d_band, nrows, ncols, static_cast<int64_t*>(h->d_offsets), stats, st, err, errlen);
+  if (rc != MODLE_PIXELS_OK) return rc;
+  rc = reserve(h, stats->nnz, ncols + 1, err, errlen);
+  if (rc != MODLE_PIXELS_OK) return rc;
+  rc = extract_impl(h, d_band, nrows, ncols, bin_offset, static_cast<const int64_t*>(h->d_offsets),
+                    static_cast<int64_t*>(h->d_bin1), static_cast<int64_t*>(h->d_bin2),
+                    static_cast<int32_t*>(h->d_count), stats->nnz, st, err, errlen);
+  if (rc != MODLE_PIXELS_OK) return rc;
+  PIX_TRY(hipMemcpyAsync(h->h_offsets, h->d_offsets, (ncols + 1) * 8, hipMemcpyDeviceToHost, st));
+  if (stats->nnz != 0) {
+    PIX_TRY(hipMemcpyAsync(h->h_bin1, h->d_bin1, stats->nnz * 8, hipMemcpyDeviceToHost, st));
+    PIX_TRY(hipMemcpyAsync(h->h_bin2, h->d_bin2, stats->nnz * 8, hipMemcpyDeviceToHost, st));
+    PIX_TRY(hipMemcpyAsync(h->h_count, h->d_count, stats->nnz * 4, hipMemcpyDeviceToHost, st));
+  }
+  PIX_TRY(hipStreamSynchronize(st));
+  *bin1_offset = static_cast<const int64_t*>(h->h_offsets);
+  if (stats->nnz != 0) {
+    *bin1 = static_cast<const int64_t*>(h->h_bin1);
+    *bin2 = static_cast<const int64_t*>(h->h_bin2);
+    *count = static_cast<const int32_t*>(h->h_count);
+  }
+  return MODLE_PIXELS_OK;
+}
