@@ -75,6 +75,44 @@ int modle_pixels_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_
                          const int64_t** bin2, const int32_t** count, const int64_t** bin1_offset,
                          modle_pixels_stats* stats, void* stream, char* err, size_t errlen);
 
+/* ---- Coarsening: the same contacts at `factor` times the bin size -------------------------
+ *
+ * `first_bin` is the chromosome-relative index of the interval's first fine bin (offset_bp /
+ * bin_size): coarse bins are anchored at the chromosome's start, not at the interval's.  With
+ * p = first_bin % factor, fine column i belongs to coarse column (i + p) / factor, and coarse pixel
+ * (I, J) is the sum of the fine pixels (i, j) with (i + p) / factor == I and (j + p) / factor == J
+ * (in a diagonal block the upper triangle only, like `cooler coarsen`).  The result is a band in
+ * the layout above, of
+ *     ncols' = (p + ncols + factor - 1) / factor
+ *     nrows' = min(ncols', (nrows - 1 + factor - 1) / factor + 1)
+ * and nrows' * ncols' + 1 words, EVERY one of which is written: pixels hold their sums, the words
+ * that are no pixels (left-edge triangle, trailing word) hold 0; the caller does not pre-zero.
+ * A sum that does not fit 32 bits is stored as 0xFFFFFFFF (saturation), which the range check of
+ * modle_pixels_count then reports.  Coarsening by k1 with first_bin and then by k2 with
+ * first_bin / k1 equals coarsening by k1 * k2 with first_bin.
+ *
+ * `factor` < 2 (or above 2^32), nrows == 0 and nrows > ncols are MODLE_PIXELS_ERR_ARG. */
+
+/* The shape of the coarse band.  Host only: no device is needed. */
+int modle_pixels_coarse_shape(uint64_t nrows, uint64_t ncols, uint64_t factor, uint64_t first_bin,
+                              uint64_t* nrows_out, uint64_t* ncols_out);
+
+/* Enqueues the coarsening of the band at `d_band` into the device array `d_out` of `out_words`
+ * words (>= nrows' * ncols' + 1, else MODLE_PIXELS_ERR_ARG and nothing is written) on `stream`;
+ * the call does not wait.  The input is read, never written, and must not overlap `d_out`. */
+int modle_pixels_coarsen(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                         uint64_t ncols, uint64_t factor, uint64_t first_bin, uint32_t* d_out,
+                         uint64_t out_words, void* stream, char* err, size_t errlen);
+
+/* One call: coarsen into a scratch band owned by the context (grown on demand, freed by
+ * modle_pixels_destroy), then modle_pixels_to_host on it.  `bin_offset` is the interval's first
+ * bin within the COARSE file; *bin1_offset has ncols' + 1 entries. */
+int modle_pixels_coarse_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                                uint64_t ncols, uint64_t factor, uint64_t first_bin,
+                                int64_t bin_offset, const int64_t** bin1, const int64_t** bin2,
+                                const int32_t** count, const int64_t** bin1_offset,
+                                modle_pixels_stats* stats, void* stream, char* err, size_t errlen);
+
 #ifdef __cplusplus
 }
 #endif

@@ -273,6 +273,17 @@ class Simulator:
         d_contacts, _, nrows, ncols = self.outputs(interval_id)
         return pixels.extract(d_contacts, nrows, ncols, bin_offset, stream, device=self.device)
 
+    def coarse_pixels(self, interval_id, factor, first_bin, bin_offset=0, stream=None):
+        """`pixels` at `factor` times the bin size: the band is coarsened on the device
+        (pixels.coarse_extract) and the pixels of the coarse band come back.  `first_bin`: the
+        interval's first bin within its chromosome (start / bin_size), which anchors the coarse bins
+        at the chromosome's start; `bin_offset`: its first bin within the coarse file."""
+        from . import pixels
+
+        d_contacts, _, nrows, ncols = self.outputs(interval_id)
+        return pixels.coarse_extract(d_contacts, nrows, ncols, factor, first_bin, bin_offset, stream,
+                                     device=self.device)
+
     def simulate_interval(self, start, end, bar_pos, bar_dir, stp_active, stp_inactive, tasks):
         """One-call seam (modle_hip_simulate_interval): returns contacts, missed, occupancy,
         results."""

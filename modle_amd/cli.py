@@ -5,7 +5,8 @@
 Option names, defaults and the derivation of the dependent parameters follow the reference's
 `modle simulate` (reference: src/modle/cli.cpp:53-602 options, :886-1016 transform_args); the
 task derivation is `run_simulate`'s (src/libmodle/cpu/scheduler_simulate.cpp:43-170) and the
-outputs are the reference's: `<prefix>.cool` and, with the 1-D LEF position track on,
+outputs are the reference's: `<prefix>.cool` (with --mcool-resolutions `<prefix>.mcool`: the same
+contacts at several bin sizes, coarsened on the GPU) and, with the 1-D LEF position track on,
 `<prefix>_lef_1d_occupancy.bw` (cli.cpp:867-882).  Everything heavy is native: parsing and
 task generation in libmodle_hip.so (host), the simulation on the MI355X (one process per GPU;
 under torch.distributed.run the cells are sharded over the ranks and the matrices are summed
@@ -63,6 +64,27 @@ def genomic_distance(text):
     return int(m)
 
 
+def resolution_list(text):
+    """`10kb,25kb,100kb`: comma-separated genomic distances (--mcool-resolutions)"""
+    items = [t.strip() for t in text.split(",")]
+    if not text.strip() or any(not t for t in items):
+        raise argparse.ArgumentTypeError(f"{text!r} is not a comma-separated list of resolutions")
+    return [genomic_distance(t) for t in items]
+
+
+def mcool_bin_sizes(resolutions, base):
+    """the bin sizes of the .mcool: the base (-r) and the listed resolutions, sorted, without
+    duplicates.  Every listed one must be a multiple of the base and larger than it."""
+    base = int(base)
+    for r in resolutions:
+        if r <= base or r % base != 0:
+            raise SystemExit(f"--mcool-resolutions: {r} is not a multiple of the resolution ({base}) "
+                             "that is larger than it")
+        if r >= 2**32:
+            raise SystemExit(f"--mcool-resolutions: {r} does not fit the 32-bit bin size of a cooler")
+    return [base] + sorted(set(resolutions))
+
+
 def build_parser():
     ap = argparse.ArgumentParser(prog="modle_amd", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -78,6 +100,10 @@ def build_parser():
     io.add_argument("-q", "--quiet", action="store_true")
     io.add_argument("-v", "--verbose", action="store_true", help="accepted (the log is short anyway)")
     io.add_argument("--skip-output", action="store_true")
+    io.add_argument("--mcool-resolutions", type=resolution_list, default=None, metavar="LIST",
+                    help="write <prefix>.mcool instead of <prefix>.cool: the matrix at the resolution "
+                         "(-r), which need not be listed, and at every bin size of the comma-separated "
+                         "LIST (e.g. 10kb,25kb,100kb; multiples of -r), coarsened on the GPU")
     io.add_argument("--log-model-internal-state", action="store_true",
                     help="write <prefix>_internal_state.log.gz: one line of statistics per task and "
                          "epoch (uses the diagnostic build libmodle_hip_statelog.so)")
@@ -186,8 +212,8 @@ def config_from_args(a):
     return api.make_config(**over)
 
 
-def output_paths(prefix):
-    return prefix + ".cool", prefix + "_lef_1d_occupancy.bw"
+def output_paths(prefix, mcool=False):
+    return prefix + (".mcool" if mcool else ".cool"), prefix + "_lef_1d_occupancy.bw"
 
 
 def state_log_path(prefix):
@@ -196,7 +222,9 @@ def state_log_path(prefix):
 
 def simulate(a, log=print):
     cfg = config_from_args(a)
-    cool_path, bw_path = output_paths(a.output_prefix)
+    # (a bad list ends the run here, before anything is imported or simulated)
+    bin_sizes = None if a.mcool_resolutions is None else mcool_bin_sizes(a.mcool_resolutions, cfg.bin_size)
+    cool_path, bw_path = output_paths(a.output_prefix, mcool=bin_sizes is not None)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     device = a.device if a.device is not None else int(os.environ.get("LOCAL_RANK", "0"))
@@ -211,6 +239,11 @@ def simulate(a, log=print):
     log(f"imported {len(chroms)} chromosomes, {len(intervals)} intervals, "
         f"{stats['barriers_imported']} barriers ({stats['barriers_without_strand']} without strand dropped)")
     plan = driver.plan_genome(cfg, intervals, rank, world)
+    if bin_sizes is not None and not a.skip_output:
+        hit = driver.mcool_collision(plan, int(cfg.bin_size), bin_sizes)
+        if hit is not None:
+            raise SystemExit(f"--mcool-resolutions: the intervals {hit[1]} and {hit[2]} share a bin at "
+                             f"resolution {hit[0]}: its pixels would not be sorted and unique")
     use_dist = world > 1
     if use_dist:
         import torch
@@ -289,12 +322,24 @@ def simulate(a, log=print):
             warn_missing(k, px[4])
             return px
 
+        def extract_at(k, factor, first_bin, bin_offset):
+            # the coarse resolutions of the .mcool: summed on the device from the same matrix (with
+            # several ranks: from the reduced tensor, like the pixels of the base resolution)
+            if factor == 1:
+                return extract(k, bin_offset)
+            if ids[k] is None:
+                return None
+            return sim.coarse_pixels(ids[k], factor, first_bin, bin_offset)
+
         if rank == 0 and not a.skip_output:
             meta = json.dumps({k: v for k, v in vars(a).items() if v is not None and k != "command"},
                               sort_keys=True)
-            driver.write_cooler_pixels(cool_path, cfg, plan, extract, assembly=a.assembly_name,
-                                       generated_by="modle_amd (MI355X)", metadata_json=meta,
-                                       force_overwrite=a.force, chroms=chroms)
+            kw = dict(assembly=a.assembly_name, generated_by="modle_amd (MI355X)", metadata_json=meta,
+                      force_overwrite=a.force, chroms=chroms)
+            if bin_sizes is None:
+                driver.write_cooler_pixels(cool_path, cfg, plan, extract, **kw)
+            else:
+                driver.write_mcool_pixels(cool_path, cfg, plan, extract_at, bin_sizes, **kw)
             log(f"written {cool_path}")
         elif rank == 0:
             for k, iid in enumerate(ids):  # --skip-output: nothing is extracted, only summed

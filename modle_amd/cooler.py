@@ -38,6 +38,16 @@ def lib():
             ctypes.c_size_t]
         lb.modle_cool_close.restype = ctypes.c_int
         lb.modle_cool_close.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+        lb.modle_mcool_create.restype = ctypes.c_int  # include/modle_mcool.h
+        lb.modle_mcool_create.argtypes = [
+            ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p),
+            ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32),
+            ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
+            ctypes.POINTER(ctypes.c_void_p), ctypes.c_char_p, ctypes.c_size_t]
+        lb.modle_mcool_resolution.restype = ctypes.c_void_p
+        lb.modle_mcool_resolution.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
+        lb.modle_mcool_close.restype = ctypes.c_int
+        lb.modle_mcool_close.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
         _LIB = lb
     return _LIB
 
@@ -48,22 +58,13 @@ class CoolerError(RuntimeError):
         self.code = code
 
 
-class CoolerWriter:
-    """`chroms`: list of (name, size); matrices are appended in ascending chromosome order."""
+class _Cooler:
+    """One cooler behind a modle_cool_file handle: a file of its own (CoolerWriter) or one
+    resolution of a multi-resolution file (McoolWriter.resolution)."""
 
-    def __init__(self, path, chroms, bin_size, assembly="unknown", generated_by="modle-hip",
-                 metadata_json="", force_overwrite=False):
-        names = (ctypes.c_char_p * len(chroms))(*[n.encode() for n, _ in chroms])
-        sizes = (ctypes.c_uint32 * len(chroms))(*[int(s) for _, s in chroms])
-        self._h = ctypes.c_void_p()
+    def __init__(self, handle, chroms):
+        self._h = handle
         self._err = ctypes.create_string_buffer(512)
-        rc = lib().modle_cool_create(os.fsencode(path), int(force_overwrite), names, sizes,
-                                     len(chroms), int(bin_size), assembly.encode(),
-                                     generated_by.encode(), metadata_json.encode(),
-                                     ctypes.byref(self._h), self._err, len(self._err))
-        if rc != 0:
-            self._h = None
-            raise CoolerError(rc, self._err.value.decode())
         self._index = {n: i for i, (n, _) in enumerate(chroms)}
 
     def append(self, chrom, band, nrows, ncols, offset_bp=0):
@@ -112,10 +113,76 @@ class CoolerWriter:
         if rc != 0:
             raise CoolerError(rc, self._err.value.decode())
 
+
+class CoolerWriter(_Cooler):
+    """`chroms`: list of (name, size); matrices are appended in ascending chromosome order."""
+
+    def __init__(self, path, chroms, bin_size, assembly="unknown", generated_by="modle-hip",
+                 metadata_json="", force_overwrite=False):
+        names = (ctypes.c_char_p * len(chroms))(*[n.encode() for n, _ in chroms])
+        sizes = (ctypes.c_uint32 * len(chroms))(*[int(s) for _, s in chroms])
+        self._h = ctypes.c_void_p()
+        self._err = ctypes.create_string_buffer(512)
+        rc = lib().modle_cool_create(os.fsencode(path), int(force_overwrite), names, sizes,
+                                     len(chroms), int(bin_size), assembly.encode(),
+                                     generated_by.encode(), metadata_json.encode(),
+                                     ctypes.byref(self._h), self._err, len(self._err))
+        if rc != 0:
+            self._h = None
+            raise CoolerError(rc, self._err.value.decode())
+        self._index = {n: i for i, (n, _) in enumerate(chroms)}
+
     def close(self):
         if self._h is not None:
             h, self._h = self._h, None
             rc = lib().modle_cool_close(h, self._err, len(self._err))
+            if rc != 0:
+                raise CoolerError(rc, self._err.value.decode())
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+class McoolWriter:
+    """A multi-resolution cooler (include/modle_mcool.h): one cooler per entry of `bin_sizes`
+    (ascending, distinct multiples of the first) under /resolutions/<bin size>.  `resolution(b)`
+    is written like a CoolerWriter of bin size `b` (bin_offset, append_pixels, append), in genome
+    order per resolution; `close` finishes all of them."""
+
+    def __init__(self, path, chroms, bin_sizes, assembly="unknown", generated_by="modle-hip",
+                 metadata_json="", force_overwrite=False):
+        bin_sizes = [int(b) for b in bin_sizes]
+        if any(not 0 <= b < 2**32 for b in bin_sizes):
+            raise CoolerError(-1, "modle_mcool_create: a bin size does not fit 32 bits")
+        names = (ctypes.c_char_p * len(chroms))(*[n.encode() for n, _ in chroms])
+        sizes = (ctypes.c_uint32 * len(chroms))(*[int(s) for _, s in chroms])
+        res = (ctypes.c_uint32 * len(bin_sizes))(*bin_sizes)
+        self._h = ctypes.c_void_p()
+        self._err = ctypes.create_string_buffer(512)
+        rc = lib().modle_mcool_create(os.fsencode(path), int(force_overwrite), names, sizes,
+                                      len(chroms), res, len(bin_sizes), assembly.encode(),
+                                      generated_by.encode(), metadata_json.encode(),
+                                      ctypes.byref(self._h), self._err, len(self._err))
+        if rc != 0:
+            self._h = None
+            raise CoolerError(rc, self._err.value.decode())
+        self.bin_sizes = bin_sizes
+        self._res = {b: _Cooler(ctypes.c_void_p(lib().modle_mcool_resolution(self._h, k)), chroms)
+                     for k, b in enumerate(bin_sizes)}
+
+    def resolution(self, bin_size):
+        return self._res[int(bin_size)]
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            for r in self._res.values():
+                r._h = None  # borrowed handles: gone with the file
+            rc = lib().modle_mcool_close(h, self._err, len(self._err))
             if rc != 0:
                 raise CoolerError(rc, self._err.value.decode())
 

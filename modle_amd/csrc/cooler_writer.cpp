@@ -5,6 +5,10 @@
 // bins/{chrom, start, end (int32)}, pixels/{bin1_id, bin2_id (int64), count (int32)},
 // indexes/{bin1_offset, chrom_offset (int64)}; chunked, deflate level 6; attributes of
 // cooler/cooler.hpp:50-73 / file_write_impl.hpp:297-330.
+//
+// A cooler lives at a location: the root of its own file (modle_cool_create), or the group
+// /resolutions/<bin size> of a multi-resolution file (include/modle_mcool.h; the root attributes
+// are those of hictk's MultiResFile::create, cooler/impl/multires_cooler_impl.hpp:60-82).
 #include <hdf5.h>
 
 #include <algorithm>
@@ -17,6 +21,7 @@
 
 #include "modle_cooler.h"
 #include "modle_cooler_pixels.h"
+#include "modle_mcool.h"
 
 namespace {
 
@@ -81,7 +86,8 @@ bool write_attr_string(hid_t loc, const char* name, const std::string& v) {
 }  // namespace
 
 struct modle_cool_file {
-  hid_t file = -1;
+  hid_t file = -1;  // the file, where the handle owns it (-1: a resolution of a modle_mcool_file)
+  hid_t loc = -1;   // where the cooler lives: `file`, or a group that the handle owns
   hid_t d_bin1 = -1, d_bin2 = -1, d_count = -1;
   hsize_t n_pixels = 0;
   uint32_t bin_size = 0;
@@ -100,6 +106,7 @@ void destroy(modle_cool_file* f) {
   if (f == nullptr) return;
   for (hid_t d : {f->d_bin1, f->d_bin2, f->d_count})
     if (d >= 0) H5Dclose(d);
+  if (f->loc >= 0 && f->loc != f->file) H5Gclose(f->loc);
   if (f->file >= 0) H5Fclose(f->file);
   delete f;
 }
@@ -113,27 +120,20 @@ bool write_whole(hid_t file, const char* path, hid_t filetype, hid_t memtype, co
 
 }  // namespace
 
-extern "C" int modle_cool_create(const char* path, int force_overwrite,
-                                 const char* const* chrom_names, const uint32_t* chrom_sizes,
-                                 size_t n_chroms, uint32_t bin_size, const char* assembly,
-                                 const char* generated_by, const char* metadata_json,
-                                 modle_cool_file** out, char* err, size_t errlen) {
-  if (path == nullptr || chrom_names == nullptr || chrom_sizes == nullptr || n_chroms == 0 ||
-      bin_size == 0 || out == nullptr || assembly == nullptr || generated_by == nullptr ||
-      assembly[0] == '\0' || generated_by[0] == '\0') {
-    set_err(err, errlen, "modle_cool_create: invalid argument");
-    return MODLE_COOL_ERR_ARG;
-  }
-  *out = nullptr;
-  H5Eset_auto2(H5E_DEFAULT, nullptr, nullptr);  // errors are reported through return codes
-  auto* f = new modle_cool_file;
-  f->file = H5Fcreate(path, force_overwrite ? H5F_ACC_TRUNC : H5F_ACC_EXCL, H5P_DEFAULT, H5P_DEFAULT);
-  if (f->file < 0) {
-    set_err(err, errlen, std::string("cannot create \"") + path + "\"" +
-                             (force_overwrite ? "" : " (file exists? pass force_overwrite)"));
-    destroy(f);
-    return MODLE_COOL_ERR_IO;
-  }
+namespace {
+
+bool bad_create_args(const char* path, const char* const* chrom_names, const uint32_t* chrom_sizes,
+                     size_t n_chroms, const char* assembly, const char* generated_by) {
+  return path == nullptr || chrom_names == nullptr || chrom_sizes == nullptr || n_chroms == 0 ||
+         assembly == nullptr || generated_by == nullptr || assembly[0] == '\0' || generated_by[0] == '\0';
+}
+
+// groups, chroms, bins and the empty pixel tables of one cooler at f->loc; on an error the
+// caller destroys `f`
+int init_cooler(modle_cool_file* f, const char* path, const char* const* chrom_names,
+                const uint32_t* chrom_sizes, size_t n_chroms, uint32_t bin_size, const char* assembly,
+                const char* generated_by, const char* metadata_json, const char* who, char* err,
+                size_t errlen) {
   f->bin_size = bin_size;
   f->assembly = assembly;
   f->generated_by = generated_by;
@@ -142,7 +142,7 @@ extern "C" int modle_cool_create(const char* path, int force_overwrite,
 
   bool ok = true;
   for (const char* g : {"chroms", "bins", "pixels", "indexes"}) {
-    H5Id grp(H5Gcreate2(f->file, g, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT), H5Gclose);
+    H5Id grp(H5Gcreate2(f->loc, g, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT), H5Gclose);
     ok = ok && grp >= 0;
   }
   // chroms
@@ -150,8 +150,7 @@ extern "C" int modle_cool_create(const char* path, int force_overwrite,
   for (size_t i = 0; i < n_chroms; ++i) {
     if (chrom_names[i] == nullptr || chrom_names[i][0] == '\0' ||
         chrom_sizes[i] > static_cast<uint32_t>(std::numeric_limits<int32_t>::max())) {
-      set_err(err, errlen, "modle_cool_create: invalid chromosome name or size");
-      destroy(f);
+      set_err(err, errlen, std::string(who) + ": invalid chromosome name or size");
       return MODLE_COOL_ERR_ARG;
     }
     longest = std::max(longest, std::strlen(chrom_names[i]));
@@ -161,11 +160,11 @@ extern "C" int modle_cool_create(const char* path, int force_overwrite,
     for (size_t i = 0; i < n_chroms; ++i) std::memcpy(&names[i * longest], chrom_names[i], std::strlen(chrom_names[i]));
     H5Id stype(H5Tcopy(H5T_C_S1), H5Tclose);
     ok = ok && stype >= 0 && H5Tset_size(stype, longest) >= 0 && H5Tset_strpad(stype, H5T_STR_NULLPAD) >= 0;
-    H5Id d(ok ? create_dataset(f->file, "chroms/name", stype) : -1, H5Dclose);
+    H5Id d(ok ? create_dataset(f->loc, "chroms/name", stype) : -1, H5Dclose);
     hsize_t size = 0;
     ok = ok && d >= 0 && append(d, stype, names.data(), n_chroms, size);
     std::vector<int32_t> lengths(f->chrom_sizes.begin(), f->chrom_sizes.end());
-    ok = ok && write_whole(f->file, "chroms/length", H5T_STD_I32LE, H5T_NATIVE_INT32, lengths);
+    ok = ok && write_whole(f->loc, "chroms/length", H5T_STD_I32LE, H5T_NATIVE_INT32, lengths);
   }
   // bins (fixed size; the last bin of a chromosome is shorter)
   {
@@ -179,19 +178,53 @@ extern "C" int modle_cool_create(const char* path, int force_overwrite,
       }
       f->chrom_offset.push_back(static_cast<int64_t>(chrom.size()));
     }
-    ok = ok && write_whole(f->file, "bins/chrom", H5T_STD_I32LE, H5T_NATIVE_INT32, chrom);
-    ok = ok && write_whole(f->file, "bins/start", H5T_STD_I32LE, H5T_NATIVE_INT32, start);
-    ok = ok && write_whole(f->file, "bins/end", H5T_STD_I32LE, H5T_NATIVE_INT32, end);
+    ok = ok && write_whole(f->loc, "bins/chrom", H5T_STD_I32LE, H5T_NATIVE_INT32, chrom);
+    ok = ok && write_whole(f->loc, "bins/start", H5T_STD_I32LE, H5T_NATIVE_INT32, start);
+    ok = ok && write_whole(f->loc, "bins/end", H5T_STD_I32LE, H5T_NATIVE_INT32, end);
     f->bin1_offset.assign(chrom.size() + 1, 0);
   }
-  f->d_bin1 = create_dataset(f->file, "pixels/bin1_id", H5T_STD_I64LE);
-  f->d_bin2 = create_dataset(f->file, "pixels/bin2_id", H5T_STD_I64LE);
-  f->d_count = create_dataset(f->file, "pixels/count", H5T_STD_I32LE);
+  f->d_bin1 = create_dataset(f->loc, "pixels/bin1_id", H5T_STD_I64LE);
+  f->d_bin2 = create_dataset(f->loc, "pixels/bin2_id", H5T_STD_I64LE);
+  f->d_count = create_dataset(f->loc, "pixels/count", H5T_STD_I32LE);
   ok = ok && f->d_bin1 >= 0 && f->d_bin2 >= 0 && f->d_count >= 0;
   if (!ok) {
     set_err(err, errlen, std::string("HDF5 error while initialising \"") + path + "\"");
-    destroy(f);
     return MODLE_COOL_ERR_IO;
+  }
+  return MODLE_COOL_OK;
+}
+
+hid_t create_file(const char* path, int force_overwrite, char* err, size_t errlen) {
+  H5Eset_auto2(H5E_DEFAULT, nullptr, nullptr);  // errors are reported through return codes
+  const hid_t file = H5Fcreate(path, force_overwrite ? H5F_ACC_TRUNC : H5F_ACC_EXCL, H5P_DEFAULT, H5P_DEFAULT);
+  if (file < 0)
+    set_err(err, errlen, std::string("cannot create \"") + path + "\"" +
+                             (force_overwrite ? "" : " (file exists? pass force_overwrite)"));
+  return file;
+}
+
+}  // namespace
+
+extern "C" int modle_cool_create(const char* path, int force_overwrite,
+                                 const char* const* chrom_names, const uint32_t* chrom_sizes,
+                                 size_t n_chroms, uint32_t bin_size, const char* assembly,
+                                 const char* generated_by, const char* metadata_json,
+                                 modle_cool_file** out, char* err, size_t errlen) {
+  if (bad_create_args(path, chrom_names, chrom_sizes, n_chroms, assembly, generated_by) || bin_size == 0 ||
+      out == nullptr) {
+    set_err(err, errlen, "modle_cool_create: invalid argument");
+    return MODLE_COOL_ERR_ARG;
+  }
+  *out = nullptr;
+  const hid_t file = create_file(path, force_overwrite, err, errlen);
+  if (file < 0) return MODLE_COOL_ERR_IO;
+  auto* f = new modle_cool_file;
+  f->file = f->loc = file;
+  const int rc = init_cooler(f, path, chrom_names, chrom_sizes, n_chroms, bin_size, assembly, generated_by,
+                             metadata_json, "modle_cool_create", err, errlen);
+  if (rc != MODLE_COOL_OK) {
+    destroy(f);
+    return rc;
   }
   *out = f;
   return MODLE_COOL_OK;
@@ -332,15 +365,14 @@ extern "C" int modle_cool_append_pixels(modle_cool_file* f, size_t chrom_id, uin
   return MODLE_COOL_OK;
 }
 
-extern "C" int modle_cool_close(modle_cool_file* f, char* err, size_t errlen) {
-  if (f == nullptr) {
-    set_err(err, errlen, "modle_cool_close: invalid argument");
-    return MODLE_COOL_ERR_ARG;
-  }
+namespace {
+
+// the indexes and the attributes of the cooler at f->loc
+bool finish_cooler(modle_cool_file* f) {
   for (size_t b = static_cast<size_t>(f->next_bin1); b < f->bin1_offset.size(); ++b)
     f->bin1_offset[b] = static_cast<int64_t>(f->n_pixels);
-  bool ok = write_whole(f->file, "indexes/bin1_offset", H5T_STD_I64LE, H5T_NATIVE_INT64, f->bin1_offset);
-  ok = ok && write_whole(f->file, "indexes/chrom_offset", H5T_STD_I64LE, H5T_NATIVE_INT64, f->chrom_offset);
+  bool ok = write_whole(f->loc, "indexes/bin1_offset", H5T_STD_I64LE, H5T_NATIVE_INT64, f->bin1_offset);
+  ok = ok && write_whole(f->loc, "indexes/chrom_offset", H5T_STD_I64LE, H5T_NATIVE_INT64, f->chrom_offset);
   char date[64];
   {
     const std::time_t t = std::time(nullptr);
@@ -353,23 +385,125 @@ extern "C" int modle_cool_close(modle_cool_file* f, char* err, size_t errlen) {
   const int64_t nbins = static_cast<int64_t>(f->bin1_offset.size()) - 1;
   const int32_t nchroms = static_cast<int32_t>(f->chrom_sizes.size());
   const int64_t nnz = static_cast<int64_t>(f->n_pixels);
-  ok = ok && write_attr_string(f->file, "assembly", f->assembly);
-  ok = ok && write_attr_scalar(f->file, "bin-size", H5T_STD_U32LE, H5T_NATIVE_UINT32, &bin_size);
-  ok = ok && write_attr_string(f->file, "bin-type", "fixed");
-  ok = ok && write_attr_string(f->file, "creation-date", date);
-  ok = ok && write_attr_string(f->file, "format", "HDF5::Cooler");
-  ok = ok && write_attr_string(f->file, "format-url", "https://github.com/open2c/cooler");
-  ok = ok && write_attr_scalar(f->file, "format-version", H5T_STD_U8LE, H5T_NATIVE_UINT8, &version);
-  ok = ok && write_attr_string(f->file, "generated-by", f->generated_by);
-  ok = ok && write_attr_string(f->file, "metadata", f->metadata);
-  ok = ok && write_attr_scalar(f->file, "nbins", H5T_STD_I64LE, H5T_NATIVE_INT64, &nbins);
-  ok = ok && write_attr_scalar(f->file, "nchroms", H5T_STD_I32LE, H5T_NATIVE_INT32, &nchroms);
-  ok = ok && write_attr_scalar(f->file, "nnz", H5T_STD_I64LE, H5T_NATIVE_INT64, &nnz);
-  ok = ok && write_attr_string(f->file, "storage-mode", "symmetric-upper");
-  ok = ok && write_attr_scalar(f->file, "sum", H5T_STD_I64LE, H5T_NATIVE_INT64, &f->sum);
-  ok = ok && write_attr_scalar(f->file, "cis", H5T_STD_I64LE, H5T_NATIVE_INT64, &f->cis);
+  ok = ok && write_attr_string(f->loc, "assembly", f->assembly);
+  ok = ok && write_attr_scalar(f->loc, "bin-size", H5T_STD_U32LE, H5T_NATIVE_UINT32, &bin_size);
+  ok = ok && write_attr_string(f->loc, "bin-type", "fixed");
+  ok = ok && write_attr_string(f->loc, "creation-date", date);
+  ok = ok && write_attr_string(f->loc, "format", "HDF5::Cooler");
+  ok = ok && write_attr_string(f->loc, "format-url", "https://github.com/open2c/cooler");
+  ok = ok && write_attr_scalar(f->loc, "format-version", H5T_STD_U8LE, H5T_NATIVE_UINT8, &version);
+  ok = ok && write_attr_string(f->loc, "generated-by", f->generated_by);
+  ok = ok && write_attr_string(f->loc, "metadata", f->metadata);
+  ok = ok && write_attr_scalar(f->loc, "nbins", H5T_STD_I64LE, H5T_NATIVE_INT64, &nbins);
+  ok = ok && write_attr_scalar(f->loc, "nchroms", H5T_STD_I32LE, H5T_NATIVE_INT32, &nchroms);
+  ok = ok && write_attr_scalar(f->loc, "nnz", H5T_STD_I64LE, H5T_NATIVE_INT64, &nnz);
+  ok = ok && write_attr_string(f->loc, "storage-mode", "symmetric-upper");
+  ok = ok && write_attr_scalar(f->loc, "sum", H5T_STD_I64LE, H5T_NATIVE_INT64, &f->sum);
+  ok = ok && write_attr_scalar(f->loc, "cis", H5T_STD_I64LE, H5T_NATIVE_INT64, &f->cis);
+  return ok;
+}
+
+}  // namespace
+
+extern "C" int modle_cool_close(modle_cool_file* f, char* err, size_t errlen) {
+  if (f == nullptr || f->file < 0) {  // (a resolution of a modle_mcool_file is closed with its file)
+    set_err(err, errlen, "modle_cool_close: invalid argument");
+    return MODLE_COOL_ERR_ARG;
+  }
+  bool ok = finish_cooler(f);
   ok = ok && H5Fflush(f->file, H5F_SCOPE_GLOBAL) >= 0;
   destroy(f);
+  if (!ok) {
+    set_err(err, errlen, "HDF5 error while finalising the file");
+    return MODLE_COOL_ERR_IO;
+  }
+  return MODLE_COOL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Multi-resolution files (include/modle_mcool.h): one cooler per bin size under /resolutions.
+// ---------------------------------------------------------------------------------------------
+struct modle_mcool_file {
+  hid_t file = -1;
+  std::vector<modle_cool_file*> resolutions;  // ascending bin size
+};
+
+namespace {
+void destroy(modle_mcool_file* m) {
+  if (m == nullptr) return;
+  for (modle_cool_file* f : m->resolutions) destroy(f);
+  if (m->file >= 0) H5Fclose(m->file);
+  delete m;
+}
+}  // namespace
+
+extern "C" int modle_mcool_create(const char* path, int force_overwrite, const char* const* chrom_names,
+                                  const uint32_t* chrom_sizes, size_t n_chroms, const uint32_t* bin_sizes,
+                                  size_t n_res, const char* assembly, const char* generated_by,
+                                  const char* metadata_json, modle_mcool_file** out, char* err,
+                                  size_t errlen) {
+  if (bad_create_args(path, chrom_names, chrom_sizes, n_chroms, assembly, generated_by) ||
+      bin_sizes == nullptr || n_res == 0 || out == nullptr) {
+    set_err(err, errlen, "modle_mcool_create: invalid argument");
+    return MODLE_COOL_ERR_ARG;
+  }
+  *out = nullptr;
+  for (size_t r = 0; r < n_res; ++r) {
+    if (bin_sizes[0] == 0 || bin_sizes[r] % bin_sizes[0] != 0 || (r != 0 && bin_sizes[r] <= bin_sizes[r - 1])) {
+      set_err(err, errlen, "modle_mcool_create: the bin sizes must be ascending, distinct multiples of the first");
+      return MODLE_COOL_ERR_ARG;
+    }
+  }
+  auto* m = new modle_mcool_file;
+  m->file = create_file(path, force_overwrite, err, errlen);
+  if (m->file < 0) {
+    destroy(m);
+    return MODLE_COOL_ERR_IO;
+  }
+  const int64_t version = 2;
+  bool ok = write_attr_string(m->file, "format", "HDF5::MCOOL");
+  ok = ok && write_attr_scalar(m->file, "format-version", H5T_STD_I64LE, H5T_NATIVE_INT64, &version);
+  ok = ok && write_attr_string(m->file, "bin-type", "fixed");
+  {
+    H5Id grp(H5Gcreate2(m->file, "resolutions", H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT), H5Gclose);
+    ok = ok && grp >= 0;
+  }
+  int rc = ok ? MODLE_COOL_OK : MODLE_COOL_ERR_IO;
+  if (!ok) set_err(err, errlen, std::string("HDF5 error while initialising \"") + path + "\"");
+  for (size_t r = 0; r < n_res && rc == MODLE_COOL_OK; ++r) {
+    auto* f = new modle_cool_file;
+    m->resolutions.push_back(f);
+    f->loc = H5Gcreate2(m->file, ("resolutions/" + std::to_string(bin_sizes[r])).c_str(), H5P_DEFAULT,
+                        H5P_DEFAULT, H5P_DEFAULT);
+    if (f->loc < 0) {
+      set_err(err, errlen, std::string("HDF5 error while initialising \"") + path + "\"");
+      rc = MODLE_COOL_ERR_IO;
+      break;
+    }
+    rc = init_cooler(f, path, chrom_names, chrom_sizes, n_chroms, bin_sizes[r], assembly, generated_by,
+                     metadata_json, "modle_mcool_create", err, errlen);
+  }
+  if (rc != MODLE_COOL_OK) {
+    destroy(m);
+    return rc;
+  }
+  *out = m;
+  return MODLE_COOL_OK;
+}
+
+extern "C" modle_cool_file* modle_mcool_resolution(modle_mcool_file* m, size_t index) {
+  return (m == nullptr || index >= m->resolutions.size()) ? nullptr : m->resolutions[index];
+}
+
+extern "C" int modle_mcool_close(modle_mcool_file* m, char* err, size_t errlen) {
+  if (m == nullptr) {
+    set_err(err, errlen, "modle_mcool_close: invalid argument");
+    return MODLE_COOL_ERR_ARG;
+  }
+  bool ok = true;
+  for (modle_cool_file* f : m->resolutions) ok = finish_cooler(f) && ok;
+  ok = ok && H5Fflush(m->file, H5F_SCOPE_GLOBAL) >= 0;
+  destroy(m);
   if (!ok) {
     set_err(err, errlen, "HDF5 error while finalising the file");
     return MODLE_COOL_ERR_IO;

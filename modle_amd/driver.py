@@ -189,6 +189,66 @@ def write_cooler_pixels(path, cfg, plan, extract, assembly="unknown", generated_
                             offset_bp=int(iv["start"]))
 
 
+def coarse_bin_range(first_bin, ncols, factor):
+    """first and last coarse bin, within the chromosome, of the `ncols` fine bins from `first_bin`
+    (coarse bins are anchored at the chromosome's start: include/modle_pixels.h)"""
+    return first_bin // factor, (first_bin + ncols - 1) // factor
+
+
+def mcool_collision(plan, base, bin_sizes):
+    """The first (resolution, name of interval a, name of interval b) at which two intervals of one
+    chromosome that have a matrix touch the same coarse bin -- the pixel table of that resolution
+    would not be sorted and unique -- or None.  Names are `chrom:start-end`."""
+    for b in bin_sizes:
+        last = None  # (chromosome, last coarse bin, name) of the interval before
+        for entry in plan:
+            iv = entry["interval"]
+            if entry["skipped"] or entry["ncols"] == 0:
+                continue
+            lo, hi = coarse_bin_range(int(iv["start"]) // base, entry["ncols"], b // base)
+            name = f"{iv['name']}:{iv['start']}-{iv['end']}"
+            if last is not None and last[0] == iv["name"] and lo <= last[1]:
+                return b, last[2], name
+            last = (iv["name"], hi, name)
+    return None
+
+
+def write_mcool_pixels(path, cfg, plan, extract, bin_sizes, assembly="unknown", generated_by="modle-hip",
+                       metadata_json="", force_overwrite=False, chroms=None):
+    """write_cooler_pixels for a multi-resolution file: one cooler per entry of `bin_sizes`
+    (ascending; the first is cfg.bin_size, the others multiples of it) under
+    /resolutions/<bin size>.  For every entry of the plan that is not skipped, in genome order,
+    `extract(k, factor, first_bin, bin_offset)` is called once per resolution and returns the
+    sorted non-zero pixels of plan entry k at `factor` times the bin size, with `bin_offset` (the
+    interval's first bin within that resolution) added to the ids -- what api.Simulator.pixels
+    (factor == 1, the existing path) and api.Simulator.coarse_pixels return -- or None.
+    `first_bin` is the interval's first fine bin within its chromosome.  One interval's pixels of
+    one resolution are on the host at a time."""
+    from . import cooler
+
+    base = int(cfg.bin_size)
+    bin_sizes = [int(b) for b in bin_sizes]
+    if not bin_sizes or bin_sizes[0] != base:
+        raise ValueError("write_mcool_pixels: bin_sizes must start with the simulation's bin size")
+    if chroms is None:
+        chroms = _chroms_of_plan(plan)
+    with cooler.McoolWriter(path, chroms, bin_sizes, assembly=assembly, generated_by=generated_by,
+                            metadata_json=metadata_json, force_overwrite=force_overwrite) as w:
+        for k, entry in enumerate(plan):
+            if entry["skipped"] or entry["ncols"] == 0:
+                continue
+            iv = entry["interval"]
+            first_bin = int(iv["start"]) // base
+            for b in bin_sizes:
+                res, factor = w.resolution(b), b // base
+                px = extract(k, factor, first_bin, res.bin_offset(iv["name"], int(iv["start"])))
+                if px is None:
+                    continue
+                lo, hi = coarse_bin_range(first_bin, entry["ncols"], factor)
+                res.append_pixels(iv["name"], hi - lo + 1, px[0], px[1], px[2], bin1_offset=px[3],
+                                  offset_bp=int(iv["start"]))
+
+
 def write_bigwig(path, cfg, plan, occupancies, chroms=None, force_overwrite=False):
     """Writes the 1-D LEF occupancy of every simulated interval the way the reference's IO thread
     does (simulation.cpp:130-141, 170-197): every chromosome of the genome in the header, one

@@ -12,7 +12,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "libmodle_pixels.so")
 ERR_ARG, ERR_DEVICE, ERR_RANGE = -1, -2, -3
 EXPORTS = ["modle_pixels_create", "modle_pixels_destroy", "modle_pixels_count", "modle_pixels_extract",
-           "modle_pixels_to_host"]  # every symbol include/modle_pixels.h declares
+           "modle_pixels_to_host", "modle_pixels_coarse_shape", "modle_pixels_coarsen",
+           "modle_pixels_coarse_to_host"]  # every symbol include/modle_pixels.h declares
 
 _LIB = None
 _EXTRACTORS = {}
@@ -51,6 +52,12 @@ def lib():
                                                     C.c_void_p, C.c_uint64, C.c_void_p] + err
         lb.modle_pixels_to_host.argtypes = shape + [C.c_int64] + [C.POINTER(C.c_void_p)] * 4 + \
             [C.POINTER(_CStats), C.c_void_p] + err
+        u64p = C.POINTER(C.c_uint64)
+        lb.modle_pixels_coarse_shape.argtypes = [C.c_uint64] * 4 + [u64p, u64p]
+        lb.modle_pixels_coarsen.argtypes = shape + [C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64,
+                                                    C.c_void_p] + err
+        lb.modle_pixels_coarse_to_host.argtypes = shape + [C.c_uint64, C.c_uint64, C.c_int64] + \
+            [C.POINTER(C.c_void_p)] * 4 + [C.POINTER(_CStats), C.c_void_p] + err
         for name in EXPORTS:
             getattr(lb, name)  # raises AttributeError if a declared symbol is not exported
         _LIB = lb
@@ -69,6 +76,17 @@ def _host_array(ptr, n, dtype):
         return np.zeros(0, dtype=dtype)
     ctype = C.c_int64 if dtype == np.int64 else C.c_int32
     return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(n,)).copy()
+
+
+def coarse_shape(nrows, ncols, factor, first_bin=0):
+    """(nrows', ncols') of the band coarsened by `factor` (modle_pixels_coarse_shape; no device is
+    needed).  `first_bin`: chromosome-relative index of the interval's first fine bin."""
+    nr, nc = C.c_uint64(), C.c_uint64()
+    rc = lib().modle_pixels_coarse_shape(int(nrows), int(ncols), int(factor), int(first_bin),
+                                         C.byref(nr), C.byref(nc))
+    if rc != 0:
+        raise PixelsError(rc, "coarse_shape: invalid argument (factor >= 2, 0 < nrows <= ncols)")
+    return nr.value, nc.value
 
 
 class Extractor:
@@ -139,6 +157,37 @@ class Extractor:
                 _host_array(pc.value, n, np.int32), _host_array(po.value, int(ncols) + 1, np.int64),
                 Stats(st.nnz, st.sum, st.max_count))
 
+    def coarsen_into(self, d_band, nrows, ncols, factor, first_bin, d_out, out_words, stream=None):
+        """enqueues the coarsening of the band by `factor` into the caller-owned device array
+        `d_out` of `out_words` >= nrows' * ncols' + 1 words, all of which are written
+        (modle_pixels_coarsen); returns (nrows', ncols')"""
+        err = C.create_string_buffer(512)
+        rc = self._L.modle_pixels_coarsen(self._h, d_band, int(nrows), int(ncols), int(factor),
+                                          int(first_bin), d_out, int(out_words), _stream_ptr(stream),
+                                          err, len(err))
+        if rc != 0:
+            raise PixelsError(rc, err.value.decode(errors="replace"))
+        return coarse_shape(nrows, ncols, factor, first_bin)
+
+    def coarse_extract(self, d_band, nrows, ncols, factor, first_bin, bin_offset=0, stream=None):
+        """one-call form at `factor` times the bin size (modle_pixels_coarse_to_host): what
+        extract returns, for the coarse band; bin1_offset has ncols' + 1 entries and `bin_offset`
+        counts coarse bins.  A sum above INT32_MAX raises PixelsError(ERR_RANGE)."""
+        p1, p2, pc, po = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        st = _CStats()
+        err = C.create_string_buffer(512)
+        rc = self._L.modle_pixels_coarse_to_host(self._h, d_band, int(nrows), int(ncols), int(factor),
+                                                 int(first_bin), int(bin_offset), C.byref(p1),
+                                                 C.byref(p2), C.byref(pc), C.byref(po), C.byref(st),
+                                                 _stream_ptr(stream), err, len(err))
+        if rc != 0:
+            raise PixelsError(rc, err.value.decode(errors="replace"))
+        n = int(st.nnz)
+        _, ncols_out = coarse_shape(nrows, ncols, factor, first_bin)
+        return (_host_array(p1.value, n, np.int64), _host_array(p2.value, n, np.int64),
+                _host_array(pc.value, n, np.int32), _host_array(po.value, ncols_out + 1, np.int64),
+                Stats(st.nnz, st.sum, st.max_count))
+
 
 def extractor(device=0):
     """the process-wide context of `device`"""
@@ -152,3 +201,9 @@ def extract(d_band, nrows, ncols, bin_offset=0, stream=None, device=0):
     """Pixels of the band at device pointer `d_band` (uint32, layout of modle_hip_interval_outputs;
     e.g. a torch tensor's data_ptr()): returns bin1, bin2, count, bin1_offset, stats."""
     return extractor(device).extract(d_band, nrows, ncols, bin_offset, stream)
+
+
+def coarse_extract(d_band, nrows, ncols, factor, first_bin, bin_offset=0, stream=None, device=0):
+    """Pixels of the band at device pointer `d_band` at `factor` times its bin size, coarsened and
+    extracted on the device: returns bin1, bin2, count, bin1_offset, stats."""
+    return extractor(device).coarse_extract(d_band, nrows, ncols, factor, first_bin, bin_offset, stream)

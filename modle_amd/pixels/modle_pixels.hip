@@ -23,6 +23,7 @@
 #include <string>
 
 #include "modle_pixels.h"
+#include "pixels_context.h"
 
 namespace {
 
@@ -33,13 +34,6 @@ constexpr unsigned kScanThreads = 1024;
 constexpr unsigned kExtractThreads = 256;  // 4 waves
 constexpr unsigned kRowsPerWave = 16;
 constexpr unsigned kRowsPerBlock = kRowsPerWave * (kExtractThreads / 64);
-
-struct DeviceStats {
-  unsigned long long nnz;
-  unsigned long long sum;
-  unsigned int max_count;
-  unsigned int pad_;
-};
 
 // Tile (bx, by): columns [j0, j0 + cn), band words [d0, d0 + dn).  Its pixels belong to the rows
 // j - d, a range of cn + dn - 1 rows: slot = (j - j0) + (d0 + dn - 1 - d).
@@ -164,32 +158,13 @@ __global__ __launch_bounds__(kExtractThreads) void pixels_extract(
   }
 }
 
+}  // namespace
+
+namespace modle_pixels_detail {
+
 void set_err(char* err, size_t errlen, const std::string& msg) {
   if (err != nullptr && errlen != 0) std::snprintf(err, errlen, "%s", msg.c_str());
 }
-
-}  // namespace
-
-struct modle_pixels_handle {
-  int device = 0;
-  DeviceStats* d_stats = nullptr;
-  DeviceStats* h_stats = nullptr;  // pinned
-  // one-call form: device arrays and their pinned host mirrors, grown on demand
-  void *d_bin1 = nullptr, *d_bin2 = nullptr, *d_count = nullptr, *d_offsets = nullptr;
-  void *h_bin1 = nullptr, *h_bin2 = nullptr, *h_count = nullptr, *h_offsets = nullptr;
-  uint64_t cap_pixels = 0, cap_offsets = 0;
-};
-
-namespace {
-
-#define PIX_TRY(call)                                                                           \
-  do {                                                                                          \
-    const hipError_t e_ = (call);                                                               \
-    if (e_ != hipSuccess) {                                                                     \
-      set_err(err, errlen, std::string(#call) + ": " + hipGetErrorString(e_));                  \
-      return MODLE_PIXELS_ERR_DEVICE;                                                           \
-    }                                                                                           \
-  } while (0)
 
 bool bad_shape(uint64_t nrows, uint64_t ncols) {
   // (the last two: the grid of pixels_count, x < 2^31 and y < 2^16 blocks)
@@ -197,6 +172,13 @@ bool bad_shape(uint64_t nrows, uint64_t ncols) {
          ncols > static_cast<uint64_t>(std::numeric_limits<int32_t>::max()) * kCountCols ||
          nrows > 65535ull * kCountDepth;
 }
+
+}  // namespace modle_pixels_detail
+
+namespace {
+
+using modle_pixels_detail::bad_shape;
+using modle_pixels_detail::set_err;
 
 void free_buffers(modle_pixels_handle* h, bool pixels, bool offsets) {
   if (pixels) {
@@ -308,6 +290,7 @@ extern "C" void modle_pixels_destroy(modle_pixels_handle* h) {
   if (h == nullptr) return;
   (void)hipSetDevice(h->device);
   free_buffers(h, true, true);
+  (void)hipFree(h->d_coarse);
   (void)hipFree(h->d_stats);
   (void)hipHostFree(h->h_stats);
   delete h;
@@ -354,10 +337,17 @@ extern "C" int modle_pixels_to_host(modle_pixels_handle* h, const uint32_t* d_ba
     set_err(err, errlen, "modle_pixels_to_host: invalid argument (0 < nrows <= ncols, or both 0)");
     return MODLE_PIXELS_ERR_ARG;
   }
+  return modle_pixels_detail::to_host(h, d_band, nrows, ncols, bin_offset, bin1, bin2, count, bin1_offset, stats,
+                                      static_cast<hipStream_t>(stream), err, errlen);
+}
+
+int modle_pixels_detail::to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols,
+                                 int64_t bin_offset, const int64_t** bin1, const int64_t** bin2,
+                                 const int32_t** count, const int64_t** bin1_offset,
+                                 modle_pixels_stats* stats, hipStream_t st, char* err, size_t errlen) {
   *bin1 = *bin2 = nullptr;
   *count = nullptr;
   *bin1_offset = nullptr;
-  const hipStream_t st = static_cast<hipStream_t>(stream);
   PIX_TRY(hipSetDevice(h->device));
   int rc = reserve(h, 0, ncols + 1, err, errlen);
   if (rc != MODLE_PIXELS_OK) return rc;
