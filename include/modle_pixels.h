@@ -1,4 +1,5 @@
-/* modle_pixels.h -- C ABI of the sparse-pixel extraction (modle_amd/libmodle_pixels.so).
+/* modle_pixels.h -- C ABI of the sparse-pixel extraction (modle_amd/libmodle_pixels.so), of the
+ * coarsening of a band and of its dense regions (further down).
  *
  * The simulation leaves every interval as a dense band matrix in device memory
  * (modle_hip_interval_outputs).  A cooler file is made of the non-zero pixels only, sorted by
@@ -112,6 +113,39 @@ int modle_pixels_coarse_to_host(modle_pixels_handle* h, const uint32_t* d_band, 
                                 int64_t bin_offset, const int64_t** bin1, const int64_t** bin2,
                                 const int32_t** count, const int64_t** bin1_offset,
                                 modle_pixels_stats* stats, void* stream, char* err, size_t errlen);
+
+/* ---- Dense regions: the band unpacked into square tiles -------------------------------------
+ *
+ * A run of `count` tiles: tile t covers the bins lo_t = first + t * step .. lo_t + size - 1 of the
+ * band and becomes the symmetric size x size matrix
+ *     out[t][r][c] = d < nrows ? band[j * nrows + d] : 0,   a = lo_t + r, b = lo_t + c,
+ *                                                             d = |a - b|, j = max(a, b)
+ * of uint32[count][size][size], row-major: the same integers in another layout.  EVERY output word is
+ * written exactly once, the zeros outside the band included; the caller does not pre-zero.  The
+ * words of the band that are no pixels are never read.  A single region is count == 1. */
+
+/* How many tiles of the run lie inside [0, ncols): (ncols - first - size) / step + 1.  Host only.
+ * size == 0, step == 0 and first + size > ncols are MODLE_PIXELS_ERR_ARG. */
+int modle_pixels_tiles_fit(uint64_t ncols, uint64_t first, uint64_t size, uint64_t step,
+                           uint64_t* max_count);
+
+/* Enqueues the unpacking of `count` tiles into the device array `d_out` of `out_words` words on
+ * `stream`; the call does not wait.  MODLE_PIXELS_ERR_ARG, with nothing written: a null pointer,
+ * nrows == 0, nrows > ncols, count == 0, count > modle_pixels_tiles_fit's max_count, out_words <
+ * count * size * size (a product that overflows included), d_out overlapping the band.  The input is
+ * read, never written. */
+int modle_pixels_dense_tiles(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                             uint64_t ncols, uint64_t first, uint64_t size, uint64_t step,
+                             uint64_t count, uint32_t* d_out, uint64_t out_words, void* stream,
+                             char* err, size_t errlen);
+
+/* One call for the single region [lo, hi), 0 <= lo < hi <= ncols: unpacks into a scratch buffer
+ * of the context and copies it to a pinned host buffer of the context (both grown on demand, freed
+ * by modle_pixels_destroy).  *dense (uint32[hi - lo][hi - lo]) stays valid until the next call on
+ * the context.  Waits for `stream`. */
+int modle_pixels_dense_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                               uint64_t ncols, uint64_t lo, uint64_t hi, const uint32_t** dense,
+                               void* stream, char* err, size_t errlen);
 
 #ifdef __cplusplus
 }

@@ -284,6 +284,43 @@ class Simulator:
         return pixels.coarse_extract(d_contacts, nrows, ncols, factor, first_bin, bin_offset, stream,
                                      device=self.device)
 
+    def dense(self, interval_id, lo, hi, factor=1, first_bin=0, stream=None):
+        """The symmetric matrix of the bins [lo, hi) of the interval as a numpy uint32[hi - lo, hi - lo],
+        unpacked on the device from the band where it lies (pixels.dense); only the region crosses to
+        the host.  With `factor` > 1 the band is first coarsened on the device into a scratch band
+        (`first_bin` as for coarse_pixels) and `lo`, `hi` are column indexes of that coarse band."""
+        from . import pixels
+
+        d_band, _, nrows, ncols = self.outputs(interval_id)
+        if int(factor) == 1:
+            return pixels.dense(d_band, nrows, ncols, lo, hi, stream, device=self.device)
+        import torch
+
+        nr, nc = pixels.coarse_shape(nrows, ncols, factor, first_bin)
+        scratch = torch.empty(nr * nc + 1, dtype=torch.int32, device=torch.device("cuda", self.device))
+        ex = pixels.extractor(self.device)
+        ex.coarsen_into(d_band, nrows, ncols, factor, first_bin, scratch.data_ptr(), nr * nc + 1, stream)
+        return ex.dense(scratch.data_ptr(), nr, nc, lo, hi, stream)  # (waits: the scratch may go)
+
+    def dense_tiles(self, interval_id, first, size, step, count=None, stream=None):
+        """`count` square windows of the interval (window t: the bins first + t * step .. + size - 1;
+        None: all that fit) as a torch tensor [count, size, size] on the simulator's device, filled
+        there by the kernel: nothing crosses to the host.  The dtype is int32 and holds the uint32
+        counts bit for bit, like the tensors of the multi-rank path.  The kernel is enqueued on
+        `stream` (None: the default stream, on which torch orders its own work) and not waited for."""
+        import torch
+
+        from . import pixels
+
+        d_band, _, nrows, ncols = self.outputs(interval_id)
+        if count is None:
+            count = pixels.tiles_fit(ncols, first, size, step)
+        out = torch.empty((int(count), int(size), int(size)), dtype=torch.int32,
+                          device=torch.device("cuda", self.device))
+        pixels.dense_tiles_into(d_band, nrows, ncols, first, size, step, count, out.data_ptr(), out.numel(),
+                                stream, device=self.device)
+        return out
+
     def simulate_interval(self, start, end, bar_pos, bar_dir, stp_active, stp_inactive, tasks):
         """One-call seam (modle_hip_simulate_interval): returns contacts, missed, occupancy,
         results."""

@@ -7,11 +7,13 @@ Option names, defaults and the derivation of the dependent parameters follow the
 task derivation is `run_simulate`'s (src/libmodle/cpu/scheduler_simulate.cpp:43-170) and the
 outputs are the reference's: `<prefix>.cool` (with --mcool-resolutions `<prefix>.mcool`: the same
 contacts at several bin sizes, coarsened on the GPU) and, with the 1-D LEF position track on,
-`<prefix>_lef_1d_occupancy.bw` (cli.cpp:867-882).  Everything heavy is native: parsing and
+`<prefix>_lef_1d_occupancy.bw` (cli.cpp:867-882); with --dense-region also `<prefix>_dense.npz`, the
+square matrices of the named regions, unpacked on the GPU.  Everything heavy is native: parsing and
 task generation in libmodle_hip.so (host), the simulation on the MI355X (one process per GPU;
 under torch.distributed.run the cells are sharded over the ranks and the matrices are summed
 with RCCL), the writers in libmodle_cooler.so.  `-t/--threads` is accepted and ignored."""
 import argparse
+import decimal
 import json
 import os
 import sys
@@ -36,7 +38,9 @@ _DISTANCE_UNITS = {"bp": 1, "k": 10**3, "kb": 10**3, "kbp": 10**3, "m": 10**6, "
 def genomic_distance(text):
     """`20kb`, `1.5Mbp`, `3000000`: a number of base pairs with an optional unit, the reference's
     AsGenomicDistance transform (src/common/cli_utils_impl.hpp:304-362; the unit is case
-    insensitive and the product must be a whole number)"""
+    insensitive and the product must be a whole number).  The reference multiplies in double and so
+    refuses `1.025mb` (1024999.9999999999); a product that is whole in exact decimal arithmetic is
+    accepted here as well."""
     k = len(text)
     while k > 0 and text[k - 1].isalpha():
         k -= 1
@@ -58,6 +62,15 @@ def genomic_distance(text):
         m = float(num) * _DISTANCE_UNITS[unit]
     except ValueError:
         raise argparse.ArgumentTypeError(f"unable to convert {num} to a number")
+    if m != m or m in (float("inf"), float("-inf")):
+        raise argparse.ArgumentTypeError(f"unable to convert {num} to a number")
+    if m != int(m):
+        try:
+            exact = decimal.Decimal(num) * _DISTANCE_UNITS[unit]
+        except decimal.InvalidOperation:
+            exact = None
+        if exact is not None and exact == exact.to_integral_value():
+            m = int(exact)
     if m != int(m) or m < 0:
         raise argparse.ArgumentTypeError(f"Unable to convert {text} to a number of base-pairs "
                                          f"({m} is not an integral number)")
@@ -85,6 +98,24 @@ def mcool_bin_sizes(resolutions, base):
     return [base] + sorted(set(resolutions))
 
 
+def dense_region(text):
+    """`chrom` or `chrom:start-end` (--dense-region): (chrom, None, None) or (chrom, start, end) in
+    base pairs; the positions are genomic distances (`100kb`, `1.5mb`) and may carry commas"""
+    if ":" not in text:
+        if not text.strip():
+            raise argparse.ArgumentTypeError("an empty region")
+        return text, None, None
+    chrom, _, span = text.rpartition(":")
+    ends = span.replace(",", "").split("-")
+    if not chrom or len(ends) != 2 or not ends[0] or not ends[1]:
+        raise argparse.ArgumentTypeError(f"{text!r} is not chrom or chrom:start-end")
+    return chrom, genomic_distance(ends[0]), genomic_distance(ends[1])
+
+
+def dense_path(prefix):
+    return prefix + "_dense.npz"
+
+
 def build_parser():
     ap = argparse.ArgumentParser(prog="modle_amd", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -104,6 +135,10 @@ def build_parser():
                     help="write <prefix>.mcool instead of <prefix>.cool: the matrix at the resolution "
                          "(-r), which need not be listed, and at every bin size of the comma-separated "
                          "LIST (e.g. 10kb,25kb,100kb; multiples of -r), coarsened on the GPU")
+    io.add_argument("--dense-region", type=dense_region, action="append", default=None, metavar="REGION",
+                    help="also write <prefix>_dense.npz with the symmetric int32 matrix of REGION (chrom or "
+                         "chrom:start-end, snapped outward to whole bins of -r; inside one simulated "
+                         "interval), unpacked on the GPU; may be given several times")
     io.add_argument("--log-model-internal-state", action="store_true",
                     help="write <prefix>_internal_state.log.gz: one line of statistics per task and "
                          "epoch (uses the diagnostic build libmodle_hip_statelog.so)")
@@ -230,7 +265,8 @@ def simulate(a, log=print):
     device = a.device if a.device is not None else int(os.environ.get("LOCAL_RANK", "0"))
     if not a.skip_output and rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(cool_path)), exist_ok=True)
-        for p in (cool_path, bw_path if cfg.track_1d_lef_position else None):
+        for p in (cool_path, bw_path if cfg.track_1d_lef_position else None,
+                  dense_path(a.output_prefix) if a.dense_region else None):
             if p and os.path.exists(p) and not a.force:
                 raise SystemExit(f"refusing to overwrite {p}: pass --force to overwrite")
     t0 = time.time()
@@ -244,6 +280,8 @@ def simulate(a, log=print):
         if hit is not None:
             raise SystemExit(f"--mcool-resolutions: the intervals {hit[1]} and {hit[2]} share a bin at "
                              f"resolution {hit[0]}: its pixels would not be sorted and unique")
+    # (a bad region, too, ends the run before anything is simulated)
+    regions = driver.dense_regions(plan, int(cfg.bin_size), chroms, a.dense_region) if a.dense_region else []
     use_dist = world > 1
     if use_dist:
         import torch
@@ -341,6 +379,12 @@ def simulate(a, log=print):
             else:
                 driver.write_mcool_pixels(cool_path, cfg, plan, extract_at, bin_sizes, **kw)
             log(f"written {cool_path}")
+            if regions:
+                # (the cooler's INT32 range check has passed: the uint32 words are int32 counts; with
+                # several ranks the region is unpacked from the reduced tensor, like the pixels)
+                np.savez(dense_path(a.output_prefix),
+                         **{key: sim.dense(ids[k], lo, hi).view(np.int32) for k, lo, hi, key in regions})
+                log(f"written {dense_path(a.output_prefix)}")
         elif rank == 0:
             for k, iid in enumerate(ids):  # --skip-output: nothing is extracted, only summed
                 if iid is not None:

@@ -249,6 +249,47 @@ def write_mcool_pixels(path, cfg, plan, extract, bin_sizes, assembly="unknown", 
                                   offset_bp=int(iv["start"]))
 
 
+def dense_regions(plan, bin_size, chroms, regions):
+    """Maps every region of --dense-region to (k, lo, hi, key): the index k of the plan entry whose
+    matrix holds it, the columns [lo, hi) of that entry's band, and the name of its array,
+    `chrom:start-end` of the bins it covers (the end clipped at the chromosome's).  `regions`:
+    (chrom, start, end) in base pairs, or (chrom, None, None) for the whole chromosome; positions are
+    snapped outward to whole bins of `bin_size`.  `chroms`: [(name, size)] of the genome.  Needs no
+    GPU.  SystemExit: an unknown chromosome, start >= end, a region beyond the chromosome, a region
+    that does not lie inside exactly one simulated interval (one skipped for having no barriers is
+    not simulated), a duplicate."""
+    bin_size, sizes = int(bin_size), dict(chroms)
+    out, seen = [], set()
+    for chrom, start, end in regions:
+        what = chrom if start is None else f"{chrom}:{start}-{end}"
+        if chrom not in sizes:
+            raise SystemExit(f"--dense-region {what}: unknown chromosome {chrom}")
+        if start is None:
+            start, end = 0, int(sizes[chrom])
+        if start >= end:
+            raise SystemExit(f"--dense-region {what}: the start is not below the end")
+        if end > sizes[chrom]:
+            raise SystemExit(f"--dense-region {what}: beyond the end of {chrom} ({sizes[chrom]})")
+        lo, hi = start // bin_size, (end + bin_size - 1) // bin_size  # bins within the chromosome
+        hits = []
+        for k, entry in enumerate(plan):
+            iv = entry["interval"]
+            first = int(iv["start"]) // bin_size
+            if iv["name"] == chrom and first <= lo and hi <= first + entry["ncols"]:
+                hits.append((k, first))
+        if len(hits) != 1 or plan[hits[0][0]]["skipped"]:
+            why = "lies in an interval that is skipped for having no barriers" if len(hits) == 1 else \
+                "does not lie inside exactly one simulated interval"
+            raise SystemExit(f"--dense-region {what}: bins {lo}..{hi - 1} of {chrom}: the region {why}")
+        key = f"{chrom}:{lo * bin_size}-{min(hi * bin_size, int(sizes[chrom]))}"
+        if key in seen:
+            raise SystemExit(f"--dense-region {what}: {key} is requested twice")
+        seen.add(key)
+        k, first = hits[0]
+        out.append((k, lo - first, hi - first, key))
+    return out
+
+
 def write_bigwig(path, cfg, plan, occupancies, chroms=None, force_overwrite=False):
     """Writes the 1-D LEF occupancy of every simulated interval the way the reference's IO thread
     does (simulation.cpp:130-141, 170-197): every chromosome of the genome in the header, one

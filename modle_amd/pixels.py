@@ -1,6 +1,7 @@
 """ctypes view of the sparse-pixel extraction, include/modle_pixels.h (modle_amd/libmodle_pixels.so,
 built by `make -C modle_amd/pixels`): the non-zero pixels of a band matrix that lies in device
-memory, in cooler order, found on the GPU.  There is no host fallback: without the library or
+memory, in cooler order, found on the GPU; the band at a multiple of its bin size; and square regions
+of it as dense matrices.  There is no host fallback: without the library or
 without a device the calls fail."""
 import ctypes as C
 import os
@@ -13,7 +14,8 @@ SO_PATH = os.path.join(_HERE, "libmodle_pixels.so")
 ERR_ARG, ERR_DEVICE, ERR_RANGE = -1, -2, -3
 EXPORTS = ["modle_pixels_create", "modle_pixels_destroy", "modle_pixels_count", "modle_pixels_extract",
            "modle_pixels_to_host", "modle_pixels_coarse_shape", "modle_pixels_coarsen",
-           "modle_pixels_coarse_to_host"]  # every symbol include/modle_pixels.h declares
+           "modle_pixels_coarse_to_host", "modle_pixels_tiles_fit", "modle_pixels_dense_tiles",
+           "modle_pixels_dense_to_host"]  # every symbol include/modle_pixels.h declares
 
 _LIB = None
 _EXTRACTORS = {}
@@ -58,6 +60,10 @@ def lib():
                                                     C.c_void_p] + err
         lb.modle_pixels_coarse_to_host.argtypes = shape + [C.c_uint64, C.c_uint64, C.c_int64] + \
             [C.POINTER(C.c_void_p)] * 4 + [C.POINTER(_CStats), C.c_void_p] + err
+        lb.modle_pixels_tiles_fit.argtypes = [C.c_uint64] * 4 + [u64p]
+        lb.modle_pixels_dense_tiles.argtypes = shape + [C.c_uint64] * 4 + [C.c_void_p, C.c_uint64, C.c_void_p] + err
+        lb.modle_pixels_dense_to_host.argtypes = shape + [C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p),
+                                                          C.c_void_p] + err
         for name in EXPORTS:
             getattr(lb, name)  # raises AttributeError if a declared symbol is not exported
         _LIB = lb
@@ -87,6 +93,18 @@ def coarse_shape(nrows, ncols, factor, first_bin=0):
     if rc != 0:
         raise PixelsError(rc, "coarse_shape: invalid argument (factor >= 2, 0 < nrows <= ncols)")
     return nr.value, nc.value
+
+
+def tiles_fit(ncols, first, size, step):
+    """how many tiles of `size` bins, `step` apart from bin `first`, lie inside [0, ncols)
+    (modle_pixels_tiles_fit; no device is needed)"""
+    if min(int(ncols), int(first), int(size), int(step)) < 0:
+        raise PixelsError(ERR_ARG, "tiles_fit: negative argument")
+    n = C.c_uint64()
+    rc = lib().modle_pixels_tiles_fit(int(ncols), int(first), int(size), int(step), C.byref(n))
+    if rc != 0:
+        raise PixelsError(rc, "tiles_fit: invalid argument (size > 0, step > 0, first + size <= ncols)")
+    return n.value
 
 
 class Extractor:
@@ -189,6 +207,30 @@ class Extractor:
                 Stats(st.nnz, st.sum, st.max_count))
 
 
+    def dense_tiles_into(self, d_band, nrows, ncols, first, size, step, count, d_out, out_words, stream=None):
+        """enqueues the unpacking of `count` square tiles (tile t: the bins first + t * step ..
+        + size - 1) into the caller-owned device array `d_out` of `out_words` >= count * size * size
+        words, uint32[count][size][size], all of which are written (modle_pixels_dense_tiles)"""
+        err = C.create_string_buffer(512)
+        rc = self._L.modle_pixels_dense_tiles(self._h, d_band, int(nrows), int(ncols), int(first), int(size),
+                                              int(step), int(count), d_out, int(out_words),
+                                              _stream_ptr(stream), err, len(err))
+        if rc != 0:
+            raise PixelsError(rc, err.value.decode(errors="replace"))
+
+    def dense(self, d_band, nrows, ncols, lo, hi, stream=None):
+        """the symmetric matrix of the bins [lo, hi) as a numpy uint32[hi - lo, hi - lo] the caller
+        owns, unpacked on the device (modle_pixels_dense_to_host)"""
+        ptr = C.c_void_p()
+        err = C.create_string_buffer(512)
+        rc = self._L.modle_pixels_dense_to_host(self._h, d_band, int(nrows), int(ncols), int(lo), int(hi),
+                                                C.byref(ptr), _stream_ptr(stream), err, len(err))
+        if rc != 0:
+            raise PixelsError(rc, err.value.decode(errors="replace"))
+        n = int(hi) - int(lo)
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint32)), shape=(n, n)).copy()
+
+
 def extractor(device=0):
     """the process-wide context of `device`"""
     ex = _EXTRACTORS.get(int(device))
@@ -207,3 +249,15 @@ def coarse_extract(d_band, nrows, ncols, factor, first_bin, bin_offset=0, stream
     """Pixels of the band at device pointer `d_band` at `factor` times its bin size, coarsened and
     extracted on the device: returns bin1, bin2, count, bin1_offset, stats."""
     return extractor(device).coarse_extract(d_band, nrows, ncols, factor, first_bin, bin_offset, stream)
+
+
+def dense_tiles_into(d_band, nrows, ncols, first, size, step, count, d_out, out_words, stream=None, device=0):
+    """`count` square tiles of the band at device pointer `d_band`, unpacked into the device array
+    `d_out` (uint32[count][size][size]); enqueued on `stream`, nothing crosses to the host."""
+    extractor(device).dense_tiles_into(d_band, nrows, ncols, first, size, step, count, d_out, out_words, stream)
+
+
+def dense(d_band, nrows, ncols, lo, hi, stream=None, device=0):
+    """The symmetric matrix of the bins [lo, hi) of the band at device pointer `d_band`: numpy
+    uint32[hi - lo, hi - lo], unpacked on the device."""
+    return extractor(device).dense(d_band, nrows, ncols, lo, hi, stream)

@@ -291,6 +291,8 @@ extern "C" void modle_pixels_destroy(modle_pixels_handle* h) {
   (void)hipSetDevice(h->device);
   free_buffers(h, true, true);
   (void)hipFree(h->d_coarse);
+  (void)hipFree(h->d_dense);
+  (void)hipHostFree(h->h_dense);
   (void)hipFree(h->d_stats);
   (void)hipHostFree(h->h_stats);
   delete h;

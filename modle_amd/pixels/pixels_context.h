@@ -27,6 +27,9 @@ struct modle_pixels_handle {
   // modle_pixels_coarse_to_host: the coarse band (modle_coarsen.hip), grown on demand
   uint32_t* d_coarse = nullptr;
   uint64_t cap_coarse = 0;  // words
+  // modle_pixels_dense_to_host: the region (modle_dense.hip) and its pinned host mirror, grown on demand
+  uint32_t *d_dense = nullptr, *h_dense = nullptr;
+  uint64_t cap_dense = 0;  // words
 };
 
 namespace modle_pixels_detail {
