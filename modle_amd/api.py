@@ -264,25 +264,25 @@ class Simulator:
             C.byref(missed), occ.ctypes.data if occ is not None else None, err, len(err)), err)
         return contacts, missed.value, occ
 
-    def pixels(self, interval_id, bin_offset=0, stream=None):
+    def pixels(self, interval_id, bin_offset=0, stream=None, factor=1, first_bin=0):
         """The interval's non-zero pixels in cooler order, extracted on the device from the band
-        matrix where it lies (pixels.py): bin1, bin2, count, bin1_offset, stats.  Call it after
-        wait(); the dense matrix is not copied to the host."""
+        matrix where it lies (pixels.py): a pixels.Pixels of bin1, bin2, count, bin1_offset, stats.
+        Call it after wait(); the dense matrix is not copied to the host.  With `factor` > 1 the band
+        is first coarsened on the device (pixels.coarse_extract) and the pixels at `factor` times the
+        bin size come back: `first_bin` is the interval's first bin within its chromosome (start /
+        bin_size), which anchors the coarse bins at the chromosome's start, and `bin_offset` its
+        first bin within the coarse file."""
         from . import pixels
 
         d_contacts, _, nrows, ncols = self.outputs(interval_id)
-        return pixels.extract(d_contacts, nrows, ncols, bin_offset, stream, device=self.device)
-
-    def coarse_pixels(self, interval_id, factor, first_bin, bin_offset=0, stream=None):
-        """`pixels` at `factor` times the bin size: the band is coarsened on the device
-        (pixels.coarse_extract) and the pixels of the coarse band come back.  `first_bin`: the
-        interval's first bin within its chromosome (start / bin_size), which anchors the coarse bins
-        at the chromosome's start; `bin_offset`: its first bin within the coarse file."""
-        from . import pixels
-
-        d_contacts, _, nrows, ncols = self.outputs(interval_id)
+        if int(factor) == 1:
+            return pixels.extract(d_contacts, nrows, ncols, bin_offset, stream, device=self.device)
         return pixels.coarse_extract(d_contacts, nrows, ncols, factor, first_bin, bin_offset, stream,
                                      device=self.device)
+
+    def coarse_pixels(self, interval_id, factor, first_bin, bin_offset=0, stream=None):
+        """`pixels` at `factor` times the bin size"""
+        return self.pixels(interval_id, bin_offset, stream, factor, first_bin)
 
     def dense(self, interval_id, lo, hi, factor=1, first_bin=0, stream=None):
         """The symmetric matrix of the bins [lo, hi) of the interval as a numpy uint32[hi - lo, hi - lo],

@@ -13,13 +13,12 @@ task generation in libmodle_hip.so (host), the simulation on the MI355X (one pro
 under torch.distributed.run the cells are sharded over the ranks and the matrices are summed
 with RCCL), the writers in libmodle_cooler.so.  `-t/--threads` is accepted and ignored."""
 import argparse
+import collections
 import decimal
 import json
 import os
 import sys
 import time
-
-import numpy as np
 
 from . import api, driver, genome
 from .params import CS_LOOP, CS_NOISIFY, CS_TAD
@@ -255,147 +254,118 @@ def state_log_path(prefix):
     return prefix + "_internal_state.log.gz"  # cli.cpp:871-875
 
 
-def simulate(a, log=print):
-    cfg = config_from_args(a)
+# what preflight settles; a path is None for a file the run does not write, `state_log` is this rank's
+Outputs = collections.namedtuple("Outputs", "cooler bigwig dense state_log")
+Preflight = collections.namedtuple("Preflight", "bin_sizes outputs rank world device")
+
+
+def preflight(a, cfg):
+    """What the arguments alone settle and refuse, without a genome or a GPU.  SystemExit: a bad
+    --mcool-resolutions list; on rank 0, an output that exists without --force (cooler or .mcool, then
+    bigwig, then .npz).  With --skip-output no file is planned and none is looked at."""
     # (a bad list ends the run here, before anything is imported or simulated)
     bin_sizes = None if a.mcool_resolutions is None else mcool_bin_sizes(a.mcool_resolutions, cfg.bin_size)
-    cool_path, bw_path = output_paths(a.output_prefix, mcool=bin_sizes is not None)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     device = a.device if a.device is not None else int(os.environ.get("LOCAL_RANK", "0"))
-    if not a.skip_output and rank == 0:
+    if a.skip_output:
+        return Preflight(bin_sizes, Outputs(None, None, None, None), rank, world, device)
+    cool_path, bw_path = output_paths(a.output_prefix, mcool=bin_sizes is not None)
+    log_path = state_log_path(a.output_prefix) if world == 1 else \
+        f"{a.output_prefix}_internal_state.rank{rank}.log.gz"
+    outputs = Outputs(cool_path, bw_path if cfg.track_1d_lef_position else None,
+                      dense_path(a.output_prefix) if a.dense_region else None,
+                      log_path if a.log_model_internal_state else None)
+    if rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(cool_path)), exist_ok=True)
-        for p in (cool_path, bw_path if cfg.track_1d_lef_position else None,
-                  dense_path(a.output_prefix) if a.dense_region else None):
+        for p in (outputs.cooler, outputs.bigwig, outputs.dense):
             if p and os.path.exists(p) and not a.force:
                 raise SystemExit(f"refusing to overwrite {p}: pass --force to overwrite")
-    t0 = time.time()
+    return Preflight(bin_sizes, outputs, rank, world, device)
+
+
+def plan_run(a, cfg, pre, log):
+    """The chromosomes, this rank's plan and the dense regions; a resolution or region that the plan
+    shows to be bad still ends the run before anything is simulated."""
     chroms, intervals, stats = genome.import_genome(cfg, a.chrom_sizes, a.extrusion_barrier_file,
                                                     a.genomic_intervals, a.name_as_stp)
     log(f"imported {len(chroms)} chromosomes, {len(intervals)} intervals, "
         f"{stats['barriers_imported']} barriers ({stats['barriers_without_strand']} without strand dropped)")
-    plan = driver.plan_genome(cfg, intervals, rank, world)
-    if bin_sizes is not None and not a.skip_output:
-        hit = driver.mcool_collision(plan, int(cfg.bin_size), bin_sizes)
+    plan = driver.plan_genome(cfg, intervals, pre.rank, pre.world)
+    if pre.bin_sizes is not None and not a.skip_output:
+        hit = driver.mcool_collision(plan, int(cfg.bin_size), pre.bin_sizes)
         if hit is not None:
             raise SystemExit(f"--mcool-resolutions: the intervals {hit[1]} and {hit[2]} share a bin at "
                              f"resolution {hit[0]}: its pixels would not be sorted and unique")
-    # (a bad region, too, ends the run before anything is simulated)
     regions = driver.dense_regions(plan, int(cfg.bin_size), chroms, a.dense_region) if a.dense_region else []
-    use_dist = world > 1
-    if use_dist:
+    return chroms, plan, regions
+
+
+def open_simulator(cfg, pre):
+    """the process group when there are several ranks, and the simulator on this rank's device"""
+    if pre.world > 1:
         import torch
         import torch.distributed as dist
 
-        torch.cuda.set_device(device)
-        dist.init_process_group("nccl", device_id=torch.device("cuda", device))
-    sim = api.Simulator(cfg, device)
-    try:
-        if a.log_model_internal_state and not a.skip_output:
-            # (with --skip-output the log would not be written: nothing is recorded, and the
-            # default build of the library serves, like the reference accepts the combination)
-            sim.enable_state_log(a.internal_state_max_epochs)
-        tensors = None
-        if use_dist:
-            # the matrices are torch tensors the kernel accumulates into: they are reduced in
-            # place and rank 0 extracts its pixels from the reduced tensor, without a host copy
-            dev = torch.device("cuda", device)
-            tensors = [None if e["skipped"] else
-                       (torch.zeros(e["nrows"] * e["ncols"] + 1, dtype=torch.int32, device=dev),
-                        torch.zeros(e["ncols"], dtype=torch.int64, device=dev)) for e in plan]
-            torch.cuda.synchronize(dev)
-        ids = driver.enqueue_plan(sim, cfg, plan, device_buffers=None if tensors is None else [
-            (None, None) if t is None else (t[0].data_ptr(), t[1].data_ptr()) for t in tensors])
-        n_tasks = sum(len(e["tasks"]) for e in plan if not e["skipped"])
-        log(f"simulating {n_tasks} (interval, cell) tasks on device {device} (rank {rank} of {world})")
-        sim.launch()
-        sim.wait()
-        log(f"simulation kernel: {sim.kernel_ms() / 1e3:.2f} s")
-        if a.log_model_internal_state and not a.skip_output:
-            import gzip
+        torch.cuda.set_device(pre.device)
+        dist.init_process_group("nccl", device_id=torch.device("cuda", pre.device))
+    return api.Simulator(cfg, pre.device)
 
-            path = state_log_path(a.output_prefix) if world == 1 else \
-                f"{a.output_prefix}_internal_state.rank{rank}.log.gz"
-            with gzip.open(path, "wt") as fh:
-                fh.write(driver.STATE_LOG_HEADER)
-                for entry, iid in zip(plan, ids):
-                    if iid is None:
-                        continue
-                    iv = entry["interval"]
-                    for k, task in enumerate(entry["tasks"]):
-                        fh.writelines(driver.format_state_log(task, iv, len(iv["bar_pos"]),
-                                                              sim.state_log(iid, k)))
-            log(f"written {path}")
+
+def run_plan(sim, a, cfg, plan, pre, log):
+    """Enqueues the plan, launches it and waits: the interval ids and, with several ranks, the torch
+    tensors the kernel accumulated into (else None), for driver.write_outputs"""
+    if pre.outputs.state_log is not None:
+        # (with --skip-output the log would not be written: nothing is recorded, and the
+        # default build of the library serves, like the reference accepts the combination)
+        sim.enable_state_log(a.internal_state_max_epochs)
+    tensors = None
+    if pre.world > 1:
+        import torch
+
+        # the matrices are torch tensors the kernel accumulates into: they are reduced in
+        # place and rank 0 extracts its pixels from the reduced tensor, without a host copy
+        dev = torch.device("cuda", pre.device)
+        tensors = [None if e["skipped"] else
+                   (torch.zeros(e["nrows"] * e["ncols"] + 1, dtype=torch.int32, device=dev),
+                    torch.zeros(e["ncols"], dtype=torch.int64, device=dev)) for e in plan]
+        torch.cuda.synchronize(dev)
+    ids = driver.enqueue_plan(sim, cfg, plan, device_buffers=None if tensors is None else [
+        (None, None) if t is None else (t[0].data_ptr(), t[1].data_ptr()) for t in tensors])
+    n_tasks = sum(len(e["tasks"]) for e in plan if not e["skipped"])
+    log(f"simulating {n_tasks} (interval, cell) tasks on device {pre.device} (rank {pre.rank} of {pre.world})")
+    sim.launch()
+    sim.wait()
+    log(f"simulation kernel: {sim.kernel_ms() / 1e3:.2f} s")
+    return ids, tensors
+
+
+def simulate(a, log=print):
+    """preflight (arguments only) -> plan_run -> open_simulator -> run_plan -> driver.write_outputs,
+    and the bigwig once the simulator is closed"""
+    cfg = config_from_args(a)
+    pre = preflight(a, cfg)
+    t0 = time.time()
+    chroms, plan, regions = plan_run(a, cfg, pre, log)
+    sim = open_simulator(cfg, pre)
+    try:
+        ids, tensors = run_plan(sim, a, cfg, plan, pre, log)
         # The contact matrices stay on the device: the cooler is written from their non-zero
         # pixels, extracted there (libmodle_pixels.so), and the warning uses the extraction's sum.
-        from . import pixels
-
-        occupancies, missed_updates = [], []
-        for k, iid in enumerate(ids):
-            if iid is None:
-                occupancies.append(None)
-                missed_updates.append(0)
-                continue
-            _, missed, occ = sim.copy_outputs(iid, want_contacts=False)
-            if use_dist:
-                tc, to = tensors[k]
-                dist.reduce(tc, dst=0, op=dist.ReduceOp.SUM)
-                dist.reduce(to, dst=0, op=dist.ReduceOp.SUM)
-                occ = to.cpu().numpy().view(np.uint64) if occ is not None else None
-            occupancies.append(occ)
-            missed_updates.append(missed)
-        if use_dist:
-            torch.cuda.synchronize(torch.device("cuda", device))
-
-        def warn_missing(k, stats):
-            total, missed = int(stats.sum), missed_updates[k]
-            if total + missed > 0 and missed / (total + missed) >= 0.01:
-                log(f"warning: {100.0 * missed / (total + missed):.2f}% missing interactions for "
-                    f"{plan[k]['interval']['name']}")  # simulation.cpp:153-157
-
-        def extract(k, bin_offset):
-            if ids[k] is None:
-                return None
-            px = sim.pixels(ids[k], bin_offset)
-            warn_missing(k, px[4])
-            return px
-
-        def extract_at(k, factor, first_bin, bin_offset):
-            # the coarse resolutions of the .mcool: summed on the device from the same matrix (with
-            # several ranks: from the reduced tensor, like the pixels of the base resolution)
-            if factor == 1:
-                return extract(k, bin_offset)
-            if ids[k] is None:
-                return None
-            return sim.coarse_pixels(ids[k], factor, first_bin, bin_offset)
-
-        if rank == 0 and not a.skip_output:
-            meta = json.dumps({k: v for k, v in vars(a).items() if v is not None and k != "command"},
-                              sort_keys=True)
-            kw = dict(assembly=a.assembly_name, generated_by="modle_amd (MI355X)", metadata_json=meta,
-                      force_overwrite=a.force, chroms=chroms)
-            if bin_sizes is None:
-                driver.write_cooler_pixels(cool_path, cfg, plan, extract, **kw)
-            else:
-                driver.write_mcool_pixels(cool_path, cfg, plan, extract_at, bin_sizes, **kw)
-            log(f"written {cool_path}")
-            if regions:
-                # (the cooler's INT32 range check has passed: the uint32 words are int32 counts; with
-                # several ranks the region is unpacked from the reduced tensor, like the pixels)
-                np.savez(dense_path(a.output_prefix),
-                         **{key: sim.dense(ids[k], lo, hi).view(np.int32) for k, lo, hi, key in regions})
-                log(f"written {dense_path(a.output_prefix)}")
-        elif rank == 0:
-            for k, iid in enumerate(ids):  # --skip-output: nothing is extracted, only summed
-                if iid is not None:
-                    d_contacts, _, nrows, ncols = sim.outputs(iid)
-                    warn_missing(k, pixels.extractor(device).count(d_contacts, nrows, ncols))
+        meta = json.dumps({k: v for k, v in vars(a).items() if v is not None and k != "command"},
+                          sort_keys=True)
+        occupancies = driver.write_outputs(
+            sim, cfg, plan, ids, tensors, pre.outputs, pre.bin_sizes, regions, pre.rank, log,
+            assembly=a.assembly_name, generated_by="modle_amd (MI355X)", metadata_json=meta,
+            force_overwrite=a.force, chroms=chroms)
     finally:
         sim.close()
-    if rank == 0 and not a.skip_output and cfg.track_1d_lef_position:
-        driver.write_bigwig(bw_path, cfg, plan, occupancies, chroms, force_overwrite=a.force)
-        log(f"written {bw_path}")
-    if use_dist:
+    if pre.rank == 0 and pre.outputs.bigwig is not None:
+        driver.write_bigwig(pre.outputs.bigwig, cfg, plan, occupancies, chroms, force_overwrite=a.force)
+        log(f"written {pre.outputs.bigwig}")
+    if pre.world > 1:
+        import torch.distributed as dist
+
         dist.destroy_process_group()
     log(f"done in {time.time() - t0:.1f} s")
     return 0

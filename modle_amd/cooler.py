@@ -58,14 +58,49 @@ class CoolerError(RuntimeError):
         self.code = code
 
 
-class _Cooler:
-    """One cooler behind a modle_cool_file handle: a file of its own (CoolerWriter) or one
-    resolution of a multi-resolution file (McoolWriter.resolution)."""
+def _marshal_chroms(chroms):
+    """[(name, size)] as the (names, sizes, count) arguments of the create calls"""
+    names = (ctypes.c_char_p * len(chroms))(*[n.encode() for n, _ in chroms])
+    sizes = (ctypes.c_uint32 * len(chroms))(*[int(s) for _, s in chroms])
+    return names, sizes, len(chroms)
+
+
+class _Handle:
+    """A handle of the library with its error buffer and the chromosomes' indexes.  `_close_fn` names
+    the call that finishes a handle this object owns; a borrowed one (one resolution of a
+    multi-resolution file) has none and is only let go of."""
+    _close_fn = None
 
     def __init__(self, handle, chroms):
         self._h = handle
         self._err = ctypes.create_string_buffer(512)
         self._index = {n: i for i, (n, _) in enumerate(chroms)}
+
+    def _cid(self, chrom):
+        return self._index[chrom] if isinstance(chrom, str) else int(chrom)
+
+    def _call(self, fn, *args):
+        rc = fn(*args, self._err, len(self._err))
+        if rc != 0:
+            raise CoolerError(rc, self._err.value.decode())
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            if self._close_fn is not None:
+                self._call(getattr(lib(), self._close_fn), h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+class _Cooler(_Handle):
+    """One cooler behind a modle_cool_file handle: a file of its own (CoolerWriter) or one
+    resolution of a multi-resolution file (McoolWriter.resolution)."""
 
     def append(self, chrom, band, nrows, ncols, offset_bp=0):
         """band: uint32 array of nrows * ncols (+1) words in the layout of the HIP library"""
@@ -73,21 +108,14 @@ class _Cooler:
         band = np.ascontiguousarray(band, dtype=np.uint32)
         if band.size < nrows * ncols:
             raise ValueError("band matrix smaller than nrows * ncols")
-        cid = self._index[chrom] if isinstance(chrom, str) else int(chrom)
-        rc = lib().modle_cool_append_matrix(self._h, cid, int(offset_bp), band.ctypes.data,
-                                            int(nrows), int(ncols), self._err, len(self._err))
-        if rc != 0:
-            raise CoolerError(rc, self._err.value.decode())
+        self._call(lib().modle_cool_append_matrix, self._h, self._cid(chrom), int(offset_bp),
+                   band.ctypes.data, int(nrows), int(ncols))
 
     def bin_offset(self, chrom, offset_bp=0):
         """first bin id, within the file, of the interval of `chrom` that starts at `offset_bp`:
         what the pixels of that interval are extracted with (pixels.extract(bin_offset=...))"""
-        cid = self._index[chrom] if isinstance(chrom, str) else int(chrom)
         out = ctypes.c_int64(0)
-        rc = lib().modle_cool_bin_offset(self._h, cid, int(offset_bp), ctypes.byref(out), self._err,
-                                         len(self._err))
-        if rc != 0:
-            raise CoolerError(rc, self._err.value.decode())
+        self._call(lib().modle_cool_bin_offset, self._h, self._cid(chrom), int(offset_bp), ctypes.byref(out))
         return out.value
 
     def append_pixels(self, chrom, ncols, bin1, bin2, count, bin1_offset=None, offset_bp=0):
@@ -105,71 +133,48 @@ class _Cooler:
             off = np.ascontiguousarray(bin1_offset, dtype=np.int64)
             if off.shape != (int(ncols) + 1,):
                 raise ValueError("bin1_offset must hold ncols + 1 entries")
-        cid = self._index[chrom] if isinstance(chrom, str) else int(chrom)
-        rc = lib().modle_cool_append_pixels(self._h, cid, int(offset_bp), int(ncols), bin1.ctypes.data,
-                                            bin2.ctypes.data, count.ctypes.data, len(bin1),
-                                            off.ctypes.data if off is not None else None, self._err,
-                                            len(self._err))
-        if rc != 0:
-            raise CoolerError(rc, self._err.value.decode())
+        self._call(lib().modle_cool_append_pixels, self._h, self._cid(chrom), int(offset_bp), int(ncols),
+                   bin1.ctypes.data, bin2.ctypes.data, count.ctypes.data, len(bin1),
+                   off.ctypes.data if off is not None else None)
 
 
 class CoolerWriter(_Cooler):
-    """`chroms`: list of (name, size); matrices are appended in ascending chromosome order."""
+    """`chroms`: list of (name, size); matrices are appended in ascending chromosome order.  It is
+    the one-resolution case of McoolWriter: `bin_sizes == [bin_size]`, `resolution(bin_size)` is the
+    writer itself."""
+    _close_fn = "modle_cool_close"
 
     def __init__(self, path, chroms, bin_size, assembly="unknown", generated_by="modle-hip",
                  metadata_json="", force_overwrite=False):
-        names = (ctypes.c_char_p * len(chroms))(*[n.encode() for n, _ in chroms])
-        sizes = (ctypes.c_uint32 * len(chroms))(*[int(s) for _, s in chroms])
-        self._h = ctypes.c_void_p()
-        self._err = ctypes.create_string_buffer(512)
-        rc = lib().modle_cool_create(os.fsencode(path), int(force_overwrite), names, sizes,
-                                     len(chroms), int(bin_size), assembly.encode(),
-                                     generated_by.encode(), metadata_json.encode(),
-                                     ctypes.byref(self._h), self._err, len(self._err))
-        if rc != 0:
-            self._h = None
-            raise CoolerError(rc, self._err.value.decode())
-        self._index = {n: i for i, (n, _) in enumerate(chroms)}
+        super().__init__(ctypes.c_void_p(), chroms)
+        self._call(lib().modle_cool_create, os.fsencode(path), int(force_overwrite), *_marshal_chroms(chroms),
+                   int(bin_size), assembly.encode(), generated_by.encode(), metadata_json.encode(),
+                   ctypes.byref(self._h))
+        self.bin_sizes = [int(bin_size)]
 
-    def close(self):
-        if self._h is not None:
-            h, self._h = self._h, None
-            rc = lib().modle_cool_close(h, self._err, len(self._err))
-            if rc != 0:
-                raise CoolerError(rc, self._err.value.decode())
-
-    def __enter__(self):
+    def resolution(self, bin_size):
+        if int(bin_size) != self.bin_sizes[0]:
+            raise KeyError(bin_size)
         return self
 
-    def __exit__(self, *exc):
-        self.close()
-        return False
 
-
-class McoolWriter:
+class McoolWriter(_Handle):
     """A multi-resolution cooler (include/modle_mcool.h): one cooler per entry of `bin_sizes`
     (ascending, distinct multiples of the first) under /resolutions/<bin size>.  `resolution(b)`
     is written like a CoolerWriter of bin size `b` (bin_offset, append_pixels, append), in genome
     order per resolution; `close` finishes all of them."""
+    _close_fn = "modle_mcool_close"
 
     def __init__(self, path, chroms, bin_sizes, assembly="unknown", generated_by="modle-hip",
                  metadata_json="", force_overwrite=False):
         bin_sizes = [int(b) for b in bin_sizes]
         if any(not 0 <= b < 2**32 for b in bin_sizes):
             raise CoolerError(-1, "modle_mcool_create: a bin size does not fit 32 bits")
-        names = (ctypes.c_char_p * len(chroms))(*[n.encode() for n, _ in chroms])
-        sizes = (ctypes.c_uint32 * len(chroms))(*[int(s) for _, s in chroms])
         res = (ctypes.c_uint32 * len(bin_sizes))(*bin_sizes)
-        self._h = ctypes.c_void_p()
-        self._err = ctypes.create_string_buffer(512)
-        rc = lib().modle_mcool_create(os.fsencode(path), int(force_overwrite), names, sizes,
-                                      len(chroms), res, len(bin_sizes), assembly.encode(),
-                                      generated_by.encode(), metadata_json.encode(),
-                                      ctypes.byref(self._h), self._err, len(self._err))
-        if rc != 0:
-            self._h = None
-            raise CoolerError(rc, self._err.value.decode())
+        super().__init__(ctypes.c_void_p(), chroms)
+        self._call(lib().modle_mcool_create, os.fsencode(path), int(force_overwrite), *_marshal_chroms(chroms),
+                   res, len(bin_sizes), assembly.encode(), generated_by.encode(), metadata_json.encode(),
+                   ctypes.byref(self._h))
         self.bin_sizes = bin_sizes
         self._res = {b: _Cooler(ctypes.c_void_p(lib().modle_mcool_resolution(self._h, k)), chroms)
                      for k, b in enumerate(bin_sizes)}
@@ -178,17 +183,6 @@ class McoolWriter:
         return self._res[int(bin_size)]
 
     def close(self):
-        if self._h is not None:
-            h, self._h = self._h, None
-            for r in self._res.values():
-                r._h = None  # borrowed handles: gone with the file
-            rc = lib().modle_mcool_close(h, self._err, len(self._err))
-            if rc != 0:
-                raise CoolerError(rc, self._err.value.decode())
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
+        for r in self._res.values():
+            r.close()  # borrowed handles: gone with the file
+        super().close()

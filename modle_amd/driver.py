@@ -7,7 +7,13 @@ registers the interval with the simulator and enqueues the tasks.  One launch th
 tasks of all intervals together (the reference's workers also drain one queue that mixes
 intervals).  Cells are independent, so sharding them over ranks needs no data-path collective;
 the per-rank contact matrices are summed afterwards (`reduce_outputs`).
+
+`write_outputs` is the front end's output stage after the launch.
 """
+import functools
+
+import numpy as np
+
 from . import api
 
 
@@ -162,33 +168,6 @@ def write_cooler(path, cfg, plan, matrices, assembly="unknown", generated_by="mo
             w.append(iv["name"], m, entry["nrows"], entry["ncols"], offset_bp=int(iv["start"]))
 
 
-def write_cooler_pixels(path, cfg, plan, extract, assembly="unknown", generated_by="modle-hip",
-                        metadata_json="", force_overwrite=False, chroms=None):
-    """write_cooler from sparse pixels: the same file (dataset for dataset, attribute for
-    attribute), without a dense matrix on the host.  `extract(k, bin_offset)` returns the sorted
-    non-zero pixels of plan entry k with `bin_offset` (the interval's first bin within the file)
-    added to the bin ids, as (bin1, bin2, count, bin1_offset[, stats]) -- what
-    api.Simulator.pixels / pixels.extract return -- or None for an entry without a matrix.  It is
-    called once per entry that is not skipped, in genome order, so that one interval's pixels are
-    on the host at a time."""
-    from . import cooler
-
-    if chroms is None:
-        chroms = _chroms_of_plan(plan)
-    with cooler.CoolerWriter(path, chroms, int(cfg.bin_size), assembly=assembly,
-                             generated_by=generated_by, metadata_json=metadata_json,
-                             force_overwrite=force_overwrite) as w:
-        for k, entry in enumerate(plan):
-            if entry["skipped"]:
-                continue
-            iv = entry["interval"]
-            px = extract(k, w.bin_offset(iv["name"], int(iv["start"])))
-            if px is None:
-                continue
-            w.append_pixels(iv["name"], entry["ncols"], px[0], px[1], px[2], bin1_offset=px[3],
-                            offset_bp=int(iv["start"]))
-
-
 def coarse_bin_range(first_bin, ncols, factor):
     """first and last coarse bin, within the chromosome, of the `ncols` fine bins from `first_bin`
     (coarse bins are anchored at the chromosome's start: include/modle_pixels.h)"""
@@ -213,40 +192,45 @@ def mcool_collision(plan, base, bin_sizes):
     return None
 
 
-def write_mcool_pixels(path, cfg, plan, extract, bin_sizes, assembly="unknown", generated_by="modle-hip",
-                       metadata_json="", force_overwrite=False, chroms=None):
-    """write_cooler_pixels for a multi-resolution file: one cooler per entry of `bin_sizes`
-    (ascending; the first is cfg.bin_size, the others multiples of it) under
-    /resolutions/<bin size>.  For every entry of the plan that is not skipped, in genome order,
-    `extract(k, factor, first_bin, bin_offset)` is called once per resolution and returns the
-    sorted non-zero pixels of plan entry k at `factor` times the bin size, with `bin_offset` (the
-    interval's first bin within that resolution) added to the ids -- what api.Simulator.pixels
-    (factor == 1, the existing path) and api.Simulator.coarse_pixels return -- or None.
-    `first_bin` is the interval's first fine bin within its chromosome.  One interval's pixels of
-    one resolution are on the host at a time."""
+def write_pixels(path, cfg, plan, extract, bin_sizes=None, assembly="unknown", generated_by="modle-hip",
+                 metadata_json="", force_overwrite=False, chroms=None):
+    """write_cooler from sparse pixels, without a dense matrix on the host.  `bin_sizes=None`: the
+    .cool write_cooler writes (dataset for dataset, attribute for attribute).  A list (ascending; the
+    first is cfg.bin_size, the others multiples of it): a multi-resolution file with one such cooler
+    per entry under /resolutions/<bin size>.  For every entry of the plan that is not skipped, in
+    genome order, `extract(k, factor, first_bin, bin_offset)` is called once per resolution and returns
+    the sorted non-zero pixels of plan entry k at `factor` times the bin size, with `bin_offset` (the
+    interval's first bin within that resolution) added to the ids -- a pixels.Pixels, what
+    api.Simulator.pixels returns -- or None for an entry without a matrix.  `first_bin` is the
+    interval's first fine bin within its chromosome.  One interval's pixels of one resolution are on
+    the host at a time.  (An entry that is not skipped has a column: plan_genome refuses an empty interval.)"""
     from . import cooler
 
     base = int(cfg.bin_size)
-    bin_sizes = [int(b) for b in bin_sizes]
-    if not bin_sizes or bin_sizes[0] != base:
-        raise ValueError("write_mcool_pixels: bin_sizes must start with the simulation's bin size")
     if chroms is None:
         chroms = _chroms_of_plan(plan)
-    with cooler.McoolWriter(path, chroms, bin_sizes, assembly=assembly, generated_by=generated_by,
-                            metadata_json=metadata_json, force_overwrite=force_overwrite) as w:
+    kw = dict(assembly=assembly, generated_by=generated_by, metadata_json=metadata_json,
+              force_overwrite=force_overwrite)
+    if bin_sizes is None:
+        writer = cooler.CoolerWriter(path, chroms, base, **kw)
+    else:
+        if not bin_sizes or int(bin_sizes[0]) != base:
+            raise ValueError("write_pixels: bin_sizes must start with the simulation's bin size")
+        writer = cooler.McoolWriter(path, chroms, bin_sizes, **kw)
+    with writer as w:
         for k, entry in enumerate(plan):
-            if entry["skipped"] or entry["ncols"] == 0:
+            if entry["skipped"]:
                 continue
             iv = entry["interval"]
             first_bin = int(iv["start"]) // base
-            for b in bin_sizes:
+            for b in w.bin_sizes:
                 res, factor = w.resolution(b), b // base
                 px = extract(k, factor, first_bin, res.bin_offset(iv["name"], int(iv["start"])))
                 if px is None:
                     continue
                 lo, hi = coarse_bin_range(first_bin, entry["ncols"], factor)
-                res.append_pixels(iv["name"], hi - lo + 1, px[0], px[1], px[2], bin1_offset=px[3],
-                                  offset_bp=int(iv["start"]))
+                res.append_pixels(iv["name"], hi - lo + 1, px.bin1, px.bin2, px.count,
+                                  bin1_offset=px.bin1_offset, offset_bp=int(iv["start"]))
 
 
 def dense_regions(plan, bin_size, chroms, regions):
@@ -329,6 +313,90 @@ def format_state_log(task, interval, n_barriers, records):
                    f"{interval['end']}\t{'True' if burnin else 'False'}\t{occ!r}\t{n}\t{int(rec[3])}\t"
                    f"{int(rec[4])}\t{int(rec[5])}\t{int(rec[6])}\t{int(rec[7])}\t{int(rec[8])}\t{avg!r}\n")
     return out
+
+
+def write_state_log(path, sim, plan, ids):
+    """<prefix>_internal_state.log.gz: the records of every task of every registered interval"""
+    import gzip
+
+    with gzip.open(path, "wt") as fh:
+        fh.write(STATE_LOG_HEADER)
+        for entry, iid in zip(plan, ids):
+            if iid is None:
+                continue
+            iv = entry["interval"]
+            for k, task in enumerate(entry["tasks"]):
+                fh.writelines(format_state_log(task, iv, len(iv["bar_pos"]), sim.state_log(iid, k)))
+
+
+def warn_missing(name, total, missed, log):
+    """simulation.cpp:153-157: 1% or more of an interval's interactions fell outside its matrix"""
+    if total + missed > 0 and missed / (total + missed) >= 0.01:
+        log(f"warning: {100.0 * missed / (total + missed):.2f}% missing interactions for {name}")
+
+
+def _interval_pixels(sim, plan, ids, missed, log, k, factor, first_bin, bin_offset):
+    """write_pixels' callback: every resolution from the same matrix on the device (with several
+    ranks: the reduced tensor); the base resolution's sum feeds the missing-interactions warning"""
+    if ids[k] is None:
+        return None
+    px = sim.pixels(ids[k], bin_offset, factor=factor, first_bin=first_bin)
+    if factor == 1:
+        warn_missing(plan[k]["interval"]["name"], px.stats.sum, missed[k], log)
+    return px
+
+
+def write_outputs(sim, cfg, plan, ids, tensors, outputs, bin_sizes=None, regions=(), rank=0, log=print,
+                  **attrs):
+    """What a finished launch writes while the simulator is open: the state log (every rank its
+    own), then on rank 0 the cooler or .mcool with the missing-interactions warnings, and the dense
+    `regions` (of dense_regions).  `outputs.state_log`, `.cooler`, `.dense`: the paths, None for a file
+    that is not written; without a cooler (--skip-output) the matrices are only summed, for the
+    warnings.  `tensors`: with several ranks the (contacts, occupancy) torch tensors per plan entry;
+    they are reduced in place onto rank 0, which extracts from the reduced tensor without a host copy.
+    `attrs`: write_pixels' keywords.  Returns the occupancies per plan entry, for write_bigwig."""
+    from . import pixels
+
+    if outputs.state_log is not None:
+        write_state_log(outputs.state_log, sim, plan, ids)
+        log(f"written {outputs.state_log}")
+    if tensors is not None:
+        import torch
+        import torch.distributed as dist
+    occupancies, missed = [], []
+    for k, iid in enumerate(ids):
+        if iid is None:
+            occupancies.append(None)
+            missed.append(0)
+            continue
+        _, n_missed, occ = sim.copy_outputs(iid, want_contacts=False)
+        if tensors is not None:
+            tc, to = tensors[k]
+            dist.reduce(tc, dst=0, op=dist.ReduceOp.SUM)
+            dist.reduce(to, dst=0, op=dist.ReduceOp.SUM)
+            occ = to.cpu().numpy().view(np.uint64) if occ is not None else None
+        occupancies.append(occ)
+        missed.append(n_missed)
+    if tensors is not None:
+        torch.cuda.synchronize(torch.device("cuda", sim.device))
+    if rank != 0:
+        return occupancies
+    if outputs.cooler is None:
+        for k, iid in enumerate(ids):
+            if iid is not None:
+                d_contacts, _, nrows, ncols = sim.outputs(iid)
+                stats = pixels.extractor(sim.device).count(d_contacts, nrows, ncols)
+                warn_missing(plan[k]["interval"]["name"], stats.sum, missed[k], log)
+        return occupancies
+    write_pixels(outputs.cooler, cfg, plan, functools.partial(_interval_pixels, sim, plan, ids, missed, log),
+                 bin_sizes, **attrs)
+    log(f"written {outputs.cooler}")
+    if outputs.dense is not None:
+        # (the cooler's INT32 range check has passed: the uint32 words are int32 counts; with
+        # several ranks the region is unpacked from the reduced tensor, like the pixels)
+        np.savez(outputs.dense, **{key: sim.dense(ids[k], lo, hi).view(np.int32) for k, lo, hi, key in regions})
+        log(f"written {outputs.dense}")
+    return occupancies
 
 
 # ---------------------------------------------------------------------------------------------

@@ -21,6 +21,7 @@ _LIB = None
 _EXTRACTORS = {}
 
 Stats = namedtuple("Stats", "nnz sum max_count")
+Pixels = namedtuple("Pixels", "bin1 bin2 count bin1_offset stats")  # what extract / coarse_extract return
 
 
 class _CStats(C.Structure):  # modle_pixels_stats
@@ -84,6 +85,14 @@ def _host_array(ptr, n, dtype):
     return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(n,)).copy()
 
 
+def _call(fn, *args):
+    """`fn(*args, err, errlen)`: every entry point of the library that can fail"""
+    err = C.create_string_buffer(512)
+    rc = fn(*args, err, len(err))
+    if rc != 0:
+        raise PixelsError(rc, err.value.decode(errors="replace"))
+
+
 def coarse_shape(nrows, ncols, factor, first_bin=0):
     """(nrows', ncols') of the band coarsened by `factor` (modle_pixels_coarse_shape; no device is
     needed).  `first_bin`: chromosome-relative index of the interval's first fine bin."""
@@ -113,11 +122,11 @@ class Extractor:
     def __init__(self, device=0):
         self._L = lib()
         self._h = C.c_void_p()
-        err = C.create_string_buffer(512)
-        rc = self._L.modle_pixels_create(int(device), C.byref(self._h), err, len(err))
-        if rc != 0:
+        try:
+            _call(self._L.modle_pixels_create, int(device), C.byref(self._h))
+        except PixelsError:
             self._h = None
-            raise PixelsError(rc, err.value.decode(errors="replace"))
+            raise
         self.device = int(device)
 
     def close(self):
@@ -142,91 +151,65 @@ class Extractor:
         """step 1: fills the device array `d_bin1_offset` (int64[ncols + 1], a device pointer; None
         when only the statistics are wanted) and returns Stats; waits for the stream"""
         st = _CStats()
-        err = C.create_string_buffer(512)
-        rc = self._L.modle_pixels_count(self._h, d_band, int(nrows), int(ncols), d_bin1_offset,
-                                        C.byref(st), _stream_ptr(stream), err, len(err))
-        if rc != 0:
-            raise PixelsError(rc, err.value.decode(errors="replace"))
+        _call(self._L.modle_pixels_count, self._h, d_band, int(nrows), int(ncols), d_bin1_offset,
+              C.byref(st), _stream_ptr(stream))
         return Stats(st.nnz, st.sum, st.max_count)
 
     def extract_into(self, d_band, nrows, ncols, bin_offset, d_bin1_offset, d_bin1, d_bin2, d_count,
                      nnz, stream=None):
         """step 2: enqueues the extraction into caller-owned device arrays of `nnz` entries"""
-        err = C.create_string_buffer(512)
-        rc = self._L.modle_pixels_extract(self._h, d_band, int(nrows), int(ncols), int(bin_offset),
-                                          d_bin1_offset, d_bin1, d_bin2, d_count, int(nnz),
-                                          _stream_ptr(stream), err, len(err))
-        if rc != 0:
-            raise PixelsError(rc, err.value.decode(errors="replace"))
+        _call(self._L.modle_pixels_extract, self._h, d_band, int(nrows), int(ncols), int(bin_offset),
+              d_bin1_offset, d_bin1, d_bin2, d_count, int(nnz), _stream_ptr(stream))
 
-    def extract(self, d_band, nrows, ncols, bin_offset=0, stream=None):
-        """one-call form: numpy bin1, bin2 (int64), count (int32), bin1_offset (int64[ncols + 1])
-        and Stats(nnz, sum, max_count).  A count above INT32_MAX raises PixelsError(ERR_RANGE)."""
+    def _to_host(self, fn, ncols_out, *args, stream=None):
+        """a one-call form `fn(handle, *args, four array pointers, stats, stream, err)`: the
+        context's pinned arrays, copied into numpy arrays the caller owns.  `ncols_out()` is asked
+        for the columns of the extracted band once the library has accepted the arguments."""
         p1, p2, pc, po = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
         st = _CStats()
-        err = C.create_string_buffer(512)
-        rc = self._L.modle_pixels_to_host(self._h, d_band, int(nrows), int(ncols), int(bin_offset),
-                                          C.byref(p1), C.byref(p2), C.byref(pc), C.byref(po),
-                                          C.byref(st), _stream_ptr(stream), err, len(err))
-        if rc != 0:
-            raise PixelsError(rc, err.value.decode(errors="replace"))
+        _call(fn, self._h, *args, C.byref(p1), C.byref(p2), C.byref(pc), C.byref(po), C.byref(st),
+              _stream_ptr(stream))
         n = int(st.nnz)
-        return (_host_array(p1.value, n, np.int64), _host_array(p2.value, n, np.int64),
-                _host_array(pc.value, n, np.int32), _host_array(po.value, int(ncols) + 1, np.int64),
-                Stats(st.nnz, st.sum, st.max_count))
+        return Pixels(_host_array(p1.value, n, np.int64), _host_array(p2.value, n, np.int64),
+                      _host_array(pc.value, n, np.int32), _host_array(po.value, ncols_out() + 1, np.int64),
+                      Stats(st.nnz, st.sum, st.max_count))
+
+    def extract(self, d_band, nrows, ncols, bin_offset=0, stream=None):
+        """one-call form: Pixels of numpy bin1, bin2 (int64), count (int32), bin1_offset
+        (int64[ncols + 1]) and Stats(nnz, sum, max_count).  A count above INT32_MAX raises
+        PixelsError(ERR_RANGE)."""
+        return self._to_host(self._L.modle_pixels_to_host, lambda: int(ncols), d_band, int(nrows), int(ncols),
+                             int(bin_offset), stream=stream)
 
     def coarsen_into(self, d_band, nrows, ncols, factor, first_bin, d_out, out_words, stream=None):
         """enqueues the coarsening of the band by `factor` into the caller-owned device array
         `d_out` of `out_words` >= nrows' * ncols' + 1 words, all of which are written
         (modle_pixels_coarsen); returns (nrows', ncols')"""
-        err = C.create_string_buffer(512)
-        rc = self._L.modle_pixels_coarsen(self._h, d_band, int(nrows), int(ncols), int(factor),
-                                          int(first_bin), d_out, int(out_words), _stream_ptr(stream),
-                                          err, len(err))
-        if rc != 0:
-            raise PixelsError(rc, err.value.decode(errors="replace"))
+        _call(self._L.modle_pixels_coarsen, self._h, d_band, int(nrows), int(ncols), int(factor),
+              int(first_bin), d_out, int(out_words), _stream_ptr(stream))
         return coarse_shape(nrows, ncols, factor, first_bin)
 
     def coarse_extract(self, d_band, nrows, ncols, factor, first_bin, bin_offset=0, stream=None):
         """one-call form at `factor` times the bin size (modle_pixels_coarse_to_host): what
         extract returns, for the coarse band; bin1_offset has ncols' + 1 entries and `bin_offset`
         counts coarse bins.  A sum above INT32_MAX raises PixelsError(ERR_RANGE)."""
-        p1, p2, pc, po = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
-        st = _CStats()
-        err = C.create_string_buffer(512)
-        rc = self._L.modle_pixels_coarse_to_host(self._h, d_band, int(nrows), int(ncols), int(factor),
-                                                 int(first_bin), int(bin_offset), C.byref(p1),
-                                                 C.byref(p2), C.byref(pc), C.byref(po), C.byref(st),
-                                                 _stream_ptr(stream), err, len(err))
-        if rc != 0:
-            raise PixelsError(rc, err.value.decode(errors="replace"))
-        n = int(st.nnz)
-        _, ncols_out = coarse_shape(nrows, ncols, factor, first_bin)
-        return (_host_array(p1.value, n, np.int64), _host_array(p2.value, n, np.int64),
-                _host_array(pc.value, n, np.int32), _host_array(po.value, ncols_out + 1, np.int64),
-                Stats(st.nnz, st.sum, st.max_count))
-
+        return self._to_host(self._L.modle_pixels_coarse_to_host,
+                             lambda: coarse_shape(nrows, ncols, factor, first_bin)[1], d_band, int(nrows),
+                             int(ncols), int(factor), int(first_bin), int(bin_offset), stream=stream)
 
     def dense_tiles_into(self, d_band, nrows, ncols, first, size, step, count, d_out, out_words, stream=None):
         """enqueues the unpacking of `count` square tiles (tile t: the bins first + t * step ..
         + size - 1) into the caller-owned device array `d_out` of `out_words` >= count * size * size
         words, uint32[count][size][size], all of which are written (modle_pixels_dense_tiles)"""
-        err = C.create_string_buffer(512)
-        rc = self._L.modle_pixels_dense_tiles(self._h, d_band, int(nrows), int(ncols), int(first), int(size),
-                                              int(step), int(count), d_out, int(out_words),
-                                              _stream_ptr(stream), err, len(err))
-        if rc != 0:
-            raise PixelsError(rc, err.value.decode(errors="replace"))
+        _call(self._L.modle_pixels_dense_tiles, self._h, d_band, int(nrows), int(ncols), int(first), int(size),
+              int(step), int(count), d_out, int(out_words), _stream_ptr(stream))
 
     def dense(self, d_band, nrows, ncols, lo, hi, stream=None):
         """the symmetric matrix of the bins [lo, hi) as a numpy uint32[hi - lo, hi - lo] the caller
         owns, unpacked on the device (modle_pixels_dense_to_host)"""
         ptr = C.c_void_p()
-        err = C.create_string_buffer(512)
-        rc = self._L.modle_pixels_dense_to_host(self._h, d_band, int(nrows), int(ncols), int(lo), int(hi),
-                                                C.byref(ptr), _stream_ptr(stream), err, len(err))
-        if rc != 0:
-            raise PixelsError(rc, err.value.decode(errors="replace"))
+        _call(self._L.modle_pixels_dense_to_host, self._h, d_band, int(nrows), int(ncols), int(lo), int(hi),
+              C.byref(ptr), _stream_ptr(stream))
         n = int(hi) - int(lo)
         return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint32)), shape=(n, n)).copy()
 

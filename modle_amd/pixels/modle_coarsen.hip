@@ -163,16 +163,10 @@ extern "C" int modle_pixels_coarse_to_host(modle_pixels_handle* h, const uint32_
   const uint64_t words = nr * nc + 1;
   const hipStream_t st = static_cast<hipStream_t>(stream);
   PIX_TRY(hipSetDevice(h->device));
-  if (words > h->cap_coarse) {
-    (void)hipFree(h->d_coarse);
-    h->d_coarse = nullptr;
-    h->cap_coarse = 0;
-    const uint64_t n = words + words / 8;  // some room, like the pixel buffers
-    PIX_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_coarse), n * 4));
-    h->cap_coarse = n;
-  }
-  const int rc = coarsen_impl(h, d_band, nrows, ncols, factor, first_bin, h->d_coarse, nr, nc, st, err, errlen);
+  int rc = h->coarse.ensure(words, err, errlen);
   if (rc != MODLE_PIXELS_OK) return rc;
-  return modle_pixels_detail::to_host(h, h->d_coarse, nr, nc, bin_offset, bin1, bin2, count, bin1_offset, stats,
+  rc = coarsen_impl(h, d_band, nrows, ncols, factor, first_bin, h->coarse.dev, nr, nc, st, err, errlen);
+  if (rc != MODLE_PIXELS_OK) return rc;
+  return modle_pixels_detail::to_host(h, h->coarse.dev, nr, nc, bin_offset, bin1, bin2, count, bin1_offset, stats,
                                       st, err, errlen);
 }

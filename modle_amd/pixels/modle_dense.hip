@@ -188,19 +188,12 @@ extern "C" int modle_pixels_dense_to_host(modle_pixels_handle* h, const uint32_t
   }
   const hipStream_t st = static_cast<hipStream_t>(stream);
   PIX_TRY(hipSetDevice(h->device));
-  if (words > h->cap_dense) {
-    (void)hipFree(h->d_dense), h->d_dense = nullptr;
-    (void)hipHostFree(h->h_dense), h->h_dense = nullptr;
-    h->cap_dense = 0;
-    const uint64_t n = words + words / 8;  // some room, like the pixel buffers
-    PIX_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_dense), n * 4));
-    PIX_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->h_dense), n * 4, hipHostMallocDefault));
-    h->cap_dense = n;
-  }
-  const int rc = dense_impl(h, d_band, nrows, lo, hi - lo, 1, 1, h->d_dense, st, err, errlen);
+  int rc = h->dense.ensure(words, err, errlen);
   if (rc != MODLE_PIXELS_OK) return rc;
-  PIX_TRY(hipMemcpyAsync(h->h_dense, h->d_dense, words * 4, hipMemcpyDeviceToHost, st));
+  rc = dense_impl(h, d_band, nrows, lo, hi - lo, 1, 1, h->dense.dev, st, err, errlen);
+  if (rc != MODLE_PIXELS_OK) return rc;
+  PIX_TRY(hipMemcpyAsync(h->dense.host, h->dense.dev, words * 4, hipMemcpyDeviceToHost, st));
   PIX_TRY(hipStreamSynchronize(st));
-  *dense = h->h_dense;
+  *dense = h->dense.host;
   return MODLE_PIXELS_OK;
 }

@@ -180,38 +180,12 @@ namespace {
 using modle_pixels_detail::bad_shape;
 using modle_pixels_detail::set_err;
 
-void free_buffers(modle_pixels_handle* h, bool pixels, bool offsets) {
-  if (pixels) {
-    for (void** p : {&h->d_bin1, &h->d_bin2, &h->d_count}) (void)hipFree(*p), *p = nullptr;
-    for (void** p : {&h->h_bin1, &h->h_bin2, &h->h_count}) (void)hipHostFree(*p), *p = nullptr;
-    h->cap_pixels = 0;
-  }
-  if (offsets) {
-    (void)hipFree(h->d_offsets), h->d_offsets = nullptr;
-    (void)hipHostFree(h->h_offsets), h->h_offsets = nullptr;
-    h->cap_offsets = 0;
-  }
-}
-
-int reserve(modle_pixels_handle* h, uint64_t n_pixels, uint64_t n_offsets, char* err, size_t errlen) {
-  if (n_offsets > h->cap_offsets) {
-    free_buffers(h, false, true);
-    PIX_TRY(hipMalloc(&h->d_offsets, n_offsets * 8));
-    PIX_TRY(hipHostMalloc(&h->h_offsets, n_offsets * 8, hipHostMallocDefault));
-    h->cap_offsets = n_offsets;
-  }
-  if (n_pixels > h->cap_pixels) {
-    free_buffers(h, true, false);
-    const uint64_t n = n_pixels + n_pixels / 8;  // some room: the next interval is rarely the same size
-    PIX_TRY(hipMalloc(&h->d_bin1, n * 8));
-    PIX_TRY(hipMalloc(&h->d_bin2, n * 8));
-    PIX_TRY(hipMalloc(&h->d_count, n * 4));
-    PIX_TRY(hipHostMalloc(&h->h_bin1, n * 8, hipHostMallocDefault));
-    PIX_TRY(hipHostMalloc(&h->h_bin2, n * 8, hipHostMallocDefault));
-    PIX_TRY(hipHostMalloc(&h->h_count, n * 4, hipHostMallocDefault));
-    h->cap_pixels = n;
-  }
-  return MODLE_PIXELS_OK;
+// the pixel arrays of the one-call form, sized by nnz
+int reserve_pixels(modle_pixels_handle* h, uint64_t nnz, char* err, size_t errlen) {
+  int rc = h->bin1.ensure(nnz, err, errlen);
+  if (rc == MODLE_PIXELS_OK) rc = h->bin2.ensure(nnz, err, errlen);
+  if (rc == MODLE_PIXELS_OK) rc = h->count.ensure(nnz, err, errlen);
+  return rc;
 }
 
 int count_impl(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols,
@@ -289,13 +263,9 @@ extern "C" int modle_pixels_create(int device, modle_pixels_handle** out, char* 
 extern "C" void modle_pixels_destroy(modle_pixels_handle* h) {
   if (h == nullptr) return;
   (void)hipSetDevice(h->device);
-  free_buffers(h, true, true);
-  (void)hipFree(h->d_coarse);
-  (void)hipFree(h->d_dense);
-  (void)hipHostFree(h->h_dense);
   (void)hipFree(h->d_stats);
   (void)hipHostFree(h->h_stats);
-  delete h;
+  delete h;  // (releases every buffer of the context)
 }
 
 extern "C" int modle_pixels_count(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
@@ -307,9 +277,9 @@ extern "C" int modle_pixels_count(modle_pixels_handle* h, const uint32_t* d_band
   }
   if (d_bin1_offset == nullptr) {  // statistics only: the index goes to the context's own array
     PIX_TRY(hipSetDevice(h->device));
-    const int rc = reserve(h, 0, ncols + 1, err, errlen);
+    const int rc = h->offsets.ensure(ncols + 1, err, errlen, /*room=*/false);
     if (rc != MODLE_PIXELS_OK) return rc;
-    d_bin1_offset = static_cast<int64_t*>(h->d_offsets);
+    d_bin1_offset = h->offsets.dev;
   }
   return count_impl(h, d_band, nrows, ncols, d_bin1_offset, stats, static_cast<hipStream_t>(stream), err,
                     errlen);
@@ -351,28 +321,27 @@ int modle_pixels_detail::to_host(modle_pixels_handle* h, const uint32_t* d_band,
   *count = nullptr;
   *bin1_offset = nullptr;
   PIX_TRY(hipSetDevice(h->device));
-  int rc = reserve(h, 0, ncols + 1, err, errlen);
+  int rc = h->offsets.ensure(ncols + 1, err, errlen, /*room=*/false);
   if (rc != MODLE_PIXELS_OK) return rc;
-  rc = count_impl(h, d_band, nrows, ncols, static_cast<int64_t*>(h->d_offsets), stats, st, err, errlen);
+  rc = count_impl(h, d_band, nrows, ncols, h->offsets.dev, stats, st, err, errlen);
   if (rc != MODLE_PIXELS_OK) return rc;
-  rc = reserve(h, stats->nnz, ncols + 1, err, errlen);
+  rc = reserve_pixels(h, stats->nnz, err, errlen);
   if (rc != MODLE_PIXELS_OK) return rc;
-  rc = extract_impl(h, d_band, nrows, ncols, bin_offset, static_cast<const int64_t*>(h->d_offsets),
-                    static_cast<int64_t*>(h->d_bin1), static_cast<int64_t*>(h->d_bin2),
-                    static_cast<int32_t*>(h->d_count), stats->nnz, st, err, errlen);
+  rc = extract_impl(h, d_band, nrows, ncols, bin_offset, h->offsets.dev, h->bin1.dev, h->bin2.dev, h->count.dev,
+                    stats->nnz, st, err, errlen);
   if (rc != MODLE_PIXELS_OK) return rc;
-  PIX_TRY(hipMemcpyAsync(h->h_offsets, h->d_offsets, (ncols + 1) * 8, hipMemcpyDeviceToHost, st));
+  PIX_TRY(hipMemcpyAsync(h->offsets.host, h->offsets.dev, (ncols + 1) * 8, hipMemcpyDeviceToHost, st));
   if (stats->nnz != 0) {
-    PIX_TRY(hipMemcpyAsync(h->h_bin1, h->d_bin1, stats->nnz * 8, hipMemcpyDeviceToHost, st));
-    PIX_TRY(hipMemcpyAsync(h->h_bin2, h->d_bin2, stats->nnz * 8, hipMemcpyDeviceToHost, st));
-    PIX_TRY(hipMemcpyAsync(h->h_count, h->d_count, stats->nnz * 4, hipMemcpyDeviceToHost, st));
+    PIX_TRY(hipMemcpyAsync(h->bin1.host, h->bin1.dev, stats->nnz * 8, hipMemcpyDeviceToHost, st));
+    PIX_TRY(hipMemcpyAsync(h->bin2.host, h->bin2.dev, stats->nnz * 8, hipMemcpyDeviceToHost, st));
+    PIX_TRY(hipMemcpyAsync(h->count.host, h->count.dev, stats->nnz * 4, hipMemcpyDeviceToHost, st));
   }
   PIX_TRY(hipStreamSynchronize(st));
-  *bin1_offset = static_cast<const int64_t*>(h->h_offsets);
+  *bin1_offset = h->offsets.host;
   if (stats->nnz != 0) {
-    *bin1 = static_cast<const int64_t*>(h->h_bin1);
-    *bin2 = static_cast<const int64_t*>(h->h_bin2);
-    *count = static_cast<const int32_t*>(h->h_count);
+    *bin1 = h->bin1.host;
+    *bin2 = h->bin2.host;
+    *count = h->count.host;
   }
   return MODLE_PIXELS_OK;
 }

@@ -16,22 +16,6 @@ struct DeviceStats {
   unsigned int pad_;
 };
 
-struct modle_pixels_handle {
-  int device = 0;
-  DeviceStats* d_stats = nullptr;
-  DeviceStats* h_stats = nullptr;  // pinned
-  // one-call form: device arrays and their pinned host mirrors, grown on demand
-  void *d_bin1 = nullptr, *d_bin2 = nullptr, *d_count = nullptr, *d_offsets = nullptr;
-  void *h_bin1 = nullptr, *h_bin2 = nullptr, *h_count = nullptr, *h_offsets = nullptr;
-  uint64_t cap_pixels = 0, cap_offsets = 0;
-  // modle_pixels_coarse_to_host: the coarse band (modle_coarsen.hip), grown on demand
-  uint32_t* d_coarse = nullptr;
-  uint64_t cap_coarse = 0;  // words
-  // modle_pixels_dense_to_host: the region (modle_dense.hip) and its pinned host mirror, grown on demand
-  uint32_t *d_dense = nullptr, *h_dense = nullptr;
-  uint64_t cap_dense = 0;  // words
-};
-
 namespace modle_pixels_detail {
 
 void set_err(char* err, size_t errlen, const std::string& msg);
@@ -56,5 +40,42 @@ int to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint
       return MODLE_PIXELS_ERR_DEVICE;                                                           \
     }                                                                                           \
   } while (0)
+
+// A device array grown on demand, with (kMirror) a pinned host array of the same size.
+template <class T, bool kMirror = false>
+struct GrowBuf {
+  T* dev = nullptr;
+  T* host = nullptr;  // pinned; null without a mirror
+  uint64_t cap = 0;   // elements
+  ~GrowBuf() { release(); }
+  void release() {
+    (void)hipFree(dev), dev = nullptr;
+    (void)hipHostFree(host), host = nullptr;
+    cap = 0;
+  }
+  // Room for `n` elements: only when n exceeds the capacity, the arrays are freed and allocated
+  // anew, `room` adding an eighth (the next interval is rarely the same size).  A failure leaves
+  // the capacity at 0, so that the next call allocates again.
+  int ensure(uint64_t n, char* err, size_t errlen, bool room = true) {
+    if (n <= cap) return MODLE_PIXELS_OK;
+    release();
+    if (room) n += n / 8;
+    PIX_TRY(hipMalloc(reinterpret_cast<void**>(&dev), n * sizeof(T)));
+    if (kMirror) PIX_TRY(hipHostMalloc(reinterpret_cast<void**>(&host), n * sizeof(T), hipHostMallocDefault));
+    cap = n;
+    return MODLE_PIXELS_OK;
+  }
+};
+
+struct modle_pixels_handle {
+  int device = 0;
+  DeviceStats* d_stats = nullptr;
+  DeviceStats* h_stats = nullptr;  // pinned
+  // one-call form: the pixels (sized by nnz) and the bin1_offset index (ncols + 1 entries, exactly)
+  GrowBuf<int64_t, true> bin1, bin2, offsets;
+  GrowBuf<int32_t, true> count;
+  GrowBuf<uint32_t> coarse;       // modle_pixels_coarse_to_host: the coarse band (modle_coarsen.hip)
+  GrowBuf<uint32_t, true> dense;  // modle_pixels_dense_to_host: the region (modle_dense.hip)
+};
 
 #endif

@@ -202,7 +202,7 @@ def test_invalid_shapes_are_argument_errors(ex, sample):
 
 def test_simulated_interval_to_cooler_through_pixels(tmp_path):
     """a 2 Mb chromosome with barriers (and one without, which is skipped), 8 cells:
-    Simulator.pixels equals the reference applied to the dense matrix, write_cooler_pixels writes
+    Simulator.pixels equals the reference applied to the dense matrix, write_pixels writes
     the file write_cooler writes, and the front end's file is the same file"""
     from test_cooler_pixels import assert_same_cooler
 
@@ -237,8 +237,9 @@ def test_simulated_interval_to_cooler_through_pixels(tmp_path):
         assert ref["nnz"] > 1000
         assert_equal_to_reference(sim.pixels(ids[0]), ref)
         assert_equal_to_reference(sim.pixels(ids[0], bin_offset=77), ref, 77)
-        driver.write_cooler_pixels(sparse_path, cfg, plan,
-                                   lambda k, off: None if ids[k] is None else sim.pixels(ids[k], off), **kw)
+        driver.write_pixels(sparse_path, cfg, plan,
+                            lambda k, factor, first_bin, off: None if ids[k] is None else sim.pixels(ids[k], off),
+                            **kw)
     finally:
         sim.close()
     driver.write_cooler(dense_path, cfg, plan, [dense, None], **kw)
