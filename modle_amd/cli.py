@@ -11,7 +11,7 @@ contacts at several bin sizes, coarsened on the GPU) and, with the 1-D LEF posit
 square matrices of the named regions, unpacked on the GPU.  Everything heavy is native: parsing and
 task generation in libmodle_hip.so (host), the simulation on the MI355X (one process per GPU;
 under torch.distributed.run the cells are sharded over the ranks and the matrices are summed
-with RCCL), the writers in libmodle_cooler.so.  `-t/--threads` is accepted and ignored."""
+with RCCL, or with --dist-backend gloo on host copies), the writers in libmodle_cooler.so.  `-t/--threads` is accepted and ignored."""
 import argparse
 import collections
 import decimal
@@ -147,6 +147,10 @@ def build_parser():
     io.add_argument("--skip-chromosomes-wo-barriers", dest="wo_barriers", action="store_false")
     io.add_argument("-t", "--threads", type=int, default=None, help="ignored (the GPU does the work)")
     io.add_argument("--device", type=int, default=None, help="HIP device (default: LOCAL_RANK or 0)")
+    io.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
+                    help="nccl (= RCCL, default): the matrices are reduced on the GPUs over xGMI.  gloo: "
+                         "the same per-interval ordering with the reduce done on host copies -- for "
+                         "rehearsing the N > 1 path with several ranks on ONE GPU (tests; pass --device)")
     g = p.add_argument_group("model parameters (reference names; omitted => reference default)")
     for flags, dest, typ in [
         (("--lef-density", "--lefs-per-mbp"), "number_of_lefs_per_mbp", float),
@@ -301,14 +305,18 @@ def plan_run(a, cfg, pre, log):
     return chroms, plan, regions
 
 
-def open_simulator(cfg, pre):
-    """the process group when there are several ranks, and the simulator on this rank's device"""
+def open_simulator(cfg, pre, backend="nccl"):
+    """the process group when there are several ranks (`backend`: --dist-backend), and the simulator
+    on this rank's device"""
     if pre.world > 1:
         import torch
         import torch.distributed as dist
 
         torch.cuda.set_device(pre.device)
-        dist.init_process_group("nccl", device_id=torch.device("cuda", pre.device))
+        if backend == "nccl":
+            dist.init_process_group("nccl", device_id=torch.device("cuda", pre.device))
+        else:
+            dist.init_process_group("gloo")
     return api.Simulator(cfg, pre.device)
 
 
@@ -347,7 +355,7 @@ def simulate(a, log=print):
     pre = preflight(a, cfg)
     t0 = time.time()
     chroms, plan, regions = plan_run(a, cfg, pre, log)
-    sim = open_simulator(cfg, pre)
+    sim = open_simulator(cfg, pre, a.dist_backend)
     try:
         ids, tensors = run_plan(sim, a, cfg, plan, pre, log)
         # The contact matrices stay on the device: the cooler is written from their non-zero
@@ -355,7 +363,7 @@ def simulate(a, log=print):
         meta = json.dumps({k: v for k, v in vars(a).items() if v is not None and k != "command"},
                           sort_keys=True)
         occupancies = driver.write_outputs(
-            sim, cfg, plan, ids, tensors, pre.outputs, pre.bin_sizes, regions, pre.rank, log,
+            sim, cfg, plan, ids, tensors, pre.outputs, pre.bin_sizes, regions, pre.rank, log, a.dist_backend,
             assembly=a.assembly_name, generated_by="modle_amd (MI355X)", metadata_json=meta,
             force_overwrite=a.force, chroms=chroms)
     finally:

@@ -346,14 +346,45 @@ def _interval_pixels(sim, plan, ids, missed, log, k, factor, first_bin, bin_offs
     return px
 
 
+def reduce_to_rank0(t, backend, rank):
+    """Sum of the ranks' tensors `t` into rank 0's, in place (the other ranks' tensors are unspecified
+    afterwards).  `nccl` (= RCCL): on the device tensors.  `gloo`: on host copies -- the rehearsal with
+    several ranks on one GPU; the copy synchronises the current stream.  int32 / int64 words that hold
+    unsigned counts stay exact modulo 2^32 / 2^64 (two's complement sums)."""
+    import torch.distributed as dist
+
+    if backend == "nccl":
+        dist.reduce(t, dst=0, op=dist.ReduceOp.SUM)
+    else:
+        h = t.cpu()
+        dist.reduce(h, dst=0, op=dist.ReduceOp.SUM)
+        if rank == 0:
+            t.copy_(h)
+
+
+def reduce_missed(missed, backend, rank, device=None):
+    """The missed-update counts per plan entry (None: an entry without a matrix, zero) summed over
+    the ranks, as ints on rank 0: one reduce of one int64 vector, whatever the ranks' shards hold.
+    `device`: the torch device of the vector under `nccl`."""
+    import torch
+
+    t = torch.tensor([0 if m is None else int(m) for m in missed], dtype=torch.int64,
+                     device=device if backend == "nccl" else "cpu")
+    if len(missed) != 0:
+        reduce_to_rank0(t, backend, rank)
+    return [int(m) for m in t.tolist()]
+
+
 def write_outputs(sim, cfg, plan, ids, tensors, outputs, bin_sizes=None, regions=(), rank=0, log=print,
-                  **attrs):
+                  backend="nccl", **attrs):
     """What a finished launch writes while the simulator is open: the state log (every rank its
     own), then on rank 0 the cooler or .mcool with the missing-interactions warnings, and the dense
     `regions` (of dense_regions).  `outputs.state_log`, `.cooler`, `.dense`: the paths, None for a file
     that is not written; without a cooler (--skip-output) the matrices are only summed, for the
     warnings.  `tensors`: with several ranks the (contacts, occupancy) torch tensors per plan entry;
-    they are reduced in place onto rank 0, which extracts from the reduced tensor without a host copy.
+    they are reduced in place onto rank 0 (reduce_to_rank0 with `backend`), which extracts from the
+    reduced tensor without a host copy; the missed-update counts are summed over the ranks as well, so
+    that the warnings weigh the whole job's missed updates against the whole job's matrix.
     `attrs`: write_pixels' keywords.  Returns the occupancies per plan entry, for write_bigwig."""
     from . import pixels
 
@@ -362,7 +393,8 @@ def write_outputs(sim, cfg, plan, ids, tensors, outputs, bin_sizes=None, regions
         log(f"written {outputs.state_log}")
     if tensors is not None:
         import torch
-        import torch.distributed as dist
+
+        dev = torch.device("cuda", sim.device)
     occupancies, missed = [], []
     for k, iid in enumerate(ids):
         if iid is None:
@@ -372,13 +404,16 @@ def write_outputs(sim, cfg, plan, ids, tensors, outputs, bin_sizes=None, regions
         _, n_missed, occ = sim.copy_outputs(iid, want_contacts=False)
         if tensors is not None:
             tc, to = tensors[k]
-            dist.reduce(tc, dst=0, op=dist.ReduceOp.SUM)
-            dist.reduce(to, dst=0, op=dist.ReduceOp.SUM)
+            reduce_to_rank0(tc, backend, rank)
+            reduce_to_rank0(to, backend, rank)
             occ = to.cpu().numpy().view(np.uint64) if occ is not None else None
         occupancies.append(occ)
         missed.append(n_missed)
     if tensors is not None:
-        torch.cuda.synchronize(torch.device("cuda", sim.device))
+        # (every rank issues the same collectives in the same order: two per registered interval,
+        # then this one; an entry that is skipped costs none)
+        missed = reduce_missed(missed, backend, rank, dev)
+        torch.cuda.synchronize(dev)
     if rank != 0:
         return occupancies
     if outputs.cooler is None:

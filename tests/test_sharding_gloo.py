@@ -88,6 +88,53 @@ def test_two_rank_gloo_reduce_equals_single_rank(oracle, tmp_path):
         assert int(np.load(tmp_path / f"m{k}.npy")[0]) == out[1]
 
 
+# words of the two ranks (uint32, then uint64): small; two addends below 2^31 (2^63) whose sum is
+# above it -- the sign bit of the int32 (int64) the tensor is declared as; a sum that passes 2^32
+# (2^64) and wraps, as the device's unsigned words do; zero; one addend that has the top bit already
+WORDS32 = (np.array([1, 0x7FFFFFFF, 0x60000000, 0xFFFFFFF0, 0, 123456], dtype=np.uint32),
+           np.array([2, 1, 0x60000000, 0x20, 0, 0x80000001], dtype=np.uint32))
+WORDS64 = (np.array([1, 2**62, 2**63 - 1, 2**64 - 16, 0, 5], dtype=np.uint64),
+           np.array([2, 2**62, 1, 0x20, 0, 2**63 + 2**40], dtype=np.uint64))
+# missed-update counts per plan entry of the two ranks; None: an entry that is skipped
+MISSED = ([3, None, 2**40, 0, 9], [4, None, 5, 7, 0])
+
+
+def _reduce_worker(rank, world, port, tmpdir):
+    sys.path.insert(0, ROOT)
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from modle_amd import driver
+
+    t32 = torch.from_numpy(WORDS32[rank].view(np.int32).copy())
+    t64 = torch.from_numpy(WORDS64[rank].view(np.int64).copy())
+    driver.reduce_to_rank0(t32, "gloo", rank)
+    driver.reduce_to_rank0(t64, "gloo", rank)
+    missed = driver.reduce_missed(MISSED[rank], "gloo", rank)
+    nothing = driver.reduce_missed([], "gloo", rank)
+    if rank == 0:
+        np.save(os.path.join(tmpdir, "t32.npy"), t32.numpy().view(np.uint32))
+        np.save(os.path.join(tmpdir, "t64.npy"), t64.numpy().view(np.uint64))
+        np.save(os.path.join(tmpdir, "missed.npy"), np.array(missed, dtype=np.int64))
+        assert nothing == [] and all(type(m) is int for m in missed)
+    dist.destroy_process_group()
+
+
+def test_reduce_to_rank0_over_gloo_is_the_exact_unsigned_sum(tmp_path):
+    """driver.reduce_to_rank0 / reduce_missed as `simulate --dist-backend gloo` calls them, on host
+    tensors: rank 0 ends with the sums modulo 2^32 / 2^64 (numpy's unsigned arithmetic is the
+    reference); rank 1's tensors are unspecified"""
+    port = 33500 + os.getpid() % 2000
+    mp.spawn(_reduce_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    want32, want64 = WORDS32[0] + WORDS32[1], WORDS64[0] + WORDS64[1]
+    assert want32.tolist() == [3, 0x80000000, 0xC0000000, 0x10, 0, 0x80000001 + 123456]  # (wraps: no error)
+    assert want64.tolist() == [3, 2**63, 2**63, 0x10, 0, 2**63 + 2**40 + 5]
+    got32, got64 = np.load(tmp_path / "t32.npy"), np.load(tmp_path / "t64.npy")
+    assert got32.dtype == np.uint32 and np.array_equal(got32, want32)
+    assert got64.dtype == np.uint64 and np.array_equal(got64, want64)
+    assert np.load(tmp_path / "missed.npy").tolist() == [7, 0, 2**40 + 5, 7, 9]
+
+
 def _devices_worker(rank, world, port, tmpdir, shared):
     sys.path.insert(0, ROOT)
     os.environ["MASTER_ADDR"] = "127.0.0.1"

@@ -73,6 +73,22 @@ def test_preflight_reads_rank_world_and_device_from_the_launcher(prefix, monkeyp
     assert pre.outputs.state_log == prefix + "_internal_state.rank2.log.gz"
 
 
+def test_dist_backend_parses_defaults_to_nccl_and_refuses_other_values(prefix, capsys):
+    def parse(*extra):
+        return cli.build_parser().parse_args(["simulate", "-c", "g.chrom.sizes", "-b", "b.bed", "-o", prefix, *extra])
+
+    assert parse().dist_backend == "nccl"
+    assert parse("--dist-backend", "nccl").dist_backend == "nccl"
+    assert parse("--dist-backend", "gloo").dist_backend == "gloo"
+    for bad in ("mpi", "GLOO", "rccl", ""):
+        with pytest.raises(SystemExit) as e:
+            parse("--dist-backend", bad)
+        assert e.value.code == 2 and "--dist-backend" in capsys.readouterr().err
+    # the backend settles nothing that preflight settles
+    for options in (TRACK, NO_TRACK + MCOOL, TRACK + REGION + ["--log-model-internal-state", "--device", "3"]):
+        assert run_preflight(prefix, *options, "--dist-backend", "gloo") == run_preflight(prefix, *options)
+
+
 # (files present, options, the file the refusal names -- None: the run may go on)
 CASES = [
     (["cool"], TRACK, "cool"),
