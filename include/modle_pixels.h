@@ -1,5 +1,5 @@
 /* modle_pixels.h -- C ABI of the sparse-pixel extraction (modle_amd/libmodle_pixels.so), of the
- * coarsening of a band and of its dense regions (further down).
+ * coarsening of a band, of its dense regions and of its marginals (further down).
  *
  * The simulation leaves every interval as a dense band matrix in device memory
  * (modle_hip_interval_outputs).  A cooler file is made of the non-zero pixels only, sorted by
@@ -146,6 +146,56 @@ int modle_pixels_dense_tiles(modle_pixels_handle* h, const uint32_t* d_band, uin
 int modle_pixels_dense_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
                                uint64_t ncols, uint64_t lo, uint64_t hi, const uint32_t** dense,
                                void* stream, char* err, size_t errlen);
+
+/* ---- Marginals: the sums per diagonal and per bin --------------------------------------------
+ *
+ *     diag_sum[d] = sum of band[j * nrows + d] over d <= j < ncols,          0 <= d < nrows
+ * is the numerator of the distance-decay curve ("expected"); its denominator, the number of pixels
+ * of diagonal d, is ncols - d and needs no device.
+ *     coverage[i],  0 <= i < ncols,
+ * is row i of the symmetric matrix, with the diagonal pixel counted once and the diagonals below
+ * `min_diag` left out: the column part, band[i * nrows + d] over max(min_diag, 0) <= d <=
+ * min(i, nrows - 1), plus the row part, band[(i + d) * nrows + d] over max(min_diag, 1) <= d <=
+ * min(nrows - 1, ncols - 1 - i).  So the sum of diag_sum is modle_pixels_stats.sum, and with
+ * min_diag == 0 the sum of coverage is 2 * sum - diag_sum[0].  min_diag >= nrows gives a coverage
+ * of zeros.
+ *
+ * Both are exact 64-bit integer sums, whatever the order of summation, from one pass that reads
+ * every pixel word once; the words that are no pixels are never read.  EVERY output word is written
+ * by the call: the caller does not pre-zero.  No sum can overflow for ncols < 2^32: diag_sum[d] is a
+ * sum of at most ncols words below 2^32, coverage[i] of fewer than 2 * nrows, and nrows is below 2^24
+ * (the largest modle_pixels_count accepts).
+ *
+ * MODLE_PIXELS_ERR_ARG, with nothing written: a null handle or band, nrows == 0, nrows > ncols, no
+ * output asked for, an output that overlaps the band. */
+
+/* Enqueues the sums into the device arrays d_diag_sum (uint64[nrows]) and d_coverage
+ * (uint64[ncols]) on `stream`; the call does not wait.  Either may be NULL when that result is not
+ * wanted.  The sums are formed in words of the context and copied out whole, so the arrays need only
+ * be 4-byte aligned (any other alignment is MODLE_PIXELS_ERR_ARG). */
+int modle_pixels_marginals(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                           uint64_t ncols, uint64_t min_diag, uint64_t* d_diag_sum,
+                           uint64_t* d_coverage, void* stream, char* err, size_t errlen);
+
+/* The same into pinned host buffers of the context (grown on demand, freed by
+ * modle_pixels_destroy): *diag_sum (nrows entries) and *coverage (ncols entries) stay valid until
+ * the next call on the context.  Either of `diag_sum` and `coverage` may be NULL.  Waits for
+ * `stream`. */
+int modle_pixels_marginals_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                                   uint64_t ncols, uint64_t min_diag, const uint64_t** diag_sum,
+                                   const uint64_t** coverage, void* stream, char* err,
+                                   size_t errlen);
+
+/* One call at `factor` times the bin size: coarsens into the scratch band of the context (like
+ * modle_pixels_coarse_to_host), then modle_pixels_marginals_to_host on it.  *diag_sum has nrows'
+ * and *coverage ncols' entries (modle_pixels_coarse_shape); `min_diag` counts coarse diagonals.  A
+ * coarse pixel that saturated enters the sums as 0xFFFFFFFF: modle_pixels_coarse_to_host reports
+ * such a band as MODLE_PIXELS_ERR_RANGE. */
+int modle_pixels_coarse_marginals_to_host(modle_pixels_handle* h, const uint32_t* d_band,
+                                          uint64_t nrows, uint64_t ncols, uint64_t factor,
+                                          uint64_t first_bin, uint64_t min_diag,
+                                          const uint64_t** diag_sum, const uint64_t** coverage,
+                                          void* stream, char* err, size_t errlen);
 
 #ifdef __cplusplus
 }

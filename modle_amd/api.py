@@ -133,6 +133,11 @@ def slice_tasks(tasks, lo, hi):
     return out
 
 
+def expected_n_valid(nrows, ncols):
+    """the number of pixels of every diagonal d < nrows of a band of `ncols` columns: ncols - d"""
+    return np.uint64(ncols) - np.arange(nrows, dtype=np.uint64)
+
+
 # ---------------------------------------------------------------------------------------------
 # device path
 # ---------------------------------------------------------------------------------------------
@@ -320,6 +325,50 @@ class Simulator:
         pixels.dense_tiles_into(d_band, nrows, ncols, first, size, step, count, out.data_ptr(), out.numel(),
                                 stream, device=self.device)
         return out
+
+    def marginals(self, interval_id, min_diag=0, factor=1, first_bin=0, stream=None):
+        """(diag_sum, coverage) of the interval, numpy uint64 arrays summed on the device in one pass
+        over the band (pixels.marginals; with `factor` > 1 pixels.coarse_marginals): what expected()
+        and coverage() hand out one half of"""
+        from . import pixels
+
+        d_band, _, nrows, ncols = self.outputs(interval_id)
+        if int(factor) == 1:
+            return pixels.marginals(d_band, nrows, ncols, min_diag, stream, device=self.device)
+        return pixels.coarse_marginals(d_band, nrows, ncols, factor, first_bin, min_diag, stream,
+                                       device=self.device)
+
+    def expected(self, interval_id, factor=1, first_bin=0):
+        """The distance-decay curve of the interval, summed on the device from the band where it lies
+        (pixels.marginals): (diag_sum, n_valid), numpy uint64 arrays with one entry per diagonal d --
+        the sum of the contacts at distance d bins and the number of pixels there, ncols - d; their
+        quotient is P(s).  Call it after wait().  `factor`, `first_bin`: as for pixels(), the curve
+        at `factor` times the bin size."""
+        diag_sum, coverage = self.marginals(interval_id, 0, factor, first_bin)
+        return diag_sum, expected_n_valid(len(diag_sum), len(coverage))
+
+    def coverage(self, interval_id, min_diag=0, factor=1, first_bin=0):
+        """The sum of every row of the interval's symmetric matrix (the diagonal pixel counted once,
+        the diagonals below `min_diag` left out) as a numpy uint64 array with one entry per bin,
+        summed on the device (pixels.marginals).  `factor`, `first_bin`: as for pixels()."""
+        return self.marginals(interval_id, min_diag, factor, first_bin)[1]
+
+    def marginals_tensors(self, interval_id, min_diag=0, stream=None):
+        """(diag_sum, coverage) of the interval as two torch int64 tensors, [nrows] and [ncols], on
+        the simulator's device, filled there by the kernel: nothing crosses to the host.  The words
+        hold the uint64 sums bit for bit.  The work is enqueued on `stream` (None: the default
+        stream, on which torch orders its own work) and not waited for."""
+        import torch
+
+        from . import pixels
+
+        d_band, _, nrows, ncols = self.outputs(interval_id)
+        dev = torch.device("cuda", self.device)
+        diag_sum = torch.empty(nrows, dtype=torch.int64, device=dev)
+        coverage = torch.empty(ncols, dtype=torch.int64, device=dev)
+        pixels.marginals_into(d_band, nrows, ncols, min_diag, diag_sum.data_ptr(), coverage.data_ptr(), stream,
+                              device=self.device)
+        return diag_sum, coverage
 
     def simulate_interval(self, start, end, bar_pos, bar_dir, stp_active, stp_inactive, tasks):
         """One-call seam (modle_hip_simulate_interval): returns contacts, missed, occupancy,

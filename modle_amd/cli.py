@@ -8,7 +8,9 @@ task derivation is `run_simulate`'s (src/libmodle/cpu/scheduler_simulate.cpp:43-
 outputs are the reference's: `<prefix>.cool` (with --mcool-resolutions `<prefix>.mcool`: the same
 contacts at several bin sizes, coarsened on the GPU) and, with the 1-D LEF position track on,
 `<prefix>_lef_1d_occupancy.bw` (cli.cpp:867-882); with --dense-region also `<prefix>_dense.npz`, the
-square matrices of the named regions, unpacked on the GPU.  Everything heavy is native: parsing and
+square matrices of the named regions, unpacked on the GPU; with --expected `<prefix>_expected.tsv`, the
+contacts per diagonal, and with --coverage `<prefix>_coverage.bedgraph`, the contacts per bin, both
+summed on the GPU.  Everything heavy is native: parsing and
 task generation in libmodle_hip.so (host), the simulation on the MI355X (one process per GPU;
 under torch.distributed.run the cells are sharded over the ranks and the matrices are summed
 with RCCL, or with --dist-backend gloo on host copies), the writers in libmodle_cooler.so.  `-t/--threads` is accepted and ignored."""
@@ -115,6 +117,14 @@ def dense_path(prefix):
     return prefix + "_dense.npz"
 
 
+def expected_path(prefix):
+    return prefix + "_expected.tsv"
+
+
+def coverage_path(prefix):
+    return prefix + "_coverage.bedgraph"
+
+
 def build_parser():
     ap = argparse.ArgumentParser(prog="modle_amd", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -138,6 +148,15 @@ def build_parser():
                     help="also write <prefix>_dense.npz with the symmetric int32 matrix of REGION (chrom or "
                          "chrom:start-end, snapped outward to whole bins of -r; inside one simulated "
                          "interval), unpacked on the GPU; may be given several times")
+    io.add_argument("--expected", action="store_true", default=None,
+                    help="also write <prefix>_expected.tsv: the sum and the mean of the contacts per diagonal "
+                         "(the distance-decay curve) of every interval, at -r and at every bin size of "
+                         "--mcool-resolutions, summed on the GPU")
+    io.add_argument("--coverage", action="store_true", default=None,
+                    help="also write <prefix>_coverage.bedgraph: the sum of every bin's row of the symmetric "
+                         "matrix at -r, summed on the GPU")
+    io.add_argument("--coverage-ignore-diags", type=int, default=None, metavar="N",
+                    help="with --coverage: leave out the first N diagonals (default 0)")
     io.add_argument("--log-model-internal-state", action="store_true",
                     help="write <prefix>_internal_state.log.gz: one line of statistics per task and "
                          "epoch (uses the diagnostic build libmodle_hip_statelog.so)")
@@ -259,14 +278,21 @@ def state_log_path(prefix):
 
 
 # what preflight settles; a path is None for a file the run does not write, `state_log` is this rank's
-Outputs = collections.namedtuple("Outputs", "cooler bigwig dense state_log")
+# (`expected` and `coverage` came later: at the end, and None unless asked for)
+Outputs = collections.namedtuple("Outputs", "cooler bigwig dense state_log expected coverage", defaults=(None, None))
 Preflight = collections.namedtuple("Preflight", "bin_sizes outputs rank world device")
 
 
 def preflight(a, cfg):
     """What the arguments alone settle and refuse, without a genome or a GPU.  SystemExit: a bad
-    --mcool-resolutions list; on rank 0, an output that exists without --force (cooler or .mcool, then
-    bigwig, then .npz).  With --skip-output no file is planned and none is looked at."""
+    --mcool-resolutions list; --coverage-ignore-diags without --coverage, or negative; on rank 0, an
+    output that exists without --force (cooler or .mcool, then bigwig, then .npz, then the expected
+    and the coverage file).  With --skip-output no file is planned and none is looked at."""
+    if a.coverage_ignore_diags is not None:
+        if not a.coverage:
+            raise SystemExit("--coverage-ignore-diags needs --coverage")
+        if a.coverage_ignore_diags < 0:
+            raise SystemExit(f"--coverage-ignore-diags: {a.coverage_ignore_diags} is negative")
     # (a bad list ends the run here, before anything is imported or simulated)
     bin_sizes = None if a.mcool_resolutions is None else mcool_bin_sizes(a.mcool_resolutions, cfg.bin_size)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -279,10 +305,12 @@ def preflight(a, cfg):
         f"{a.output_prefix}_internal_state.rank{rank}.log.gz"
     outputs = Outputs(cool_path, bw_path if cfg.track_1d_lef_position else None,
                       dense_path(a.output_prefix) if a.dense_region else None,
-                      log_path if a.log_model_internal_state else None)
+                      log_path if a.log_model_internal_state else None,
+                      expected_path(a.output_prefix) if a.expected else None,
+                      coverage_path(a.output_prefix) if a.coverage else None)
     if rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(cool_path)), exist_ok=True)
-        for p in (outputs.cooler, outputs.bigwig, outputs.dense):
+        for p in (outputs.cooler, outputs.bigwig, outputs.dense, outputs.expected, outputs.coverage):
             if p and os.path.exists(p) and not a.force:
                 raise SystemExit(f"refusing to overwrite {p}: pass --force to overwrite")
     return Preflight(bin_sizes, outputs, rank, world, device)
@@ -364,7 +392,8 @@ def simulate(a, log=print):
                           sort_keys=True)
         occupancies = driver.write_outputs(
             sim, cfg, plan, ids, tensors, pre.outputs, pre.bin_sizes, regions, pre.rank, log, a.dist_backend,
-            assembly=a.assembly_name, generated_by="modle_amd (MI355X)", metadata_json=meta,
+            coverage_min_diag=a.coverage_ignore_diags or 0, assembly=a.assembly_name,
+            generated_by="modle_amd (MI355X)", metadata_json=meta,
             force_overwrite=a.force, chroms=chroms)
     finally:
         sim.close()

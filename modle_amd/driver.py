@@ -335,15 +335,106 @@ def warn_missing(name, total, missed, log):
         log(f"warning: {100.0 * missed / (total + missed):.2f}% missing interactions for {name}")
 
 
-def _interval_pixels(sim, plan, ids, missed, log, k, factor, first_bin, bin_offset):
+def _interval_pixels(sim, plan, ids, missed, log, k, factor, first_bin, bin_offset, sums=None):
     """write_pixels' callback: every resolution from the same matrix on the device (with several
-    ranks: the reduced tensor); the base resolution's sum feeds the missing-interactions warning"""
+    ranks: the reduced tensor); the base resolution's sum feeds the missing-interactions warning and
+    is kept in `sums[k]`, for the check of the marginals"""
     if ids[k] is None:
         return None
     px = sim.pixels(ids[k], bin_offset, factor=factor, first_bin=first_bin)
     if factor == 1:
         warn_missing(plan[k]["interval"]["name"], px.stats.sum, missed[k], log)
+        if sums is not None:
+            sums[k] = int(px.stats.sum)
     return px
+
+
+EXPECTED_HEADER = "chrom\tstart\tend\tbin_size\tdist\tdist_bp\tn_valid\tcount_sum\tcount_avg\n"
+
+
+def interval_name(iv):
+    return f"{iv['name']}:{iv['start']}-{iv['end']}"
+
+
+def check_marginals(name, total, diag_sum, coverage, min_diag=0):
+    """What ties the marginals of a band (api.Simulator.marginals) to the sum of its pixels, `total`
+    (pixels.Stats.sum), in exact integers: the diagonals add up to the total, and the coverage counts
+    every pixel of the diagonals it keeps twice, those of the main diagonal once -- with min_diag == 0
+    that is 2 * total - diag_sum[0].  RuntimeError, naming the interval, when one does not hold."""
+    diag = [int(x) for x in diag_sum]
+    if sum(diag) != int(total):
+        raise RuntimeError(f"{name}: the diagonal sums add up to {sum(diag)}, the pixels to {int(total)}")
+    m = int(min_diag)
+    want = 2 * sum(diag[max(m, 1):]) + (diag[0] if m == 0 else 0)
+    got = sum(int(x) for x in coverage)
+    if got != want:
+        raise RuntimeError(f"{name}: the coverage adds up to {got}, the diagonals from {m} on give {want}")
+
+
+def expected_lines(iv, bin_size, diag_sum, n_valid):
+    """the rows of <prefix>_expected.tsv for one interval at one bin size, one per diagonal d:
+    chrom, start, end, bin_size, dist (d), dist_bp, n_valid, count_sum, count_avg (the repr of the
+    quotient of the two integers)"""
+    head = f"{iv['name']}\t{iv['start']}\t{iv['end']}\t{int(bin_size)}"
+    return [f"{head}\t{d}\t{d * int(bin_size)}\t{int(n)}\t{int(s)}\t{int(s) / int(n)!r}\n"
+            for d, (s, n) in enumerate(zip(diag_sum, n_valid))]
+
+
+def coverage_lines(iv, bin_size, coverage):
+    """the lines of <prefix>_coverage.bedgraph for one interval: chrom, start, end, value per bin;
+    bin i starts i bins after the interval's start and the last one ends with the interval"""
+    start, end, b = int(iv["start"]), int(iv["end"]), int(bin_size)
+    return [f"{iv['name']}\t{start + i * b}\t{min(start + (i + 1) * b, end)}\t{int(c)}\n"
+            for i, c in enumerate(coverage)]
+
+
+def write_expected(path, plan, base, bin_sizes, marginals):
+    """<prefix>_expected.tsv: the distance-decay curve of every entry of the plan that is not skipped,
+    in plan order, then by ascending bin size (`bin_sizes`; None: the base only), then by diagonal.
+    `marginals(k, factor, first_bin)` returns (diag_sum, coverage) of plan entry k at `factor` times
+    the bin size `base` -- what api.Simulator.marginals returns -- or None for an entry without a
+    matrix; the number of pixels of diagonal d is the number of bins less d."""
+    with open(path, "w") as fh:
+        fh.write(EXPECTED_HEADER)
+        for k, entry in enumerate(plan):
+            if entry["skipped"]:
+                continue
+            iv = entry["interval"]
+            for b in (bin_sizes or [int(base)]):
+                got = marginals(k, int(b) // int(base), int(iv["start"]) // int(base))
+                if got is not None:
+                    diag_sum, coverage = got
+                    n_valid = api.expected_n_valid(len(diag_sum), len(coverage))
+                    fh.writelines(expected_lines(iv, b, diag_sum, n_valid))
+
+
+def write_coverage(path, plan, base, marginals):
+    """<prefix>_coverage.bedgraph: the coverage of every bin of every entry of the plan that is not
+    skipped, in plan order, at the bin size `base`; `marginals` as for write_expected"""
+    with open(path, "w") as fh:
+        for k, entry in enumerate(plan):
+            if entry["skipped"]:
+                continue
+            got = marginals(k, 1, int(entry["interval"]["start"]) // int(base))
+            if got is not None:
+                fh.writelines(coverage_lines(entry["interval"], base, got[1]))
+
+
+def _interval_marginals(sim, plan, ids, sums, min_diag, cache, k, factor, first_bin):
+    """write_expected's and write_coverage's callback: summed on the device from the matrix where it
+    lies (with several ranks: the reduced tensor) and checked against the sum of the interval's
+    pixels.  `min_diag` holds at the base bin size, whose result both files share (the diagonal sums
+    do not depend on it); a coarse level keeps every diagonal."""
+    if ids[k] is None:
+        return None
+    if factor == 1 and k in cache:
+        return cache[k]
+    m = min_diag if factor == 1 else 0
+    diag_sum, coverage = sim.marginals(ids[k], m, factor, first_bin)
+    check_marginals(interval_name(plan[k]["interval"]), sums[k], diag_sum, coverage, m)
+    if factor == 1:
+        cache[k] = (diag_sum, coverage)
+    return diag_sum, coverage
 
 
 def reduce_to_rank0(t, backend, rank):
@@ -376,12 +467,13 @@ def reduce_missed(missed, backend, rank, device=None):
 
 
 def write_outputs(sim, cfg, plan, ids, tensors, outputs, bin_sizes=None, regions=(), rank=0, log=print,
-                  backend="nccl", **attrs):
+                  backend="nccl", coverage_min_diag=0, **attrs):
     """What a finished launch writes while the simulator is open: the state log (every rank its
-    own), then on rank 0 the cooler or .mcool with the missing-interactions warnings, and the dense
-    `regions` (of dense_regions).  `outputs.state_log`, `.cooler`, `.dense`: the paths, None for a file
-    that is not written; without a cooler (--skip-output) the matrices are only summed, for the
-    warnings.  `tensors`: with several ranks the (contacts, occupancy) torch tensors per plan entry;
+    own), then on rank 0 the cooler or .mcool with the missing-interactions warnings, the dense
+    `regions` (of dense_regions), the distance-decay curves (at every bin size of the file) and the
+    coverage without the diagonals below `coverage_min_diag`.  `outputs.state_log`, `.cooler`, `.dense`,
+    `.expected`, `.coverage`: the paths, None for a file that is not written; without a cooler
+    (--skip-output) the matrices are only summed, for the warnings.  `tensors`: with several ranks the (contacts, occupancy) torch tensors per plan entry;
     they are reduced in place onto rank 0 (reduce_to_rank0 with `backend`), which extracts from the
     reduced tensor without a host copy; the missed-update counts are summed over the ranks as well, so
     that the warnings weigh the whole job's missed updates against the whole job's matrix.
@@ -423,14 +515,23 @@ def write_outputs(sim, cfg, plan, ids, tensors, outputs, bin_sizes=None, regions
                 stats = pixels.extractor(sim.device).count(d_contacts, nrows, ncols)
                 warn_missing(plan[k]["interval"]["name"], stats.sum, missed[k], log)
         return occupancies
-    write_pixels(outputs.cooler, cfg, plan, functools.partial(_interval_pixels, sim, plan, ids, missed, log),
-                 bin_sizes, **attrs)
+    sums = {}  # the sum of the pixels per plan entry, at the base bin size
+    write_pixels(outputs.cooler, cfg, plan,
+                 functools.partial(_interval_pixels, sim, plan, ids, missed, log, sums=sums), bin_sizes, **attrs)
     log(f"written {outputs.cooler}")
     if outputs.dense is not None:
         # (the cooler's INT32 range check has passed: the uint32 words are int32 counts; with
         # several ranks the region is unpacked from the reduced tensor, like the pixels)
         np.savez(outputs.dense, **{key: sim.dense(ids[k], lo, hi).view(np.int32) for k, lo, hi, key in regions})
         log(f"written {outputs.dense}")
+    # (likewise after the range check, and with several ranks from the reduced tensor)
+    marginals = functools.partial(_interval_marginals, sim, plan, ids, sums, int(coverage_min_diag), {})
+    if outputs.expected is not None:
+        write_expected(outputs.expected, plan, int(cfg.bin_size), bin_sizes, marginals)
+        log(f"written {outputs.expected}")
+    if outputs.coverage is not None:
+        write_coverage(outputs.coverage, plan, int(cfg.bin_size), marginals)
+        log(f"written {outputs.coverage}")
     return occupancies
 
 

@@ -1,7 +1,7 @@
 """ctypes view of the sparse-pixel extraction, include/modle_pixels.h (modle_amd/libmodle_pixels.so,
 built by `make -C modle_amd/pixels`): the non-zero pixels of a band matrix that lies in device
-memory, in cooler order, found on the GPU; the band at a multiple of its bin size; and square regions
-of it as dense matrices.  There is no host fallback: without the library or
+memory, in cooler order, found on the GPU; the band at a multiple of its bin size; square regions
+of it as dense matrices; and its marginals, the sums per diagonal and per bin.  There is no host fallback: without the library or
 without a device the calls fail."""
 import ctypes as C
 import os
@@ -15,7 +15,8 @@ ERR_ARG, ERR_DEVICE, ERR_RANGE = -1, -2, -3
 EXPORTS = ["modle_pixels_create", "modle_pixels_destroy", "modle_pixels_count", "modle_pixels_extract",
            "modle_pixels_to_host", "modle_pixels_coarse_shape", "modle_pixels_coarsen",
            "modle_pixels_coarse_to_host", "modle_pixels_tiles_fit", "modle_pixels_dense_tiles",
-           "modle_pixels_dense_to_host"]  # every symbol include/modle_pixels.h declares
+           "modle_pixels_dense_to_host", "modle_pixels_marginals", "modle_pixels_marginals_to_host",
+           "modle_pixels_coarse_marginals_to_host"]  # every symbol include/modle_pixels.h declares
 
 _LIB = None
 _EXTRACTORS = {}
@@ -65,6 +66,10 @@ def lib():
         lb.modle_pixels_dense_tiles.argtypes = shape + [C.c_uint64] * 4 + [C.c_void_p, C.c_uint64, C.c_void_p] + err
         lb.modle_pixels_dense_to_host.argtypes = shape + [C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p),
                                                           C.c_void_p] + err
+        sums = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p] + err  # diag_sum, coverage, stream
+        lb.modle_pixels_marginals.argtypes = shape + [C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p] + err
+        lb.modle_pixels_marginals_to_host.argtypes = shape + [C.c_uint64] + sums
+        lb.modle_pixels_coarse_marginals_to_host.argtypes = shape + [C.c_uint64] * 3 + sums
         for name in EXPORTS:
             getattr(lb, name)  # raises AttributeError if a declared symbol is not exported
         _LIB = lb
@@ -81,7 +86,7 @@ def _stream_ptr(stream):
 def _host_array(ptr, n, dtype):
     if n == 0 or not ptr:
         return np.zeros(0, dtype=dtype)
-    ctype = C.c_int64 if dtype == np.int64 else C.c_int32
+    ctype = {np.int64: C.c_int64, np.int32: C.c_int32, np.uint64: C.c_uint64}[dtype]
     return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(n,)).copy()
 
 
@@ -213,6 +218,37 @@ class Extractor:
         n = int(hi) - int(lo)
         return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint32)), shape=(n, n)).copy()
 
+    def marginals_into(self, d_band, nrows, ncols, min_diag, d_diag_sum, d_coverage, stream=None):
+        """enqueues the sums per diagonal into the caller-owned device array `d_diag_sum`
+        (uint64[nrows]) and the coverage per bin, without the diagonals below `min_diag`, into
+        `d_coverage` (uint64[ncols]); either may be None; every word is written, at any 4-byte
+        aligned address (modle_pixels_marginals)"""
+        _call(self._L.modle_pixels_marginals, self._h, d_band, int(nrows), int(ncols), int(min_diag), d_diag_sum,
+              d_coverage, _stream_ptr(stream))
+
+    def _marginals(self, fn, shape_out, *args, stream=None):
+        """a to-host form `fn(handle, *args, two array pointers, stream, err)`: numpy copies"""
+        pd, pc = C.c_void_p(), C.c_void_p()
+        _call(fn, self._h, *args, C.byref(pd), C.byref(pc), _stream_ptr(stream))
+        nr, nc = shape_out()
+        return _host_array(pd.value, nr, np.uint64), _host_array(pc.value, nc, np.uint64)
+
+    def marginals(self, d_band, nrows, ncols, min_diag=0, stream=None):
+        """(diag_sum, coverage) as numpy uint64[nrows] and uint64[ncols] the caller owns, summed on
+        the device in one pass over the band (modle_pixels_marginals_to_host): diag_sum[d] is the sum
+        of diagonal d, coverage[i] the sum of row i of the symmetric matrix without the diagonals
+        below `min_diag`"""
+        return self._marginals(self._L.modle_pixels_marginals_to_host, lambda: (int(nrows), int(ncols)), d_band,
+                               int(nrows), int(ncols), int(min_diag), stream=stream)
+
+    def coarse_marginals(self, d_band, nrows, ncols, factor, first_bin, min_diag=0, stream=None):
+        """`marginals` of the band at `factor` times its bin size, coarsened on the device
+        (modle_pixels_coarse_marginals_to_host): uint64[nrows'] and uint64[ncols'] of coarse_shape;
+        `min_diag` counts coarse diagonals"""
+        return self._marginals(self._L.modle_pixels_coarse_marginals_to_host,
+                               lambda: coarse_shape(nrows, ncols, factor, first_bin), d_band, int(nrows),
+                               int(ncols), int(factor), int(first_bin), int(min_diag), stream=stream)
+
 
 def extractor(device=0):
     """the process-wide context of `device`"""
@@ -244,3 +280,22 @@ def dense(d_band, nrows, ncols, lo, hi, stream=None, device=0):
     """The symmetric matrix of the bins [lo, hi) of the band at device pointer `d_band`: numpy
     uint32[hi - lo, hi - lo], unpacked on the device."""
     return extractor(device).dense(d_band, nrows, ncols, lo, hi, stream)
+
+
+def marginals_into(d_band, nrows, ncols, min_diag, d_diag_sum, d_coverage, stream=None, device=0):
+    """The sums per diagonal and the coverage per bin of the band at device pointer `d_band`, into
+    the device arrays `d_diag_sum` (uint64[nrows]) and `d_coverage` (uint64[ncols]; either may be
+    None); enqueued on `stream`, nothing crosses to the host."""
+    extractor(device).marginals_into(d_band, nrows, ncols, min_diag, d_diag_sum, d_coverage, stream)
+
+
+def marginals(d_band, nrows, ncols, min_diag=0, stream=None, device=0):
+    """(diag_sum, coverage) of the band at device pointer `d_band`: numpy uint64[nrows] and
+    uint64[ncols], summed on the device."""
+    return extractor(device).marginals(d_band, nrows, ncols, min_diag, stream)
+
+
+def coarse_marginals(d_band, nrows, ncols, factor, first_bin, min_diag=0, stream=None, device=0):
+    """(diag_sum, coverage) of the band at device pointer `d_band` at `factor` times its bin size,
+    coarsened and summed on the device."""
+    return extractor(device).coarse_marginals(d_band, nrows, ncols, factor, first_bin, min_diag, stream)

@@ -76,6 +76,8 @@ struct modle_pixels_handle {
   GrowBuf<int32_t, true> count;
   GrowBuf<uint32_t> coarse;       // modle_pixels_coarse_to_host: the coarse band (modle_coarsen.hip)
   GrowBuf<uint32_t, true> dense;  // modle_pixels_dense_to_host: the region (modle_dense.hip)
+  // modle_pixels_marginals*: diag_sum (nrows words), then coverage (ncols words) (modle_marginals.hip)
+  GrowBuf<uint64_t, true> marginals;
 };
 
 #endif
