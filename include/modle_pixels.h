@@ -1,5 +1,6 @@
 /* modle_pixels.h -- C ABI of the sparse-pixel extraction (modle_amd/libmodle_pixels.so), of the
- * coarsening of a band, of its dense regions and of its marginals (further down).
+ * coarsening of a band, of its dense regions, of its marginals and of its insulation sums (further
+ * down).
  *
  * The simulation leaves every interval as a dense band matrix in device memory
  * (modle_hip_interval_outputs).  A cooler file is made of the non-zero pixels only, sorted by
@@ -196,6 +197,60 @@ int modle_pixels_coarse_marginals_to_host(modle_pixels_handle* h, const uint32_t
                                           uint64_t first_bin, uint64_t min_diag,
                                           const uint64_t** diag_sum, const uint64_t** coverage,
                                           void* stream, char* err, size_t errlen);
+
+/* ---- Insulation: the sums over a sliding diamond window --------------------------------------
+ *
+ * For a window of `w` bins the diamond of bin b is the set of pixels (a, c) with
+ *     b - w + 1 <= a <= b <= c <= b + w - 1,   a >= 0,   c < ncols,   c - a >= min_diag
+ * (cooltools' insul_diamond convention: bin b lies on both sides of its own diamond), and
+ *     ins_sum[k][b] = sum of band[c * nrows + (c - a)] over the diamond of b for windows[k]
+ *     n_valid[b]    = the number of pixels of that diamond
+ *                   = na * nc - #{(p, q): p < na, q < nc, p + q < min_diag},
+ *                     na = min(w, b + 1), nc = min(w, ncols - b).
+ * Their quotient is the mean the insulation score is the log-ratio of; its minima are the domain
+ * boundaries.  The sums are exact 64-bit integers (at most w^2 <= 2^20 words below 2^32: no sum can
+ * overflow); the words of the band that are no pixels are never read.  EVERY output word is written
+ * exactly once, with a plain store: the caller does not pre-zero.  min_diag >= 2 * w - 1 gives zeros
+ * for that window.
+ *
+ * A window is accepted only when its whole diamond lies in the band: 1 <= w <= MODLE_PIXELS_MAX_WINDOW
+ * and 2 * w - 1 <= nrows; a call takes 1 .. MODLE_PIXELS_MAX_WINDOWS windows, in any order, from the
+ * HOST array `windows`.  MODLE_PIXELS_ERR_ARG, with nothing written: a window or a number of windows
+ * that is not accepted, a null pointer, nrows == 0, nrows > ncols, out_words < n_windows * ncols, a
+ * d_out that is not 8-byte aligned or overlaps the band. */
+#define MODLE_PIXELS_MAX_WINDOW 1024
+#define MODLE_PIXELS_MAX_WINDOWS 8
+
+/* n_valid[b] for every bin b < ncols.  Host only: no device is needed.  window == 0 or above
+ * MODLE_PIXELS_MAX_WINDOW and a null pointer are MODLE_PIXELS_ERR_ARG. */
+int modle_pixels_insulation_n_valid(uint64_t ncols, uint64_t window, uint64_t min_diag,
+                                    uint64_t* n_valid /* [ncols] */);
+
+/* Enqueues the sums into the device array d_out (uint64[n_windows][ncols], of `out_words` >=
+ * n_windows * ncols words) on `stream`; the call does not wait. */
+int modle_pixels_insulation(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                            uint64_t ncols, const uint64_t* windows, uint64_t n_windows,
+                            uint64_t min_diag, uint64_t* d_out, uint64_t out_words, void* stream,
+                            char* err, size_t errlen);
+
+/* The same into a pinned host buffer of the context (grown on demand, freed by modle_pixels_destroy):
+ * *ins_sum (uint64[n_windows][ncols]) stays valid until the next call on the context.  Waits for
+ * `stream`. */
+int modle_pixels_insulation_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                                    uint64_t ncols, const uint64_t* windows, uint64_t n_windows,
+                                    uint64_t min_diag, const uint64_t** ins_sum, void* stream,
+                                    char* err, size_t errlen);
+
+/* One call at `factor` times the bin size: coarsens into the scratch band of the context (like
+ * modle_pixels_coarse_marginals_to_host), then modle_pixels_insulation_to_host on it.  *ins_sum is
+ * uint64[n_windows][ncols'] (modle_pixels_coarse_shape); the windows and `min_diag` count coarse bins
+ * and the rule for the windows holds against nrows'. */
+int modle_pixels_coarse_insulation_to_host(modle_pixels_handle* h, const uint32_t* d_band,
+                                           uint64_t nrows, uint64_t ncols, uint64_t factor,
+                                           uint64_t first_bin, const uint64_t* windows,
+                                           uint64_t n_windows, uint64_t min_diag,
+                                           const uint64_t** ins_sum, void* stream, char* err,
+                                           size_t errlen);
 
 #ifdef __cplusplus
 }

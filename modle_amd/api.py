@@ -138,6 +138,33 @@ def expected_n_valid(nrows, ncols):
     return np.uint64(ncols) - np.arange(nrows, dtype=np.uint64)
 
 
+def insulation_score(ins_sum, n_valid):
+    """The log2 insulation score of integer insulation sums (Simulator.insulation), numpy float64 of
+    their shape: mean = ins_sum / n_valid, and score = log2(mean / median(mean)) with the median taken,
+    per window (last axis), over the bins with n_valid > 0.  nan where n_valid == 0, where ins_sum == 0
+    and, everywhere, where the median is 0 (or no bin is valid)."""
+    s, n = np.asarray(ins_sum, dtype=np.uint64), np.asarray(n_valid, dtype=np.uint64)
+    if s.shape != n.shape or s.ndim == 0:
+        raise ValueError(f"insulation_score: shapes {s.shape} and {n.shape} differ or have no bins")
+    if s.size == 0:
+        return np.zeros(s.shape, dtype=np.float64)
+    s2, n2 = s.reshape(-1, s.shape[-1]), n.reshape(-1, n.shape[-1])
+    out = np.full(s2.shape, np.nan, dtype=np.float64)
+    for k in range(s2.shape[0]):
+        valid = n2[k] > 0
+        if not valid.any():
+            continue
+        mean = s2[k][valid].astype(np.float64) / n2[k][valid].astype(np.float64)
+        med = float(np.median(mean))
+        if med == 0.0:
+            continue
+        keep = mean > 0
+        row = np.full(mean.shape, np.nan, dtype=np.float64)
+        row[keep] = np.log2(mean[keep] / med)
+        out[k][valid] = row
+    return out.reshape(s.shape)
+
+
 # ---------------------------------------------------------------------------------------------
 # device path
 # ---------------------------------------------------------------------------------------------
@@ -369,6 +396,40 @@ class Simulator:
         pixels.marginals_into(d_band, nrows, ncols, min_diag, diag_sum.data_ptr(), coverage.data_ptr(), stream,
                               device=self.device)
         return diag_sum, coverage
+
+    def insulation(self, interval_id, windows, min_diag=2, factor=1, first_bin=0, stream=None):
+        """The insulation sums of the interval: (ins_sum, n_valid), numpy uint64 [len(windows), ncols].
+        ins_sum[k][b] is the sum of the contacts that cross bin b inside the diamond of windows[k] bins
+        (pixels (a, c), b - w < a <= b <= c < b + w, without the diagonals below `min_diag`), formed on
+        the device from the band where it lies (pixels.insulation); n_valid the number of pixels of that
+        diamond.  insulation_score() turns the two into the log2 score.  Call it after wait().  With
+        `factor` > 1 the band is first coarsened on the device (`first_bin` as for pixels()) and the
+        windows and `min_diag` count coarse bins."""
+        from . import pixels
+
+        d_band, _, nrows, ncols = self.outputs(interval_id)
+        if int(factor) == 1:
+            ins_sum = pixels.insulation(d_band, nrows, ncols, windows, min_diag, stream, device=self.device)
+        else:
+            ins_sum = pixels.coarse_insulation(d_band, nrows, ncols, factor, first_bin, windows, min_diag, stream,
+                                               device=self.device)
+        n_valid = np.stack([pixels.insulation_n_valid(ins_sum.shape[1], w, min_diag) for w in windows])
+        return ins_sum, n_valid
+
+    def insulation_tensor(self, interval_id, windows, min_diag=2, stream=None):
+        """The insulation sums of the interval as one torch int64 tensor [len(windows), ncols] on the
+        simulator's device, filled there by the kernel: nothing crosses to the host.  The words hold
+        the uint64 sums bit for bit (they are below 2^52).  The kernel is enqueued on `stream` (None:
+        the default stream, on which torch orders its own work) and not waited for."""
+        import torch
+
+        from . import pixels
+
+        d_band, _, nrows, ncols = self.outputs(interval_id)
+        out = torch.empty((len(windows), ncols), dtype=torch.int64, device=torch.device("cuda", self.device))
+        pixels.insulation_into(d_band, nrows, ncols, windows, min_diag, out.data_ptr(), out.numel(), stream,
+                               device=self.device)
+        return out
 
     def simulate_interval(self, start, end, bar_pos, bar_dir, stp_active, stp_inactive, tasks):
         """One-call seam (modle_hip_simulate_interval): returns contacts, missed, occupancy,

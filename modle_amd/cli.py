@@ -10,7 +10,8 @@ contacts at several bin sizes, coarsened on the GPU) and, with the 1-D LEF posit
 `<prefix>_lef_1d_occupancy.bw` (cli.cpp:867-882); with --dense-region also `<prefix>_dense.npz`, the
 square matrices of the named regions, unpacked on the GPU; with --expected `<prefix>_expected.tsv`, the
 contacts per diagonal, and with --coverage `<prefix>_coverage.bedgraph`, the contacts per bin, both
-summed on the GPU.  Everything heavy is native: parsing and
+summed on the GPU; with --insulation-windows `<prefix>_insulation.tsv`, the insulation sums and scores
+per bin over sliding diamond windows, summed on the GPU.  Everything heavy is native: parsing and
 task generation in libmodle_hip.so (host), the simulation on the MI355X (one process per GPU;
 under torch.distributed.run the cells are sharded over the ranks and the matrices are summed
 with RCCL, or with --dist-backend gloo on host copies), the writers in libmodle_cooler.so.  `-t/--threads` is accepted and ignored."""
@@ -86,6 +87,19 @@ def resolution_list(text):
     return [genomic_distance(t) for t in items]
 
 
+MAX_INSULATION_WINDOWS, MAX_INSULATION_WINDOW_BINS = 8, 1024  # include/modle_pixels.h
+
+
+def window_list(text):
+    """`100kb,250kb`: comma-separated genomic distances (--insulation-windows), at most 8 of them"""
+    items = [t.strip() for t in text.split(",")]
+    if not text.strip() or any(not t for t in items):
+        raise argparse.ArgumentTypeError(f"{text!r} is not a comma-separated list of window sizes")
+    if len(items) > MAX_INSULATION_WINDOWS:
+        raise argparse.ArgumentTypeError(f"{text!r} lists {len(items)} windows: at most {MAX_INSULATION_WINDOWS}")
+    return [genomic_distance(t) for t in items]
+
+
 def mcool_bin_sizes(resolutions, base):
     """the bin sizes of the .mcool: the base (-r) and the listed resolutions, sorted, without
     duplicates.  Every listed one must be a multiple of the base and larger than it."""
@@ -125,6 +139,10 @@ def coverage_path(prefix):
     return prefix + "_coverage.bedgraph"
 
 
+def insulation_path(prefix):
+    return prefix + "_insulation.tsv"
+
+
 def build_parser():
     ap = argparse.ArgumentParser(prog="modle_amd", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -157,6 +175,17 @@ def build_parser():
                          "matrix at -r, summed on the GPU")
     io.add_argument("--coverage-ignore-diags", type=int, default=None, metavar="N",
                     help="with --coverage: leave out the first N diagonals (default 0)")
+    io.add_argument("--insulation-windows", type=window_list, default=None, metavar="LIST",
+                    help="also write <prefix>_insulation.tsv: for every bin and every window size of the "
+                         "comma-separated LIST (e.g. 100kb,250kb; at most 8, multiples of the insulation "
+                         "resolution, at most 1024 bins, and the diamond of 2 w - 1 diagonals must fit -w) the "
+                         "sum of the contacts that cross the bin inside the sliding diamond window, the number "
+                         "of pixels of the diamond and the log2 insulation score, summed on the GPU")
+    io.add_argument("--insulation-resolution", type=genomic_distance, default=None, metavar="R",
+                    help="with --insulation-windows: the bin size of the insulation track (a multiple of -r, "
+                         "coarsened on the GPU; default -r)")
+    io.add_argument("--insulation-ignore-diags", type=int, default=None, metavar="N",
+                    help="with --insulation-windows: leave out the first N diagonals (default 2)")
     io.add_argument("--log-model-internal-state", action="store_true",
                     help="write <prefix>_internal_state.log.gz: one line of statistics per task and "
                          "epoch (uses the diagnostic build libmodle_hip_statelog.so)")
@@ -280,26 +309,60 @@ def state_log_path(prefix):
 # what preflight settles; a path is None for a file the run does not write, `state_log` is this rank's
 # (`expected` and `coverage` came later: at the end, and None unless asked for)
 Outputs = collections.namedtuple("Outputs", "cooler bigwig dense state_log expected coverage", defaults=(None, None))
-Preflight = collections.namedtuple("Preflight", "bin_sizes outputs rank world device")
+# what --insulation-windows asks for: the file (None with --skip-output), the bin size of the track, the
+# windows in base pairs as given and the diagonals left out
+Insulation = collections.namedtuple("Insulation", "path resolution windows min_diag")
+# (`insulation` came later: at the end, and None unless asked for)
+Preflight = collections.namedtuple("Preflight", "bin_sizes outputs rank world device insulation", defaults=(None,))
+
+
+def insulation_options(a, cfg):
+    """The insulation track the arguments ask for, as an Insulation without a path, or None.
+    SystemExit: --insulation-resolution or --insulation-ignore-diags without --insulation-windows, a
+    negative number of diagonals, a resolution that is no multiple of -r, a window that is no positive
+    multiple of the insulation resolution or has more than 1024 bins."""
+    if a.insulation_windows is None:
+        for name, v in (("--insulation-resolution", a.insulation_resolution),
+                        ("--insulation-ignore-diags", a.insulation_ignore_diags)):
+            if v is not None:
+                raise SystemExit(f"{name} needs --insulation-windows")
+        return None
+    min_diag = 2 if a.insulation_ignore_diags is None else a.insulation_ignore_diags
+    if min_diag < 0:
+        raise SystemExit(f"--insulation-ignore-diags: {min_diag} is negative")
+    base = int(cfg.bin_size)
+    res = base if a.insulation_resolution is None else int(a.insulation_resolution)
+    if res < base or res % base != 0:
+        raise SystemExit(f"--insulation-resolution: {res} is not a multiple of the resolution ({base})")
+    for w in a.insulation_windows:
+        if w <= 0 or w % res != 0:
+            raise SystemExit(f"--insulation-windows: {w} is not a positive multiple of the insulation "
+                             f"resolution ({res})")
+        if w // res > MAX_INSULATION_WINDOW_BINS:
+            raise SystemExit(f"--insulation-windows: {w} is {w // res} bins of {res}: at most "
+                             f"{MAX_INSULATION_WINDOW_BINS}")
+    return Insulation(None, res, list(a.insulation_windows), min_diag)
 
 
 def preflight(a, cfg):
     """What the arguments alone settle and refuse, without a genome or a GPU.  SystemExit: a bad
-    --mcool-resolutions list; --coverage-ignore-diags without --coverage, or negative; on rank 0, an
-    output that exists without --force (cooler or .mcool, then bigwig, then .npz, then the expected
-    and the coverage file).  With --skip-output no file is planned and none is looked at."""
+    --mcool-resolutions list; --coverage-ignore-diags without --coverage, or negative; what
+    insulation_options refuses; on rank 0, an output that exists without --force (cooler or .mcool,
+    then bigwig, then .npz, then the expected, the coverage and the insulation file).  With
+    --skip-output no file is planned and none is looked at."""
     if a.coverage_ignore_diags is not None:
         if not a.coverage:
             raise SystemExit("--coverage-ignore-diags needs --coverage")
         if a.coverage_ignore_diags < 0:
             raise SystemExit(f"--coverage-ignore-diags: {a.coverage_ignore_diags} is negative")
+    ins = insulation_options(a, cfg)
     # (a bad list ends the run here, before anything is imported or simulated)
     bin_sizes = None if a.mcool_resolutions is None else mcool_bin_sizes(a.mcool_resolutions, cfg.bin_size)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     device = a.device if a.device is not None else int(os.environ.get("LOCAL_RANK", "0"))
     if a.skip_output:
-        return Preflight(bin_sizes, Outputs(None, None, None, None), rank, world, device)
+        return Preflight(bin_sizes, Outputs(None, None, None, None), rank, world, device, ins)
     cool_path, bw_path = output_paths(a.output_prefix, mcool=bin_sizes is not None)
     log_path = state_log_path(a.output_prefix) if world == 1 else \
         f"{a.output_prefix}_internal_state.rank{rank}.log.gz"
@@ -308,12 +371,15 @@ def preflight(a, cfg):
                       log_path if a.log_model_internal_state else None,
                       expected_path(a.output_prefix) if a.expected else None,
                       coverage_path(a.output_prefix) if a.coverage else None)
+    if ins is not None:
+        ins = ins._replace(path=insulation_path(a.output_prefix))
     if rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(cool_path)), exist_ok=True)
-        for p in (outputs.cooler, outputs.bigwig, outputs.dense, outputs.expected, outputs.coverage):
+        for p in (outputs.cooler, outputs.bigwig, outputs.dense, outputs.expected, outputs.coverage,
+                  None if ins is None else ins.path):
             if p and os.path.exists(p) and not a.force:
                 raise SystemExit(f"refusing to overwrite {p}: pass --force to overwrite")
-    return Preflight(bin_sizes, outputs, rank, world, device)
+    return Preflight(bin_sizes, outputs, rank, world, device, ins)
 
 
 def plan_run(a, cfg, pre, log):
@@ -329,6 +395,12 @@ def plan_run(a, cfg, pre, log):
         if hit is not None:
             raise SystemExit(f"--mcool-resolutions: the intervals {hit[1]} and {hit[2]} share a bin at "
                              f"resolution {hit[0]}: its pixels would not be sorted and unique")
+    if pre.insulation is not None and pre.insulation.path is not None:
+        bad = driver.insulation_misfit(plan, int(cfg.bin_size), pre.insulation.resolution, pre.insulation.windows)
+        if bad is not None:
+            raise SystemExit(f"--insulation-windows: the diamond of {bad[1]} ({bad[2]} bins of "
+                             f"{pre.insulation.resolution}) does not fit the band of {bad[0]} ({bad[3]} diagonals): "
+                             f"the largest window that fits is {bad[4]} ({bad[4] // pre.insulation.resolution} bins)")
     regions = driver.dense_regions(plan, int(cfg.bin_size), chroms, a.dense_region) if a.dense_region else []
     return chroms, plan, regions
 
@@ -392,7 +464,7 @@ def simulate(a, log=print):
                           sort_keys=True)
         occupancies = driver.write_outputs(
             sim, cfg, plan, ids, tensors, pre.outputs, pre.bin_sizes, regions, pre.rank, log, a.dist_backend,
-            coverage_min_diag=a.coverage_ignore_diags or 0, assembly=a.assembly_name,
+            coverage_min_diag=a.coverage_ignore_diags or 0, insulation=pre.insulation, assembly=a.assembly_name,
             generated_by="modle_amd (MI355X)", metadata_json=meta,
             force_overwrite=a.force, chroms=chroms)
     finally:

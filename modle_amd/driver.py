@@ -437,6 +437,104 @@ def _interval_marginals(sim, plan, ids, sums, min_diag, cache, k, factor, first_
     return diag_sum, coverage
 
 
+def insulation_shape(nrows, ncols, first_bin, factor):
+    """(nrows', ncols') of a band of plan shape at `factor` times the bin size, the interval starting at
+    fine bin `first_bin` of its chromosome (modle_pixels_coarse_shape; factor 1: the band itself)"""
+    if int(factor) == 1:
+        return int(nrows), int(ncols)
+    lo, hi = coarse_bin_range(int(first_bin), int(ncols), int(factor))
+    nc = hi - lo + 1
+    return min(nc, (int(nrows) - 1 + int(factor) - 1) // int(factor) + 1), nc
+
+
+def insulation_misfit(plan, base, resolution, windows):
+    """The first (name of the interval, window in bp, its bins, diagonals of the band, largest window
+    in bp that fits) of an entry of the plan that has a matrix and a window of `windows` (bp, multiples
+    of `resolution`) whose diamond leaves the band at `resolution`, 2 * w - 1 > nrows' -- or None."""
+    base, res = int(base), int(resolution)
+    for entry in plan:
+        iv = entry["interval"]
+        if entry["skipped"] or entry["ncols"] == 0:
+            continue
+        nr, _ = insulation_shape(entry["nrows"], entry["ncols"], int(iv["start"]) // base, res // base)
+        for w in windows:
+            if 2 * (int(w) // res) - 1 > nr:
+                return interval_name(iv), int(w), int(w) // res, nr, (nr + 1) // 2 * res
+    return None
+
+
+def check_insulation(name, windows, min_diag, ins_sum, diag_sum):
+    """What ties the insulation sums of a band (api.Simulator.insulation) to its diagonal sums
+    (api.Simulator.marginals, at the same bin size), in exact integers: a pixel (a, c) of diagonal
+    d = c - a lies in the diamonds of the bins a .. c that are within w of both, min(d + 1, 2 w - 1 - d)
+    of them whatever the interval's edges, so for every window
+        sum over b of ins_sum[b] = sum over d = min_diag .. 2 w - 2 of min(d + 1, 2 w - 1 - d) * diag_sum[d].
+    RuntimeError, naming the interval and the window (in bins), when it does not hold."""
+    diag = [int(x) for x in diag_sum]
+    for w, row in zip(windows, ins_sum):
+        w = int(w)
+        if 2 * w - 1 > len(diag):
+            raise RuntimeError(f"{name}: the diamond of the window of {w} bins leaves the {len(diag)} diagonals")
+        want = sum(min(d + 1, 2 * w - 1 - d) * diag[d] for d in range(int(min_diag), 2 * w - 1))
+        got = sum(int(x) for x in row)
+        if got != want:
+            raise RuntimeError(f"{name}: the insulation sums of the window of {w} bins add up to {got}, "
+                               f"the diagonals from {int(min_diag)} on give {want}")
+
+
+def insulation_header(windows):
+    """the header line of <prefix>_insulation.tsv for the `windows` in base pairs"""
+    return "chrom\tstart\tend" + "".join(f"\tsum_{w}\tn_valid_{w}\tlog2_insulation_score_{w}"
+                                         for w in map(int, windows)) + "\n"
+
+
+def insulation_lines(iv, base, factor, ins_sum, n_valid, score):
+    """the rows of <prefix>_insulation.tsv for one interval, one per bin of `factor` * `base` base pairs:
+    chrom, start, end, then per window (the rows of the three arrays) the sum, the number of pixels and
+    the repr of the score.  Fine bins count from the interval's start and coarse bins are anchored at the
+    chromosome's, so the first and the last bin are clipped to the interval."""
+    start, end, base, k = int(iv["start"]), int(iv["end"]), int(base), int(factor)
+    p = (start // base) % k
+    out = []
+    for c in range(len(ins_sum[0]) if len(ins_sum) else 0):
+        lo, hi = start + max(0, c * k - p) * base, min(end, start + ((c + 1) * k - p) * base)
+        out.append(f"{iv['name']}\t{lo}\t{hi}" + "".join(
+            f"\t{int(s[c])}\t{int(n[c])}\t{float(x[c])!r}" for s, n, x in zip(ins_sum, n_valid, score)) + "\n")
+    return out
+
+
+def write_insulation(path, plan, base, resolution, windows, insulation):
+    """<prefix>_insulation.tsv: a header, then the insulation of every bin of every entry of the plan
+    that is not skipped, in plan order, at the bin size `resolution` (a multiple of `base`) for the
+    `windows` in base pairs.  `insulation(k, factor, first_bin)` returns (ins_sum, n_valid) of plan
+    entry k -- what api.Simulator.insulation returns -- or None for an entry without a matrix."""
+    factor = int(resolution) // int(base)
+    with open(path, "w") as fh:
+        fh.write(insulation_header(windows))
+        for k, entry in enumerate(plan):
+            if entry["skipped"]:
+                continue
+            iv = entry["interval"]
+            got = insulation(k, factor, int(iv["start"]) // int(base))
+            if got is not None:
+                ins_sum, n_valid = got
+                fh.writelines(insulation_lines(iv, base, factor, ins_sum, n_valid,
+                                               api.insulation_score(ins_sum, n_valid)))
+
+
+def _interval_insulation(sim, plan, ids, windows, min_diag, marginals, k, factor, first_bin):
+    """write_insulation's callback: summed on the device from the matrix where it lies (with several
+    ranks: the reduced tensor) for the `windows` in bins, and checked against the diagonal sums of the
+    marginals pass at the same bin size (`marginals`: _interval_marginals, whose base result the
+    expected and the coverage file share)"""
+    if ids[k] is None:
+        return None
+    ins_sum, n_valid = sim.insulation(ids[k], windows, min_diag, factor, first_bin)
+    check_insulation(interval_name(plan[k]["interval"]), windows, min_diag, ins_sum,
+                     marginals(k, factor, first_bin)[0])
+    return ins_sum, n_valid
+
+
 def reduce_to_rank0(t, backend, rank):
     """Sum of the ranks' tensors `t` into rank 0's, in place (the other ranks' tensors are unspecified
     afterwards).  `nccl` (= RCCL): on the device tensors.  `gloo`: on host copies -- the rehearsal with
@@ -467,11 +565,13 @@ def reduce_missed(missed, backend, rank, device=None):
 
 
 def write_outputs(sim, cfg, plan, ids, tensors, outputs, bin_sizes=None, regions=(), rank=0, log=print,
-                  backend="nccl", coverage_min_diag=0, **attrs):
+                  backend="nccl", coverage_min_diag=0, insulation=None, **attrs):
     """What a finished launch writes while the simulator is open: the state log (every rank its
     own), then on rank 0 the cooler or .mcool with the missing-interactions warnings, the dense
     `regions` (of dense_regions), the distance-decay curves (at every bin size of the file) and the
-    coverage without the diagonals below `coverage_min_diag`.  `outputs.state_log`, `.cooler`, `.dense`,
+    coverage without the diagonals below `coverage_min_diag`, and the insulation track `insulation` (a
+    cli.Insulation: path, resolution, windows in base pairs, min_diag; None or without a path: not
+    written).  `outputs.state_log`, `.cooler`, `.dense`,
     `.expected`, `.coverage`: the paths, None for a file that is not written; without a cooler
     (--skip-output) the matrices are only summed, for the warnings.  `tensors`: with several ranks the (contacts, occupancy) torch tensors per plan entry;
     they are reduced in place onto rank 0 (reduce_to_rank0 with `backend`), which extracts from the
@@ -532,6 +632,12 @@ def write_outputs(sim, cfg, plan, ids, tensors, outputs, bin_sizes=None, regions
     if outputs.coverage is not None:
         write_coverage(outputs.coverage, plan, int(cfg.bin_size), marginals)
         log(f"written {outputs.coverage}")
+    if insulation is not None and insulation.path is not None:
+        bins = [int(w) // int(insulation.resolution) for w in insulation.windows]
+        write_insulation(insulation.path, plan, int(cfg.bin_size), insulation.resolution, insulation.windows,
+                         functools.partial(_interval_insulation, sim, plan, ids, bins, int(insulation.min_diag),
+                                           marginals))
+        log(f"written {insulation.path}")
     return occupancies
 
 

@@ -1,7 +1,8 @@
 """ctypes view of the sparse-pixel extraction, include/modle_pixels.h (modle_amd/libmodle_pixels.so,
 built by `make -C modle_amd/pixels`): the non-zero pixels of a band matrix that lies in device
 memory, in cooler order, found on the GPU; the band at a multiple of its bin size; square regions
-of it as dense matrices; and its marginals, the sums per diagonal and per bin.  There is no host fallback: without the library or
+of it as dense matrices; its marginals, the sums per diagonal and per bin; and its insulation sums
+over sliding diamond windows.  There is no host fallback: without the library or
 without a device the calls fail."""
 import ctypes as C
 import os
@@ -12,11 +13,13 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "libmodle_pixels.so")
 ERR_ARG, ERR_DEVICE, ERR_RANGE = -1, -2, -3
+MAX_WINDOW, MAX_WINDOWS = 1024, 8  # MODLE_PIXELS_MAX_WINDOW, MODLE_PIXELS_MAX_WINDOWS
 EXPORTS = ["modle_pixels_create", "modle_pixels_destroy", "modle_pixels_count", "modle_pixels_extract",
            "modle_pixels_to_host", "modle_pixels_coarse_shape", "modle_pixels_coarsen",
            "modle_pixels_coarse_to_host", "modle_pixels_tiles_fit", "modle_pixels_dense_tiles",
            "modle_pixels_dense_to_host", "modle_pixels_marginals", "modle_pixels_marginals_to_host",
-           "modle_pixels_coarse_marginals_to_host"]  # every symbol include/modle_pixels.h declares
+           "modle_pixels_coarse_marginals_to_host", "modle_pixels_insulation_n_valid", "modle_pixels_insulation",
+           "modle_pixels_insulation_to_host", "modle_pixels_coarse_insulation_to_host"]  # every symbol include/modle_pixels.h declares
 
 _LIB = None
 _EXTRACTORS = {}
@@ -70,6 +73,12 @@ def lib():
         lb.modle_pixels_marginals.argtypes = shape + [C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p] + err
         lb.modle_pixels_marginals_to_host.argtypes = shape + [C.c_uint64] + sums
         lb.modle_pixels_coarse_marginals_to_host.argtypes = shape + [C.c_uint64] * 3 + sums
+        wins = [u64p, C.c_uint64, C.c_uint64]  # windows (a host array), n_windows, min_diag
+        lb.modle_pixels_insulation_n_valid.argtypes = [C.c_uint64] * 3 + [u64p]
+        lb.modle_pixels_insulation.argtypes = shape + wins + [C.c_void_p, C.c_uint64, C.c_void_p] + err
+        lb.modle_pixels_insulation_to_host.argtypes = shape + wins + [C.POINTER(C.c_void_p), C.c_void_p] + err
+        lb.modle_pixels_coarse_insulation_to_host.argtypes = shape + [C.c_uint64] * 2 + wins + \
+            [C.POINTER(C.c_void_p), C.c_void_p] + err
         for name in EXPORTS:
             getattr(lb, name)  # raises AttributeError if a declared symbol is not exported
         _LIB = lb
@@ -119,6 +128,28 @@ def tiles_fit(ncols, first, size, step):
     if rc != 0:
         raise PixelsError(rc, "tiles_fit: invalid argument (size > 0, step > 0, first + size <= ncols)")
     return n.value
+
+
+def _windows(windows):
+    """(a ctypes uint64 array or None, its length) of a sequence of window sizes in bins; a negative
+    size is refused here, everything else by the library"""
+    ws = [int(w) for w in windows]
+    if any(w < 0 for w in ws):
+        raise PixelsError(ERR_ARG, "insulation: negative window")
+    return ((C.c_uint64 * len(ws))(*ws) if ws else None), len(ws)
+
+
+def insulation_n_valid(ncols, window, min_diag=2):
+    """the number of pixels of every bin's diamond of `window` bins without the diagonals below
+    `min_diag`, numpy uint64[ncols] (modle_pixels_insulation_n_valid; no device is needed)"""
+    if min(int(ncols), int(window), int(min_diag)) < 0:
+        raise PixelsError(ERR_ARG, "insulation_n_valid: negative argument")
+    out = np.zeros(int(ncols), dtype=np.uint64)
+    rc = lib().modle_pixels_insulation_n_valid(int(ncols), int(window), int(min_diag),
+                                               out.ctypes.data_as(C.POINTER(C.c_uint64)))
+    if rc != 0:
+        raise PixelsError(rc, "insulation_n_valid: invalid argument (1 <= window <= 1024)")
+    return out
 
 
 class Extractor:
@@ -249,6 +280,38 @@ class Extractor:
                                lambda: coarse_shape(nrows, ncols, factor, first_bin), d_band, int(nrows),
                                int(ncols), int(factor), int(first_bin), int(min_diag), stream=stream)
 
+    def insulation_into(self, d_band, nrows, ncols, windows, min_diag, d_out, out_words, stream=None):
+        """enqueues the insulation sums of the `windows` (1 to 8 sizes in bins, 2 * w - 1 <= nrows,
+        w <= 1024), without the diagonals below `min_diag`, into the caller-owned device array `d_out`
+        (uint64[len(windows)][ncols], 8-byte aligned, `out_words` >= len(windows) * ncols); every word is
+        written (modle_pixels_insulation)"""
+        ws, n = _windows(windows)
+        _call(self._L.modle_pixels_insulation, self._h, d_band, int(nrows), int(ncols), ws, n, int(min_diag), d_out,
+              int(out_words), _stream_ptr(stream))
+
+    def _insulation(self, fn, ncols_out, windows, min_diag, *args, stream=None):
+        """a to-host form `fn(handle, *args, windows, n, min_diag, one array pointer, stream, err)`: a
+        numpy copy"""
+        ws, n = _windows(windows)
+        ptr = C.c_void_p()
+        _call(fn, self._h, *args, ws, n, int(min_diag), C.byref(ptr), _stream_ptr(stream))
+        return _host_array(ptr.value, n * ncols_out(), np.uint64).reshape(n, -1)
+
+    def insulation(self, d_band, nrows, ncols, windows, min_diag=2, stream=None):
+        """the insulation sums as a numpy uint64[len(windows), ncols] the caller owns: for every window
+        w and bin b the sum of the pixels (a, c), b - w < a <= b <= c < b + w, c - a >= min_diag, formed
+        on the device (modle_pixels_insulation_to_host)"""
+        return self._insulation(self._L.modle_pixels_insulation_to_host, lambda: int(ncols), windows, min_diag,
+                                d_band, int(nrows), int(ncols), stream=stream)
+
+    def coarse_insulation(self, d_band, nrows, ncols, factor, first_bin, windows, min_diag=2, stream=None):
+        """`insulation` of the band at `factor` times its bin size, coarsened on the device
+        (modle_pixels_coarse_insulation_to_host): uint64[len(windows), ncols'] of coarse_shape; the
+        windows and `min_diag` count coarse bins"""
+        return self._insulation(self._L.modle_pixels_coarse_insulation_to_host,
+                                lambda: coarse_shape(nrows, ncols, factor, first_bin)[1], windows, min_diag,
+                                d_band, int(nrows), int(ncols), int(factor), int(first_bin), stream=stream)
+
 
 def extractor(device=0):
     """the process-wide context of `device`"""
@@ -299,3 +362,22 @@ def coarse_marginals(d_band, nrows, ncols, factor, first_bin, min_diag=0, stream
     """(diag_sum, coverage) of the band at device pointer `d_band` at `factor` times its bin size,
     coarsened and summed on the device."""
     return extractor(device).coarse_marginals(d_band, nrows, ncols, factor, first_bin, min_diag, stream)
+
+
+def insulation_into(d_band, nrows, ncols, windows, min_diag, d_out, out_words, stream=None, device=0):
+    """The insulation sums of the band at device pointer `d_band` for the `windows` (bins), into the
+    device array `d_out` (uint64[len(windows)][ncols]); enqueued on `stream`, nothing crosses to the
+    host."""
+    extractor(device).insulation_into(d_band, nrows, ncols, windows, min_diag, d_out, out_words, stream)
+
+
+def insulation(d_band, nrows, ncols, windows, min_diag=2, stream=None, device=0):
+    """The insulation sums of the band at device pointer `d_band`: numpy uint64[len(windows), ncols],
+    formed on the device."""
+    return extractor(device).insulation(d_band, nrows, ncols, windows, min_diag, stream)
+
+
+def coarse_insulation(d_band, nrows, ncols, factor, first_bin, windows, min_diag=2, stream=None, device=0):
+    """The insulation sums of the band at device pointer `d_band` at `factor` times its bin size,
+    coarsened and summed on the device."""
+    return extractor(device).coarse_insulation(d_band, nrows, ncols, factor, first_bin, windows, min_diag, stream)

@@ -78,6 +78,8 @@ struct modle_pixels_handle {
   GrowBuf<uint32_t, true> dense;  // modle_pixels_dense_to_host: the region (modle_dense.hip)
   // modle_pixels_marginals*: diag_sum (nrows words), then coverage (ncols words) (modle_marginals.hip)
   GrowBuf<uint64_t, true> marginals;
+  // modle_pixels_insulation_to_host: n_windows rows of ncols words (modle_insulation.hip)
+  GrowBuf<uint64_t, true> insulation;
 };
 
 #endif
