@@ -1,6 +1,6 @@
 /* modle_pixels.h -- C ABI of the sparse-pixel extraction (modle_amd/libmodle_pixels.so), of the
- * coarsening of a band, of its dense regions, of its marginals and of its insulation sums (further
- * down).
+ * coarsening of a band, of its dense regions, of its marginals, of its insulation sums and of its
+ * dot candidates (further down).
  *
  * The simulation leaves every interval as a dense band matrix in device memory
  * (modle_hip_interval_outputs).  A cooler file is made of the non-zero pixels only, sorted by
@@ -251,6 +251,70 @@ int modle_pixels_coarse_insulation_to_host(modle_pixels_handle* h, const uint32_
                                            uint64_t n_windows, uint64_t min_diag,
                                            const uint64_t** ins_sum, void* stream, char* err,
                                            size_t errlen);
+
+/* ---- Dots: HiCCUPS neighbourhood sums and the candidate pixels ---------------------------------
+ *
+ * A dot is a focal enrichment of a pixel over its surroundings.  For pixel (i, j), i <= j, d = j - i,
+ * obs = band[j * nrows + d], a window half-width `w` and a peak half-width `p`, 0 <= p < w <=
+ * MODLE_PIXELS_MAX_DOT_WINDOW, the four neighbourhoods of Rao et al. 2014 (and of cooltools), in (row,
+ * column) of the symmetric matrix, are
+ *   k = 0  donut       [i-w, i+w] x [j-w, j+w] without [i-p, i+p] x [j-p, j+p] and without the rest of
+ *                      row i and of column j                    area (2w+1)^2 - (2p+1)^2 - 4 (w-p)
+ *   k = 1  lower-left  [i+1, i+w] x [j-w, j-1] without [i+1, i+p] x [j-p, j-1]       area w^2 - p^2
+ *   k = 2  horizontal  rows i-1 .. i+1, columns [j-w, j-p-1] and [j+p+1, j+w]        area 6 (w-p)
+ *   k = 3  vertical    rows [i-w, i-p-1] and [i+p+1, i+w], columns j-1 .. j+1        area 6 (w-p)
+ * and O_k(i, j) is the exact integer sum of the band over neighbourhood k: at most 1681 words below
+ * 2^32, so below 2^43 -- it cannot overflow 64 bits and is exact as a double.
+ *
+ * A pixel is VALID when its whole (2w+1)^2 square lies inside the matrix, inside the band and on or
+ * above diagonal `min_diag`: i >= w, j + w < ncols, 2w + min_diag <= d <= nrows - 1 - 2w.  A call is
+ * accepted only when 4w + 1 + min_diag <= nrows; then no word that is no pixel (left-edge triangle,
+ * trailing word, d >= nrows) is ever read.  A band without a valid pixel is legal and gives zeros.
+ *
+ * The decision uses the HOST table scale[4][nrows] of doubles, every entry >= 0 and no NaN (+inf is
+ * allowed); only the entries at valid d are read.  A valid pixel is a CANDIDATE when obs >= min_count
+ * (min_count >= 1) and, for every k, (double)obs >= (double)O_k * scale[k][d]: one IEEE-754 double
+ * multiplication and one comparison, which is false against NaN (0 * inf).  Nothing else on the device
+ * uses floating point.
+ *
+ * Outputs (at least one; the call defines EVERY word of both, the caller does not pre-zero):
+ *   d_cand  uint32[nrows * ncols + 1] in the band's layout: obs at a candidate, 0 everywhere else
+ *           (triangle and trailing word included) -- a band modle_pixels_count / _extract accept as is;
+ *   d_sums  uint64[4][nrows * ncols], 8-byte aligned: d_sums[k][j * nrows + d] = O_k at a valid pixel,
+ *           0 elsewhere.  Without d_cand the table is not used and may be NULL.
+ *
+ * MODLE_PIXELS_ERR_ARG, with nothing written: a null handle or band, no output, nrows == 0, nrows >
+ * ncols, p >= w, w == 0, w > 20, 4w + 1 + min_diag > nrows, min_count == 0, a NaN or negative table
+ * entry at a valid d, a misaligned d_sums, an output that overlaps the band or the other output. */
+#define MODLE_PIXELS_MAX_DOT_WINDOW 20
+
+/* Enqueues the work on `stream`; the call does not wait. */
+int modle_pixels_dots(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols,
+                      uint64_t w, uint64_t p, uint64_t min_diag, uint64_t min_count,
+                      const double* scale, uint32_t* d_cand, uint64_t* d_sums, void* stream, char* err,
+                      size_t errlen);
+
+/* The candidates as sorted pixels: the kernel fills a scratch band of the context, then the count /
+ * scan / extract of modle_pixels_to_host run on it.  Results and `bin_offset` as for
+ * modle_pixels_to_host (pinned buffers of the context, valid until the next call on it). */
+int modle_pixels_dots_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                              uint64_t ncols, uint64_t w, uint64_t p, uint64_t min_diag,
+                              uint64_t min_count, const double* scale, int64_t bin_offset,
+                              const int64_t** bin1, const int64_t** bin2, const int32_t** count,
+                              const int64_t** bin1_offset, modle_pixels_stats* stats, void* stream,
+                              char* err, size_t errlen);
+
+/* The same at `factor` times the bin size: coarsens into the scratch band of the context (like
+ * modle_pixels_coarse_to_host), the candidates go to a second scratch band.  `w`, `p`, `min_diag`
+ * count coarse bins, the table has nrows' columns and the acceptance rule holds against nrows'
+ * (modle_pixels_coarse_shape); `bin_offset` is the interval's first bin within the COARSE file. */
+int modle_pixels_coarse_dots_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                                     uint64_t ncols, uint64_t factor, uint64_t first_bin, uint64_t w,
+                                     uint64_t p, uint64_t min_diag, uint64_t min_count,
+                                     const double* scale, int64_t bin_offset, const int64_t** bin1,
+                                     const int64_t** bin2, const int32_t** count,
+                                     const int64_t** bin1_offset, modle_pixels_stats* stats,
+                                     void* stream, char* err, size_t errlen);
 
 #ifdef __cplusplus
 }

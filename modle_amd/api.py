@@ -165,6 +165,32 @@ def insulation_score(ins_sum, n_valid):
     return out.reshape(s.shape)
 
 
+def cluster_dots(bin1, bin2, count, radius):
+    """Thins dot candidates to local maxima: the ascending indexes of the candidates that stay.  A
+    candidate stays unless another candidate lies within Chebyshev distance `radius` (bins, on both
+    axes) and beats it: a larger count, or the same count and a smaller (bin1, bin2).  Deterministic,
+    whatever the order of the input; radius 0 keeps every candidate (of distinct pixels).  This is a
+    local-maximum filter, NOT HiCCUPS' greedy merge of candidates into centroids with a growing radius:
+    a chain of candidates each within `radius` of the next keeps every local maximum along it."""
+    b1, b2 = np.asarray(bin1, dtype=np.int64), np.asarray(bin2, dtype=np.int64)
+    cnt, radius = np.asarray(count, dtype=np.int64), int(radius)
+    if not (b1.shape == b2.shape == cnt.shape) or b1.ndim != 1:
+        raise ValueError("cluster_dots: bin1, bin2 and count must be one-dimensional and of one length")
+    if radius < 0:
+        raise ValueError(f"cluster_dots: the radius {radius} is negative")
+    order = np.lexsort((b2, b1))
+    s1, s2, sc = b1[order], b2[order], cnt[order]
+    lo = np.searchsorted(s1, s1 - radius, side="left")
+    hi = np.searchsorted(s1, s1 + radius, side="right")
+    keep = np.ones(len(s1), dtype=bool)
+    for n in range(len(s1)):
+        o1, o2, oc = s1[lo[n]:hi[n]], s2[lo[n]:hi[n]], sc[lo[n]:hi[n]]
+        near = np.abs(o2 - s2[n]) <= radius
+        beats = (oc > sc[n]) | ((oc == sc[n]) & ((o1 < s1[n]) | ((o1 == s1[n]) & (o2 < s2[n]))))
+        keep[n] = not bool((near & beats).any())
+    return np.sort(order[keep])
+
+
 # ---------------------------------------------------------------------------------------------
 # device path
 # ---------------------------------------------------------------------------------------------
@@ -429,6 +455,100 @@ class Simulator:
         out = torch.empty((len(windows), ncols), dtype=torch.int64, device=torch.device("cuda", self.device))
         pixels.insulation_into(d_band, nrows, ncols, windows, min_diag, out.data_ptr(), out.numel(), stream,
                                device=self.device)
+        return out
+
+    def _dot_band(self, interval_id, factor, first_bin, stream):
+        """(device pointer, nrows, ncols, what keeps it alive) of the interval's band at `factor` times
+        the bin size: the band itself, or a torch scratch band the coarsening is enqueued into"""
+        from . import pixels
+
+        d_band, _, nrows, ncols = self.outputs(interval_id)
+        if int(factor) == 1:
+            return d_band, nrows, ncols, None
+        import torch
+
+        nr, nc = pixels.coarse_shape(nrows, ncols, factor, first_bin)
+        scratch = torch.empty(nr * nc + 1, dtype=torch.int32, device=torch.device("cuda", self.device))
+        pixels.extractor(self.device).coarsen_into(d_band, nrows, ncols, factor, first_bin, scratch.data_ptr(),
+                                                   nr * nc + 1, stream)
+        return scratch.data_ptr(), nr, nc, scratch
+
+    def dot_table(self, interval_id, w, p, folds=None, min_diag=2, factor=1, first_bin=0, stream=None):
+        """(scale, expected) of the interval for dots(): the table pixels.dot_scales builds from the
+        diagonal sums of the marginals pass (float64 [4, nrows]) and the expected count per diagonal,
+        e[d] = diag_sum[d] / (ncols - d) (float64 [nrows]), at `factor` times the bin size"""
+        from . import pixels
+
+        diag_sum, coverage = self.marginals(interval_id, 0, factor, first_bin, stream)
+        ncols = len(coverage)
+        scale = pixels.dot_scales(diag_sum, ncols, w, p, pixels.DOT_FOLDS if folds is None else folds, min_diag)
+        e = diag_sum.astype(np.float64) / (np.float64(ncols) - np.arange(len(diag_sum), dtype=np.float64))
+        return scale, e
+
+    def dots(self, interval_id, w=5, p=2, min_count=1, folds=None, min_diag=2, factor=1, first_bin=0, stream=None):
+        """The dot candidates of the interval: (bin1, bin2, count, expected), numpy int64, int64, int32
+        and float64 arrays in cooler order.  A candidate is a pixel (bin1, bin2) whose whole window of
+        half-width `w` bins lies in the band on or above diagonal `min_diag`, with count >= `min_count`
+        and count >= folds[k] * e[d] * O_k / X_k for each of the four HiCCUPS neighbourhoods k (donut,
+        lower-left, horizontal, vertical; peak half-width `p`): O_k the contacts of the neighbourhood,
+        summed on the device, X_k what the distance-decay curve e of the interval (marginals) expects
+        there; `folds` defaults to HiCCUPS' (1.75, 1.75, 1.5, 1.5).  The raw-count form of the test:
+        simulated counts need no balancing.  `expected` is e at each candidate's distance.  Only the
+        diagonal sums and the candidates cross to the host.  Call it after wait().  `factor`,
+        `first_bin`: as for pixels(); `w`, `p`, `min_diag` then count coarse bins.  cluster_dots() thins
+        the candidates to local maxima."""
+        from . import pixels
+
+        scale, e = self.dot_table(interval_id, w, p, folds, min_diag, factor, first_bin, stream)
+        d_band, _, nrows, ncols = self.outputs(interval_id)
+        if int(factor) == 1:
+            px = pixels.dots(d_band, nrows, ncols, w, p, min_diag, min_count, scale, 0, stream, device=self.device)
+        else:
+            px = pixels.coarse_dots(d_band, nrows, ncols, factor, first_bin, w, p, min_diag, min_count, scale, 0,
+                                    stream, device=self.device)
+        return px.bin1, px.bin2, px.count, e[px.bin2 - px.bin1]
+
+    def dots_tensors(self, interval_id, w=5, p=2, min_count=1, folds=None, min_diag=2, factor=1, first_bin=0,
+                     stream=None):
+        """The dot candidates of dots() as three torch tensors (bin1, bin2 int64, count int32) on the
+        simulator's device: the kernel fills a candidate band there, which is counted and extracted
+        into tensors of exactly nnz entries.  Only nnz and the nrows diagonal sums cross to the host."""
+        import torch
+
+        from . import pixels
+
+        scale, _ = self.dot_table(interval_id, w, p, folds, min_diag, factor, first_bin, stream)
+        d_band, nrows, ncols, keep = self._dot_band(interval_id, factor, first_bin, stream)
+        dev = torch.device("cuda", self.device)
+        ex = pixels.extractor(self.device)
+        cand = torch.empty(nrows * ncols + 1, dtype=torch.int32, device=dev)
+        offsets = torch.empty(ncols + 1, dtype=torch.int64, device=dev)
+        ex.dots_into(d_band, nrows, ncols, w, p, min_diag, min_count, scale, cand.data_ptr(), None, stream)
+        nnz = ex.count(cand.data_ptr(), nrows, ncols, offsets.data_ptr(), stream).nnz  # (waits)
+        del keep
+        bin1 = torch.empty(nnz, dtype=torch.int64, device=dev)
+        bin2 = torch.empty(nnz, dtype=torch.int64, device=dev)
+        count = torch.empty(nnz, dtype=torch.int32, device=dev)
+        ex.extract_into(cand.data_ptr(), nrows, ncols, 0, offsets.data_ptr(), bin1.data_ptr(), bin2.data_ptr(),
+                        count.data_ptr(), nnz, stream)
+        torch.cuda.synchronize(dev)  # the candidate band and the index go when this returns
+        return bin1, bin2, count
+
+    def dot_sums_tensor(self, interval_id, w, p, min_diag=2, factor=1, first_bin=0, stream=None):
+        """The four neighbourhood sums of every pixel of the interval as one torch int64 tensor
+        [4, ncols, nrows] on the simulator's device (out[k][j][d] = O_k of pixel (j - d, j) where it is
+        valid, 0 elsewhere), filled there by the kernel: nothing crosses to the host.  The words hold
+        the uint64 sums bit for bit (they are below 2^43)."""
+        import torch
+
+        from . import pixels
+
+        d_band, nrows, ncols, keep = self._dot_band(interval_id, factor, first_bin, stream)
+        out = torch.empty((4, ncols, nrows), dtype=torch.int64, device=torch.device("cuda", self.device))
+        pixels.dots_into(d_band, nrows, ncols, w, p, min_diag, 1, None, None, out.data_ptr(), stream,
+                         device=self.device)
+        if keep is not None:  # the scratch band goes when this returns
+            torch.cuda.synchronize(out.device)
         return out
 
     def simulate_interval(self, start, end, bar_pos, bar_dir, stp_active, stp_inactive, tasks):

@@ -11,7 +11,8 @@ contacts at several bin sizes, coarsened on the GPU) and, with the 1-D LEF posit
 square matrices of the named regions, unpacked on the GPU; with --expected `<prefix>_expected.tsv`, the
 contacts per diagonal, and with --coverage `<prefix>_coverage.bedgraph`, the contacts per bin, both
 summed on the GPU; with --insulation-windows `<prefix>_insulation.tsv`, the insulation sums and scores
-per bin over sliding diamond windows, summed on the GPU.  Everything heavy is native: parsing and
+per bin over sliding diamond windows, summed on the GPU; with --dots `<prefix>_dots.bedpe`, the pixels
+enriched over their four HiCCUPS neighbourhoods, found on the GPU.  Everything heavy is native: parsing and
 task generation in libmodle_hip.so (host), the simulation on the MI355X (one process per GPU;
 under torch.distributed.run the cells are sharded over the ranks and the matrices are summed
 with RCCL, or with --dist-backend gloo on host copies), the writers in libmodle_cooler.so.  `-t/--threads` is accepted and ignored."""
@@ -100,6 +101,21 @@ def window_list(text):
     return [genomic_distance(t) for t in items]
 
 
+MAX_DOT_WINDOW_BINS = 20  # include/modle_pixels.h
+DOT_FOLDS = (1.75, 1.75, 1.5, 1.5)  # HiCCUPS': donut, lower-left, horizontal, vertical
+
+
+def fold_list(text):
+    """`1.75,1.75,1.5,1.5`: the four thresholds of --dots-folds, finite and not negative"""
+    try:
+        folds = [float(t) for t in text.split(",")]
+    except ValueError:
+        folds = []
+    if len(folds) != 4 or any(not 0 <= f < float("inf") for f in folds):
+        raise argparse.ArgumentTypeError(f"{text!r} is not four comma-separated non-negative numbers")
+    return folds
+
+
 def mcool_bin_sizes(resolutions, base):
     """the bin sizes of the .mcool: the base (-r) and the listed resolutions, sorted, without
     duplicates.  Every listed one must be a multiple of the base and larger than it."""
@@ -141,6 +157,10 @@ def coverage_path(prefix):
 
 def insulation_path(prefix):
     return prefix + "_insulation.tsv"
+
+
+def dots_path(prefix):
+    return prefix + "_dots.bedpe"
 
 
 def build_parser():
@@ -186,6 +206,31 @@ def build_parser():
                          "coarsened on the GPU; default -r)")
     io.add_argument("--insulation-ignore-diags", type=int, default=None, metavar="N",
                     help="with --insulation-windows: leave out the first N diagonals (default 2)")
+    io.add_argument("--dots", action="store_true",
+                    help="also write <prefix>_dots.bedpe: the pixels that stand out over their four HiCCUPS "
+                         "neighbourhoods (donut, lower-left, horizontal, vertical) against the interval's own "
+                         "distance-decay curve, found on the GPU from raw counts and thinned to local maxima")
+    io.add_argument("--dots-resolution", type=genomic_distance, default=None, metavar="R",
+                    help="with --dots: the bin size dots are called at (a multiple of -r, coarsened on the GPU; "
+                         "default -r)")
+    io.add_argument("--dots-window", type=genomic_distance, default=None, metavar="SIZE",
+                    help="with --dots: the half-width of the neighbourhood window (a multiple of the dots "
+                         "resolution, at most 20 bins; 4 w + 1 diagonals and the ignored ones must fit -w; "
+                         "default 5 bins)")
+    io.add_argument("--dots-peak", type=genomic_distance, default=None, metavar="SIZE",
+                    help="with --dots: the half-width of the peak left out of the neighbourhoods (a multiple of "
+                         "the dots resolution below the window; default 2 bins)")
+    io.add_argument("--dots-min-count", type=int, default=None, metavar="N",
+                    help="with --dots: the smallest count of a dot (default 1)")
+    io.add_argument("--dots-folds", type=fold_list, default=None, metavar="a,b,c,d",
+                    help="with --dots: the enrichment asked for over the donut, lower-left, horizontal and "
+                         "vertical neighbourhood (default 1.75,1.75,1.5,1.5)")
+    io.add_argument("--dots-ignore-diags", type=int, default=None, metavar="N",
+                    help="with --dots: no window may reach below diagonal N (default 2)")
+    io.add_argument("--dots-cluster-radius", type=genomic_distance, default=None, metavar="SIZE",
+                    help="with --dots: a candidate is dropped when a better one lies within this distance on "
+                         "both axes (a multiple of the dots resolution; 0 keeps all; default 20kb, rounded down "
+                         "to whole bins, at least one bin)")
     io.add_argument("--log-model-internal-state", action="store_true",
                     help="write <prefix>_internal_state.log.gz: one line of statistics per task and "
                          "epoch (uses the diagnostic build libmodle_hip_statelog.so)")
@@ -313,7 +358,51 @@ Outputs = collections.namedtuple("Outputs", "cooler bigwig dense state_log expec
 # windows in base pairs as given and the diagonals left out
 Insulation = collections.namedtuple("Insulation", "path resolution windows min_diag")
 # (`insulation` came later: at the end, and None unless asked for)
-Preflight = collections.namedtuple("Preflight", "bin_sizes outputs rank world device insulation", defaults=(None,))
+# what --dots asks for: the file (None with --skip-output), the bin size, window, peak and cluster radius
+# in base pairs, the smallest count, the four folds and the diagonals no window may reach below
+Dots = collections.namedtuple("Dots", "path resolution window peak min_count folds min_diag radius")
+# (`insulation` and `dots` came later: at the end, and None unless asked for)
+Preflight = collections.namedtuple("Preflight", "bin_sizes outputs rank world device insulation dots",
+                                   defaults=(None, None))
+
+
+def dots_options(a, cfg):
+    """The dot calling the arguments ask for, as a Dots without a path, or None.  SystemExit: a
+    --dots-* option without --dots, a negative number of diagonals, a count below 1, a resolution that is
+    no multiple of -r, a window, peak or radius that is no multiple of the dots resolution, a peak that
+    is not below the window, a window above 20 bins."""
+    given = (("--dots-resolution", a.dots_resolution), ("--dots-window", a.dots_window), ("--dots-peak", a.dots_peak),
+             ("--dots-min-count", a.dots_min_count), ("--dots-folds", a.dots_folds),
+             ("--dots-ignore-diags", a.dots_ignore_diags), ("--dots-cluster-radius", a.dots_cluster_radius))
+    if not a.dots:
+        for name, v in given:
+            if v is not None:
+                raise SystemExit(f"{name} needs --dots")
+        return None
+    min_diag = 2 if a.dots_ignore_diags is None else a.dots_ignore_diags
+    if min_diag < 0:
+        raise SystemExit(f"--dots-ignore-diags: {min_diag} is negative")
+    min_count = 1 if a.dots_min_count is None else a.dots_min_count
+    if min_count < 1:
+        raise SystemExit(f"--dots-min-count: {min_count} is below 1")
+    base = int(cfg.bin_size)
+    res = base if a.dots_resolution is None else int(a.dots_resolution)
+    if res < base or res % base != 0:
+        raise SystemExit(f"--dots-resolution: {res} is not a multiple of the resolution ({base})")
+    window = 5 * res if a.dots_window is None else int(a.dots_window)
+    peak = min(2 * res, window - res) if a.dots_peak is None else int(a.dots_peak)
+    radius = max(1, 20_000 // res) * res if a.dots_cluster_radius is None else int(a.dots_cluster_radius)
+    for name, v, least in (("--dots-window", window, res), ("--dots-peak", peak, 0),
+                           ("--dots-cluster-radius", radius, 0)):
+        if v < least or v % res != 0:
+            raise SystemExit(f"{name}: {v} is not a {'positive ' if least else ''}multiple of the dots resolution "
+                             f"({res})")
+    if peak >= window:
+        raise SystemExit(f"--dots-peak: {peak} is not below the window ({window})")
+    if window // res > MAX_DOT_WINDOW_BINS:
+        raise SystemExit(f"--dots-window: {window} is {window // res} bins of {res}: at most {MAX_DOT_WINDOW_BINS}")
+    folds = list(DOT_FOLDS if a.dots_folds is None else a.dots_folds)
+    return Dots(None, res, window, peak, min_count, folds, min_diag, radius)
 
 
 def insulation_options(a, cfg):
@@ -347,8 +436,8 @@ def insulation_options(a, cfg):
 def preflight(a, cfg):
     """What the arguments alone settle and refuse, without a genome or a GPU.  SystemExit: a bad
     --mcool-resolutions list; --coverage-ignore-diags without --coverage, or negative; what
-    insulation_options refuses; on rank 0, an output that exists without --force (cooler or .mcool,
-    then bigwig, then .npz, then the expected, the coverage and the insulation file).  With
+    insulation_options and dots_options refuse; on rank 0, an output that exists without --force (cooler
+    or .mcool, then bigwig, then .npz, then the expected, the coverage, the insulation and the dots file).  With
     --skip-output no file is planned and none is looked at."""
     if a.coverage_ignore_diags is not None:
         if not a.coverage:
@@ -356,13 +445,14 @@ def preflight(a, cfg):
         if a.coverage_ignore_diags < 0:
             raise SystemExit(f"--coverage-ignore-diags: {a.coverage_ignore_diags} is negative")
     ins = insulation_options(a, cfg)
+    dots = dots_options(a, cfg)
     # (a bad list ends the run here, before anything is imported or simulated)
     bin_sizes = None if a.mcool_resolutions is None else mcool_bin_sizes(a.mcool_resolutions, cfg.bin_size)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     device = a.device if a.device is not None else int(os.environ.get("LOCAL_RANK", "0"))
     if a.skip_output:
-        return Preflight(bin_sizes, Outputs(None, None, None, None), rank, world, device, ins)
+        return Preflight(bin_sizes, Outputs(None, None, None, None), rank, world, device, ins, dots)
     cool_path, bw_path = output_paths(a.output_prefix, mcool=bin_sizes is not None)
     log_path = state_log_path(a.output_prefix) if world == 1 else \
         f"{a.output_prefix}_internal_state.rank{rank}.log.gz"
@@ -373,13 +463,15 @@ def preflight(a, cfg):
                       coverage_path(a.output_prefix) if a.coverage else None)
     if ins is not None:
         ins = ins._replace(path=insulation_path(a.output_prefix))
+    if dots is not None:
+        dots = dots._replace(path=dots_path(a.output_prefix))
     if rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(cool_path)), exist_ok=True)
         for p in (outputs.cooler, outputs.bigwig, outputs.dense, outputs.expected, outputs.coverage,
-                  None if ins is None else ins.path):
+                  None if ins is None else ins.path, None if dots is None else dots.path):
             if p and os.path.exists(p) and not a.force:
                 raise SystemExit(f"refusing to overwrite {p}: pass --force to overwrite")
-    return Preflight(bin_sizes, outputs, rank, world, device, ins)
+    return Preflight(bin_sizes, outputs, rank, world, device, ins, dots)
 
 
 def plan_run(a, cfg, pre, log):
@@ -401,6 +493,14 @@ def plan_run(a, cfg, pre, log):
             raise SystemExit(f"--insulation-windows: the diamond of {bad[1]} ({bad[2]} bins of "
                              f"{pre.insulation.resolution}) does not fit the band of {bad[0]} ({bad[3]} diagonals): "
                              f"the largest window that fits is {bad[4]} ({bad[4] // pre.insulation.resolution} bins)")
+    if pre.dots is not None and pre.dots.path is not None:
+        bad = driver.dots_misfit(plan, int(cfg.bin_size), pre.dots.resolution, pre.dots.window, pre.dots.min_diag)
+        if bad is not None:
+            fits = (f"the largest window that fits is {bad[4]} ({bad[4] // pre.dots.resolution} bins)" if bad[4]
+                    else "no window fits")
+            raise SystemExit(f"--dots-window: the window of {bad[1]} ({bad[2]} bins of {pre.dots.resolution}) with "
+                             f"{pre.dots.min_diag} diagonals ignored does not fit the band of {bad[0]} ({bad[3]} "
+                             f"diagonals): {fits}")
     regions = driver.dense_regions(plan, int(cfg.bin_size), chroms, a.dense_region) if a.dense_region else []
     return chroms, plan, regions
 
@@ -464,7 +564,7 @@ def simulate(a, log=print):
                           sort_keys=True)
         occupancies = driver.write_outputs(
             sim, cfg, plan, ids, tensors, pre.outputs, pre.bin_sizes, regions, pre.rank, log, a.dist_backend,
-            coverage_min_diag=a.coverage_ignore_diags or 0, insulation=pre.insulation, assembly=a.assembly_name,
+            coverage_min_diag=a.coverage_ignore_diags or 0, insulation=pre.insulation, dots=pre.dots, assembly=a.assembly_name,
             generated_by="modle_amd (MI355X)", metadata_json=meta,
             force_overwrite=a.force, chroms=chroms)
     finally:

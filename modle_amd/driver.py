@@ -535,6 +535,97 @@ def _interval_insulation(sim, plan, ids, windows, min_diag, marginals, k, factor
     return ins_sum, n_valid
 
 
+def dots_misfit(plan, base, resolution, window, min_diag):
+    """The first (name of the interval, window in bp, its bins, diagonals of the band, largest window in
+    bp that fits or 0) of an entry of the plan that has a matrix in whose band at `resolution` no pixel
+    can hold the whole window of `window` bp (a multiple of `resolution`) on or above diagonal
+    `min_diag`, 4 * w + 1 + min_diag > nrows' -- or None."""
+    base, res, w = int(base), int(resolution), int(window) // int(resolution)
+    for entry in plan:
+        iv = entry["interval"]
+        if entry["skipped"] or entry["ncols"] == 0:
+            continue
+        nr, _ = insulation_shape(entry["nrows"], entry["ncols"], int(iv["start"]) // base, res // base)
+        if 4 * w + 1 + int(min_diag) > nr:
+            return interval_name(iv), int(window), w, nr, max(0, (nr - 1 - int(min_diag)) // 4) * res
+    return None
+
+
+def check_dots(name, nrows, ncols, w, min_diag, min_count, bin1, bin2, count):
+    """What the candidates of a band of `nrows` x `ncols` (api.Simulator.dots) must satisfy before a row
+    is written: strictly ascending in (bin1, bin2), every one a valid pixel -- bin1 >= w, bin2 + w <
+    ncols, 2 w + min_diag <= bin2 - bin1 <= nrows - 1 - 2 w -- and count >= min_count.  RuntimeError,
+    naming the interval and the first candidate that fails."""
+    w, lo, hi = int(w), 2 * int(w) + int(min_diag), int(nrows) - 1 - 2 * int(w)
+    last = None
+    for b1, b2, c in zip(map(int, bin1), map(int, bin2), map(int, count)):
+        if last is not None and (b1, b2) <= last:
+            raise RuntimeError(f"{name}: the dot candidate ({b1}, {b2}) does not follow {last} in (bin1, bin2) order")
+        if b1 < w or b2 + w >= int(ncols) or not lo <= b2 - b1 <= hi:
+            raise RuntimeError(f"{name}: the dot candidate ({b1}, {b2}) is no valid pixel for a window of {w} bins "
+                               f"(diagonals {lo} .. {hi}, {int(ncols)} bins)")
+        if c < int(min_count):
+            raise RuntimeError(f"{name}: the dot candidate ({b1}, {b2}) has count {c}, below {int(min_count)}")
+        last = (b1, b2)
+
+
+def dots_header():
+    """the header line of <prefix>_dots.bedpe"""
+    return "#chrom1\tstart1\tend1\tchrom2\tstart2\tend2\tcount\texpected\tobserved_over_expected\n"
+
+
+def dots_lines(iv, base, factor, bin1, bin2, count, expected):
+    """the rows of <prefix>_dots.bedpe for one interval, one per dot, in the order given: chrom, start
+    and end of bin1, the same of bin2, the count, the repr of the expected count at that distance and
+    the repr of their quotient.  The bins are of `factor` * `base` base pairs: fine bins count from the
+    interval's start and coarse bins are anchored at the chromosome's, so the first and the last bin are
+    clipped to the interval (like insulation_lines)."""
+    start, end, base, k = int(iv["start"]), int(iv["end"]), int(base), int(factor)
+    p = (start // base) % k
+
+    def span(c):
+        return start + max(0, c * k - p) * base, min(end, start + ((c + 1) * k - p) * base)
+
+    out = []
+    for b1, b2, c, e in zip(map(int, bin1), map(int, bin2), map(int, count), map(float, expected)):
+        (lo1, hi1), (lo2, hi2) = span(b1), span(b2)
+        ratio = c / e if e > 0 else float("inf")
+        out.append(f"{iv['name']}\t{lo1}\t{hi1}\t{iv['name']}\t{lo2}\t{hi2}\t{c}\t{e!r}\t{ratio!r}\n")
+    return out
+
+
+def write_dots(path, plan, base, resolution, dots):
+    """<prefix>_dots.bedpe: the header, then the dots of every entry of the plan that is not skipped, in
+    plan order, at the bin size `resolution` (a multiple of `base`).  `dots(k, factor, first_bin)`
+    returns (bin1, bin2, count, expected) of plan entry k -- the clustered candidates, interval-relative
+    bins -- or None for an entry without a matrix."""
+    factor = int(resolution) // int(base)
+    with open(path, "w") as fh:
+        fh.write(dots_header())
+        for k, entry in enumerate(plan):
+            if entry["skipped"]:
+                continue
+            iv = entry["interval"]
+            got = dots(k, factor, int(iv["start"]) // int(base))
+            if got is not None:
+                fh.writelines(dots_lines(iv, base, factor, *got))
+
+
+def _interval_dots(sim, plan, ids, w, p, min_count, folds, min_diag, radius, k, factor, first_bin):
+    """write_dots' callback: the candidates found on the device in the matrix where it lies (with several
+    ranks: the reduced tensor) for `w`, `p`, `radius` in bins, verified (check_dots) and thinned to local
+    maxima (api.cluster_dots)"""
+    if ids[k] is None:
+        return None
+    bin1, bin2, count, expected = sim.dots(ids[k], w=w, p=p, min_count=min_count, folds=folds, min_diag=min_diag,
+                                           factor=factor, first_bin=first_bin)
+    entry = plan[k]
+    nr, nc = insulation_shape(entry["nrows"], entry["ncols"], first_bin, factor)
+    check_dots(interval_name(entry["interval"]), nr, nc, w, min_diag, min_count, bin1, bin2, count)
+    keep = api.cluster_dots(bin1, bin2, count, radius)
+    return bin1[keep], bin2[keep], count[keep], expected[keep]
+
+
 def reduce_to_rank0(t, backend, rank):
     """Sum of the ranks' tensors `t` into rank 0's, in place (the other ranks' tensors are unspecified
     afterwards).  `nccl` (= RCCL): on the device tensors.  `gloo`: on host copies -- the rehearsal with
@@ -565,13 +656,13 @@ def reduce_missed(missed, backend, rank, device=None):
 
 
 def write_outputs(sim, cfg, plan, ids, tensors, outputs, bin_sizes=None, regions=(), rank=0, log=print,
-                  backend="nccl", coverage_min_diag=0, insulation=None, **attrs):
+                  backend="nccl", coverage_min_diag=0, insulation=None, dots=None, **attrs):
     """What a finished launch writes while the simulator is open: the state log (every rank its
     own), then on rank 0 the cooler or .mcool with the missing-interactions warnings, the dense
     `regions` (of dense_regions), the distance-decay curves (at every bin size of the file) and the
     coverage without the diagonals below `coverage_min_diag`, and the insulation track `insulation` (a
     cli.Insulation: path, resolution, windows in base pairs, min_diag; None or without a path: not
-    written).  `outputs.state_log`, `.cooler`, `.dense`,
+    written), and the dots `dots` (a cli.Dots; None or without a path: not written).  `outputs.state_log`, `.cooler`, `.dense`,
     `.expected`, `.coverage`: the paths, None for a file that is not written; without a cooler
     (--skip-output) the matrices are only summed, for the warnings.  `tensors`: with several ranks the (contacts, occupancy) torch tensors per plan entry;
     they are reduced in place onto rank 0 (reduce_to_rank0 with `backend`), which extracts from the
@@ -638,6 +729,13 @@ def write_outputs(sim, cfg, plan, ids, tensors, outputs, bin_sizes=None, regions
                          functools.partial(_interval_insulation, sim, plan, ids, bins, int(insulation.min_diag),
                                            marginals))
         log(f"written {insulation.path}")
+    if dots is not None and dots.path is not None:
+        res = int(dots.resolution)
+        write_dots(dots.path, plan, int(cfg.bin_size), res,
+                   functools.partial(_interval_dots, sim, plan, ids, int(dots.window) // res, int(dots.peak) // res,
+                                     int(dots.min_count), list(dots.folds), int(dots.min_diag),
+                                     int(dots.radius) // res))
+        log(f"written {dots.path}")
     return occupancies
 
 

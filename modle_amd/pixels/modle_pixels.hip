@@ -265,6 +265,7 @@ extern "C" void modle_pixels_destroy(modle_pixels_handle* h) {
   (void)hipSetDevice(h->device);
   (void)hipFree(h->d_stats);
   (void)hipHostFree(h->h_stats);
+  if (h->dot_scale_copied != nullptr) (void)hipEventDestroy(h->dot_scale_copied);
   delete h;  // (releases every buffer of the context)
 }
 

@@ -80,6 +80,11 @@ struct modle_pixels_handle {
   GrowBuf<uint64_t, true> marginals;
   // modle_pixels_insulation_to_host: n_windows rows of ncols words (modle_insulation.hip)
   GrowBuf<uint64_t, true> insulation;
+  // modle_pixels_dots*: the candidate band of the to-host forms, and the scale table (4 rows of nrows
+  // doubles) with the event that marks its pinned copy as read (modle_dots.hip)
+  GrowBuf<uint32_t> dot_cand;
+  GrowBuf<double, true> dot_scale;
+  hipEvent_t dot_scale_copied = nullptr;
 };
 
 #endif
