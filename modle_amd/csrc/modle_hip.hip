@@ -203,7 +203,12 @@ modle_hip_handle* modle_hip_create(const modle_hip_config* c, int device, char* 
   static_assert(RNG_BLOCK == 512, "the host half is compiled with the 8-wave geometry");
   // (one table for every kernel: the 8-wave kernels hop block by block, 512 outputs; the 12-wave kernels
   // hop once per pair of their blocks of 256: sim_types.h RNG_HOP)
-  const std::vector<uint64_t> jump = modle_host::build_jump_table(512);
+  // The device keeps it in planes (jump_planes.h: conflict-free row reads); every kernel copies
+  // the uploaded words to its LDS as they are (load_block_tables).
+  const std::vector<uint64_t> canonical = modle_host::build_jump_table(512);
+  static_assert(jump_planes::TABLE_WORDS == JUMP_TABLE_WORDS, "one table size on host and device");
+  std::vector<uint64_t> jump(canonical.size());
+  jump_planes::permute(canonical.data(), jump.data());
   std::vector<f64> zig;
   zig.insert(zig.end(), ZIG_NORM_X, ZIG_NORM_X + 129);
   zig.insert(zig.end(), ZIG_NORM_Y, ZIG_NORM_Y + 129);

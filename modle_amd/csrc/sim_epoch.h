@@ -347,6 +347,9 @@ MODLE_DEV u32 simulate_cell(const Params& p, const Interval& iv, const Task& tas
 #ifndef MODLE_SUBTIMER
   c.ph[15] = wave::clock() - t_cell;  // (the whole cell: what the phases do not add up to is the glue between them)
 #endif
+#ifdef MODLE_PROF_RNG
+  c.ph[14] = c.g.gen_ticks;  // (the block generator, wherever it was called from: slot 14 holds nothing else)
+#endif
   if (lds.phase_ticks != nullptr && wave::lane() == 0) {
     for (int i = 0; i < 16; ++i) wave::atomic_add_u64(lds.phase_ticks + i, c.ph[i]);
   }

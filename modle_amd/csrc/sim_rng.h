@@ -14,8 +14,15 @@
 //   * The cell's single xoshiro256++ stream is produced in blocks of RNG_BLOCK raw outputs by
 //     all 64 lanes (lane l owns RNG_CHUNK consecutive outputs of every block and hops to its
 //     chunk of the next block with a GF(2) jump table; the 12-wave kernels hop once per pair of
-//     blocks: rng_gen_block_call) and consumed strictly in the reference's order; draws whose raw-output count is data dependent are resolved with a
-//     speculate / verify / restart scheme so the stream position of every draw is exact.
+//     blocks: rng_gen_block_call) and consumed strictly in the reference's order; draws whose
+//     raw-output count is data dependent are resolved with a speculate / verify / restart scheme so
+//     the stream position of every draw is exact.
+//   * The jump table lies in LDS in planes (jump_planes.h: the sixteen half-rows of a nibble 16 bytes
+//     apart, so the row reads of a hop are free of bank conflicts), and rng_hop keeps the fetches of
+//     the next two rows in flight while it folds the last two.  The hop runs inside a real call and
+//     may clobber no more registers than it did with one group of four rows (68 VGPRs in the 12-wave
+//     kernels): the callers keep values in the others across the call, and every form with more
+//     rows in flight, or with the emission interleaved, made the kernels spill (profiles/README.md r08).
 #pragma once
 #include "sim_types.h"
 
@@ -140,6 +147,9 @@ struct Rng {
   const u32* feed_abort;  // fed stream: the host's abort word, read while waiting for a block (or nullptr)
   u32 feed_error;      // fed stream: non-zero once a wait for the producer was abandoned (the outputs
                        // consumed since are not the stream's: the consumer reports the status)
+#ifdef MODLE_PROF_RNG
+  u64 gen_ticks;       // profiling build with -DMODLE_PROF_RNG: time spent in rng_gen_block (wave::clock ticks)
+#endif
 };
 // Hand-over words between a consumer of the stream and the wave that produces its blocks (u32, LDS;
 // helper-wave mode, sim_helper.h).  The producer replaces the older block of the ring once the
@@ -196,30 +206,46 @@ MODLE_DEV u32 ring_index(u64 p) {
   return blk * RNG_BLOCK + (off ^ ((off / RNG_SWZ) & (RNG_SWZ - 1)));
 }
 
-// T^RNG_HOP * state: XOR of one table row (4 words) per state nibble.  Rows are fetched in groups
-// of four (all loads of a group in flight, then folded; left alone the compiler waits for every LDS
-// load before issuing the next one), each row as two 128-bit reads, and folded on 32-bit halves with
-// three-input XORs.
+// rows of the hop that are fetched together (one register set; the hop keeps two)
+#ifndef MODLE_RNG_HOP_GROUP
+#define MODLE_RNG_HOP_GROUP 2
+#endif
+constexpr int RNG_HOP_GROUP = MODLE_RNG_HOP_GROUP;
+constexpr int RNG_HOP_GROUPS = 64 / RNG_HOP_GROUP;
+static_assert(RNG_HOP_GROUP % 2 == 0 && 64 % RNG_HOP_GROUP == 0, "rows are folded in pairs");
+
+// the rows of group g of the hop: one per state nibble, each as two 128-bit reads
+MODLE_DEV void rng_hop_fetch(const MODLE_LDS u64* jump, const u64 w[4], int g, wave::LdsRow r[RNG_HOP_GROUP]) {
+#pragma unroll
+  for (int q = 0; q < RNG_HOP_GROUP; ++q) {
+    const int nib = g * RNG_HOP_GROUP + q;  // nibble k of state word wi
+    const int wi = nib / 16, k = nib % 16;
+    const u32 half = k < 8 ? static_cast<u32>(w[wi]) : static_cast<u32>(w[wi] >> 32);
+    const u32 v = (half >> (4 * (k % 8))) & 15u;
+    r[q] = wave::lds_load_row(jump + ((wi * 16 + k) * 16) * 4, v);
+  }
+}
+
+// T^RNG_HOP * state: XOR of one table row (4 words) per state nibble, folded on 32-bit halves with
+// three-input XORs (XOR is associative and commutative: the order of the fold does not show in the
+// result).  Rows are fetched in groups of RNG_HOP_GROUP into two register sets: the fetches of group
+// g + 1 are issued before group g is folded, so the LDS round trip is exposed once per hop, not once
+// per group.  (Left alone the compiler waits for every LDS load before issuing the next one: hence
+// the fences.  Two sets of two rows are the 32 registers one group of four took before; more rows
+// in flight make the call clobber registers its callers keep values in.)
 MODLE_DEV void rng_hop(const MODLE_LDS u64* jump, const u64 w[4], u64 j[4]) {
   u32 acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  constexpr int GROUP = 4;
+  wave::LdsRow r[2][RNG_HOP_GROUP];
+  rng_hop_fetch(jump, w, 0, r[0]);
 #pragma unroll
-  for (int g = 0; g < 64 / GROUP; ++g) {
-    wave::LdsRow r[GROUP];
-#pragma unroll
-    for (int q = 0; q < GROUP; ++q) {
-      const int nib = g * GROUP + q;  // nibble k of state word wi
-      const int wi = nib / 16, k = nib % 16;
-      const u32 half = k < 8 ? static_cast<u32>(w[wi]) : static_cast<u32>(w[wi] >> 32);
-      const u32 v = (half >> (4 * (k % 8))) & 15u;
-      r[q] = wave::lds_load_row(jump + ((wi * 16 + k) * 16) * 4, v);
-    }
+  for (int g = 0; g < RNG_HOP_GROUPS; ++g) {
+    if (g + 1 < RNG_HOP_GROUPS) rng_hop_fetch(jump, w, g + 1, r[(g + 1) & 1]);
     wave::sched_fence();
 #pragma unroll
     for (int h = 0; h < 8; ++h) {
-      acc[h] = wave::xor3(acc[h], r[0].h[h], r[1].h[h]);
-      acc[h] = wave::xor3(acc[h], r[2].h[h], r[3].h[h]);
-      wave::pin(acc[h]);  // fold this group before the next group's rows are fetched
+#pragma unroll
+      for (int q = 0; q < RNG_HOP_GROUP; q += 2) acc[h] = wave::xor3(acc[h], r[g & 1][q].h[h], r[g & 1][q + 1].h[h]);
+      wave::pin(acc[h]);  // fold this group before the group after the next is fetched
     }
     wave::sched_fence();
   }
@@ -354,11 +380,17 @@ MODLE_DEV void rng_gen_block(Rng& g) {
     rng_take_fed_block(g);
     return;
   }
+#ifdef MODLE_PROF_RNG
+  const u64 t_gen = wave::clock();
+#endif
   wave::lockstep();  // other lanes may still be reading the block that is about to be replaced
   rng_gen_block_call((MODLE_LDS u64*)g.ring, (const MODLE_LDS u64*)g.jump, (MODLE_LDS u64*)g.state,
                      (MODLE_LDS u64*)g.snap, ((static_cast<u32>(g.gen_end) / RNG_BLOCK) & 1u) * RNG_BLOCK);
   g.gen_end += RNG_BLOCK;
   wave::sync_lds();
+#ifdef MODLE_PROF_RNG
+  g.gen_ticks += wave::clock() - t_gen;
+#endif
 }
 
 MODLE_DEV void rng_init(Rng& g, const u64 state[4]) {
@@ -378,6 +410,9 @@ MODLE_DEV void rng_init(Rng& g, const u64 state[4]) {
   g.feed = nullptr;
   g.feed_abort = nullptr;
   g.feed_error = 0;
+#ifdef MODLE_PROF_RNG
+  g.gen_ticks = 0;
+#endif
   wave::sync_lds();
 }
 #else

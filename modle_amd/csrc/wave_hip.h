@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "jump_planes.h"
+
 // software log / exp / pow shared with the CPU oracle (parity by construction, modle_math.h)
 #define MM_FN __device__ inline
 #define MM_TABLE __device__ static const
@@ -178,15 +180,17 @@ MODLE_DEV uint32_t own_regs(uint32_t v) {
 MODLE_DEV uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
   return static_cast<uint32_t>(__builtin_amdgcn_bitop3_b32(a, b, c, 0x96));
 }
-// Row `v` of a 16-row LDS table of 4 x 64-bit words (32 bytes per row, the table 16-byte aligned):
-// two 128-bit reads.  h[2 i], h[2 i + 1] = low / high half of word i.
+// Row `v` of a 16-row LDS table of 4 x 64-bit words (the table 16-byte aligned), kept as two planes
+// of sixteen half-rows (jump_planes.h: the sixteen lanes of an LDS pass then hit sixteen different
+// groups of banks, or the same address): two 128-bit reads.  h[2 i], h[2 i + 1] = low / high half
+// of word i.
 struct LdsRow {
   uint32_t h[8];
 };
 MODLE_DEV LdsRow lds_load_row(const MODLE_LDS uint64_t* table, uint32_t v) {
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  const MODLE_LDS u32x4* row = reinterpret_cast<const MODLE_LDS u32x4*>(table) + 2 * v;
-  const u32x4 a = row[0], b = row[1];
+  const MODLE_LDS u32x4* row16 = reinterpret_cast<const MODLE_LDS u32x4*>(table);
+  const u32x4 a = row16[jump_planes::half_row16(v, 0)], b = row16[jump_planes::half_row16(v, 1)];
   return LdsRow{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}};
 }
 
