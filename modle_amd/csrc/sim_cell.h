@@ -69,8 +69,13 @@ struct Cell {
 };
 // (slot 14: LEF activation; a sub-phase measurement may claim slots 14 and 15 and sends the
 // activation time to slot 1 with the bind phase)
-#if defined(MODLE_SUBTIMER_LEFBAR) || defined(MODLE_SUBTIMER_STATS) || defined(MODLE_SUBTIMER_RANK)
+#if defined(MODLE_SUBTIMER_LEFBAR) || defined(MODLE_SUBTIMER_STATS) || defined(MODLE_SUBTIMER_RANK) || \
+    defined(MODLE_SUBTIMER_PRIMARY) || defined(MODLE_SUBTIMER_BURNIN) || defined(MODLE_COUNT_PRIMARY_FAR)
 #define MODLE_SUBTIMER 1
+#endif
+#if defined(MODLE_SUBTIMER_LEFBAR) + defined(MODLE_SUBTIMER_STATS) + defined(MODLE_SUBTIMER_RANK) + defined(MODLE_SUBTIMER_PRIMARY) + \
+        defined(MODLE_SUBTIMER_BURNIN) + defined(MODLE_COUNT_PRIMARY_FAR) > 1
+#error "one measurement inside a phase per build: they share slots 14 and 15"
 #endif
 #ifdef MODLE_SUBTIMER
 #define MODLE_PH_ACTIVATION 1

@@ -1146,28 +1146,19 @@ MODLE_DEV u32 stalling_barrier_pos(const Interval& iv, u32 word) {
 #ifndef MODLE_PRIMARY_BACK
 #define MODLE_PRIMARY_BACK 128  // (a smaller value in a test build of the emulator exercises the fall-back)
 #endif
+#ifndef MODLE_PRIMARY_NEAR
+#define MODLE_PRIMARY_NEAR 16  // (a power of two; the timing with 16: profiles/README.md, r09)
+#endif
 constexpr u32 PRIMARY_BACK = MODLE_PRIMARY_BACK;  // fwd ranks before a block's first rev rank in its slice
-static_assert(PRIMARY_BACK + 128 <= STAGE_CAP, "the slice must reach the block's last rank");
-struct PrimaryBatch {
-  wave::U32x2 R, rev_move;
-  u32 sp[STAGE_CAP / 64];
+constexpr u32 PRIMARY_NEAR = MODLE_PRIMARY_NEAR;  // entries below a unit's own rank its short search covers
+constexpr u32 PRIMARY_SLICE_Q = (PRIMARY_BACK + 256 + 63) / 64;  // staged words per lane
+static_assert(64 * PRIMARY_SLICE_Q <= 2 * SORT_LDS_CAP, "the slice must fit the LDS sort buffer");
+static_assert(PRIMARY_NEAR >= 2 && (PRIMARY_NEAR & (PRIMARY_NEAR - 1)) == 0 && PRIMARY_NEAR <= 256,
+              "the short search halves its step down to one");
+struct PrimaryBlk {
+  wave::U32x4 R, rev_move;
+  u32 sp[PRIMARY_SLICE_Q];
 };
-// `base` is even; ranks outside [first, n) are masked where the values are used
-template <class Op>
-MODLE_DEV void primary_load_batch(Op op, const Workspace& ws, u32 n, u32 base, u32 w0, u32 lane,
-                                  PrimaryBatch& b, bool rev_side) {
-  if (rev_side) {
-    const u32 k0 = base + 2 * lane;
-    const u32 kq = k0 < n ? k0 : 0u;
-    b.R = wave::ld2(ws.r_pos, kq);
-    b.rev_move = wave::ld2(ws.r_move, kq);
-  }
-#pragma unroll
-  for (u32 q = 0; q < STAGE_CAP / 64; ++q) {
-    const u32 t = lane + 64 * q;
-    b.sp[q] = op(ws.f_pos, w0 + t, w0 + t < n, UNBOUND, b.sp[q]);
-  }
-}
 
 MODLE_DEV_NOINLINE void detect_primary(Cell& c, BoundaryCounts bc, bool fuse_correct) {
   Workspace& ws = c.ws;
@@ -1184,7 +1175,6 @@ MODLE_DEV_NOINLINE void detect_primary(Cell& c, BoundaryCounts bc, bool fuse_cor
   const bool never_collide = p.p_bypass != 0.0 && p_collide == 0.0;
   const bool trials = p.p_bypass != 0.0 && !never_collide;
   const u32 prim = EV_COLLISION | EV_LEF_LEF_PRIMARY;
-  u32* stage = c.lds.stage;  // slice of the fwd positions, ranks [w0, w0 + STAGE_CAP)
   // the list of pairs (rank of the rev unit, fwd units strictly upstream of it) in scratch that is
   // idle until the secondary pass; lanes with nothing to store hit scratch words of their own
   u32* const q_k = ws.tmp[0];
@@ -1196,126 +1186,166 @@ MODLE_DEV_NOINLINE void detect_primary(Cell& c, BoundaryCounts bc, bool fuse_cor
   // ---- pass 1 ----------------------------------------------------------------------------------
   // pf = number of fwd units strictly upstream of R.  Every LEF has its rev unit at or upstream of
   // its fwd unit, so pf(k) = k - (LEFs whose loop spans the position of rev unit k): at most k, and
-  // below it by the local depth of coverage, a few units to a few dozen.  The slice of fwd positions
-  // a block of 128 rev ranks searches is therefore the FIXED window of ranks [base - PRIMARY_BACK,
-  // base + 128): nothing about the loads of a block depends on the search of the block before it
-  // (it used to: the slice started where the previous block's last unit fell, so every block paid
-  // a full memory round trip after its search), and they are requested two blocks ahead.  A unit
-  // with more than PRIMARY_BACK loops over it is looked up in device memory.
+  // below it by the local depth of coverage, a few units to a few dozen.  Blocks of 256 rev ranks, four
+  // consecutive ranks per lane; a block stages the FIXED window of fwd ranks [base - PRIMARY_BACK,
+  // base + 256) once (nothing about the loads of a block depends on the search of the block before
+  // it: they are requested one block ahead), in the LDS sort buffer, which is idle between the
+  // LEF-BAR sweep and the secondary pass.  In the slice the answer of unit k is at or below the
+  // unit's own index a = k - w0, so every unit searches the PRIMARY_NEAR entries below a (fixed
+  // steps, no loop control).  A unit under more loops than that searches the rest of the slice, and
+  // one under more than PRIMARY_BACK is looked up in device memory: two rare divergent paths.
+  // Entries past the last rank repeat the last fwd position, which is never below the position of an
+  // active rev unit (pf <= k < n).
   const u32 first = bc.n5;
   const auto slice_start = [](u32 base) { return base > PRIMARY_BACK ? base - PRIMARY_BACK : 0u; };
+#ifdef MODLE_SUBTIMER_PRIMARY
+  const u64 t_pass1 = wave::clock();
+#endif
   {
-    const u32 b0 = first & ~1u;
-    PrimaryBatch pa, pb;
-    primary_load_batch(wave::LdRaw{}, ws, n, b0, slice_start(b0), lane, pa, true);
-    if (b0 + 128 < n) primary_load_batch(wave::LdRaw{}, ws, n, b0 + 128, slice_start(b0 + 128), lane, pb, true);
-    const auto block = [&](PrimaryBatch& cur, u32 base) {
-      const u32 w0 = slice_start(base);
-      primary_load_batch(wave::LdMask{}, ws, n, base, w0, lane, cur, false);  // (defaults outside the range)
-      u32 k[2], R[2], rev_move[2];
-      bool act[2];
+    u32* const sl = reinterpret_cast<u32*>(c.lds.sort_lds);
+    const auto load_blk = [&](u32 base, PrimaryBlk& r) {
+      const u32 w = base + 4 * lane;
+      const u32 wq = w < n ? w : 0u;
+      r.R = wave::ld4(ws.r_pos, wq);
+      r.rev_move = wave::ld4(ws.r_move, wq);
+      const u32 t0 = slice_start(base) + lane;
 #pragma unroll
-      for (u32 j = 0; j < 2; ++j) {
-        k[j] = base + 2 * lane + j;
-        act[j] = k[j] >= first && k[j] < n;
-        R[j] = act[j] ? cur.R.v[j] : UNBOUND;
-        rev_move[j] = act[j] ? cur.rev_move.v[j] : 0u;
-      }
+      for (u32 q = 0; q < PRIMARY_SLICE_Q; ++q) r.sp[q] = wave::LdRaw{}(ws.f_pos, umin(t0 + 64 * q, n - 1), true, 0, 0u);
+    };
+    PrimaryBlk cur;
+    load_blk(first & ~255u, cur);
+    for (u32 base = first & ~255u; base < n; base += 256) {
+      const PrimaryBlk g = cur;
+      const u32 w0 = slice_start(base);
       wave::lockstep();
 #pragma unroll
-      for (u32 q = 0; q < STAGE_CAP / 64; ++q) stage[lane + 64 * q] = cur.sp[q];
+      for (u32 q = 0; q < PRIMARY_SLICE_Q; ++q) sl[lane + 64 * q] = g.sp[q];
       wave::sync_lds();
-      // (the block's registers are free: request the block after the next one)
-      if (base + 256 < n) primary_load_batch(wave::LdRaw{}, ws, n, base + 256, slice_start(base + 256), lane, cur, true);
-      const u32 prev_in = wave::shfl_up1(R[1]);
+      if (base + 256 < n) load_blk(base + 256, cur);  // (taken over at the top of the next block)
+      const u32 k0 = base + 4 * lane;
+      u32 R[4], rev_move[4];
+      bool act[4];
+#pragma unroll
+      for (u32 j = 0; j < 4; ++j) {
+        act[j] = k0 + j >= first && k0 + j < n;
+        R[j] = act[j] ? g.R.v[j] : UNBOUND;
+        rev_move[j] = act[j] ? g.rev_move.v[j] : 0u;
+      }
+      const u32 prev_in = wave::shfl_up1(R[3]);
       const u32 Rprev0 = lane > 0 ? prev_in : carry_pos;
-      // number of staged positions below R: a fixed-step search (no loop control, the eight steps
-      // are the same for every unit; the two reads of a round are issued together)
-      u32 lo[2] = {0, 0};
-      static_assert(STAGE_CAP == 256, "the search below covers 256 entries");
+      // the short search: a unit's window starts PRIMARY_NEAR entries below its own index a0 + j, or at
+      // the slice's start; the entry at the window's start is read last (it is the partner's position
+      // when the search stays there), the steps cover the PRIMARY_NEAR - 1 entries behind it
+      const u32 a0 = k0 - w0;
+      u32 es[4], lo[4];
 #pragma unroll
-      for (u32 sft = 128; sft >= 1; sft >>= 1) {
-        u32 sv[2];
+      for (u32 j = 0; j < 4; ++j) {
+        es[j] = umax(a0 + j, PRIMARY_NEAR) - PRIMARY_NEAR;
+        lo[j] = es[j] + 1;
+      }
 #pragma unroll
-        for (u32 j = 0; j < 2; ++j) sv[j] = stage[lo[j] + sft - 1];
+      for (u32 sft = PRIMARY_NEAR / 2; sft >= 1; sft >>= 1) {
+        u32 sv[4];
+#pragma unroll
+        for (u32 j = 0; j < 4; ++j) sv[j] = sl[lo[j] + sft - 1];
         wave::sched_fence();
 #pragma unroll
-        for (u32 j = 0; j < 2; ++j) {
+        for (u32 j = 0; j < 4; ++j) {
           if (sv[j] < R[j]) lo[j] += sft;
         }
         wave::sched_fence();
       }
-      const u32 st_last = stage[STAGE_CAP - 1];
-      u32 pf[2] = {0, 0};
-      bool beyond = false;  // the answer lies outside the slice (rare): device memory
+      // the partner of each unit (the fwd unit right upstream of it): entry lo - 1 of the slice
+      u32 pf[4], F[4];
+      bool below[4];     // the answer lies below the window (rare)
+      bool far = false;  // ... of one of the lane's units
 #pragma unroll
-      for (u32 j = 0; j < 2; ++j) {
-        u32 l = lo[j];
-        if (l == STAGE_CAP - 1 && st_last < R[j]) l = STAGE_CAP;
-        pf[j] = umin(w0 + l, n);
-        // every staged position is at or above R and the slice does not start at rank 0: fwd units
-        // before the slice may be at or above R too.  (The other end cannot be exceeded: pf <= k.)
-        beyond = beyond || (act[j] && ((l == 0 && w0 > 0) || (l == STAGE_CAP && w0 + STAGE_CAP < n)));
-      }
-      if (wave::any(beyond)) {
-#pragma unroll
-        for (u32 j = 0; j < 2; ++j) {
-          const u32 l = pf[j] - w0;
-          if (act[j] && ((l == 0 && w0 > 0) || (l == STAGE_CAP && w0 + STAGE_CAP < n)))
-            pf[j] = lower_bound_u32(ws.f_pos, n, R[j]);
-          wave::pin(pf[j]);  // (the loads of this rare path end here)
-        }
-      }
-      // the partner of each unit (the fwd unit right upstream of it): its position from the slice,
-      // without branches; partners beyond the slice come from device memory
-      u32 F[2];
-      bool has[2], staged[2];
-#pragma unroll
-      for (u32 j = 0; j < 2; ++j) {
-        has[j] = act[j] && pf[j] >= 1 && pf[j] < i2;
-        const u32 kf = pf[j] - 1;
-        staged[j] = has[j] && kf >= w0 && kf - w0 < STAGE_CAP;
-        F[j] = stage[staged[j] ? kf - w0 : 0u];
-      }
+      for (u32 j = 0; j < 4; ++j) F[j] = sl[lo[j] - 1];
       wave::sched_fence();
-      if (wave::any((has[0] && !staged[0]) || (has[1] && !staged[1]))) {
 #pragma unroll
-        for (u32 j = 0; j < 2; ++j) {
-          if (has[j] && !staged[j]) F[j] = ws.f_pos[pf[j] - 1];
-          // (the load ends HERE: where a value loaded on a rare path merges with the common path
-          // the compiler waits for everything in flight -- the next block's loads -- on both)
+      for (u32 j = 0; j < 4; ++j) {
+        // the search stayed at the window's start and the entry there is not below R: the answer is at or
+        // below the start.  At the start of a slice that begins with rank 0 that IS the answer (pf = 0);
+        // everywhere else the entries in front of the window decide
+        const bool edge = lo[j] == es[j] + 1 && F[j] >= R[j];
+        pf[j] = w0 + lo[j] - (edge ? 1u : 0u);
+        below[j] = act[j] && edge && (es[j] != 0 || w0 != 0);
+        far = far || below[j];
+      }
+#ifdef MODLE_COUNT_PRIMARY_FAR  // (measurement: units that search the rest of the slice in slot 14 -- set against the rev units of
+                                // the launch, the bench line's lef_epochs_per_gpu_step --, units looked up in device memory in slot 15)
+      u32 n_dev = 0;
+#pragma unroll
+      for (u32 j = 0; j < 4; ++j) c.ph[14] += static_cast<u32>(wave::popc64(wave::ballot(below[j])));
+#endif
+      if (wave::any(far)) {
+#pragma unroll
+        for (u32 j = 0; j < 4; ++j) {
+          if (below[j]) {
+            u32 l = 0, h = es[j];  // the answer is in [0, es[j]]
+            while (l < h) {
+              const u32 mid = (l + h) >> 1;
+              if (sl[mid] < R[j]) l = mid + 1;
+              else h = mid;
+            }
+            pf[j] = w0 + l;
+            if (l != 0) {
+              F[j] = sl[l - 1];
+            } else if (w0 > 0) {
+              // every staged position is at or above R and the slice does not start at rank 0: fwd
+              // units before the slice may be at or above R too
+              pf[j] = lower_bound_u32(ws.f_pos, n, R[j]);
+              if (pf[j] >= 1) F[j] = ws.f_pos[pf[j] - 1];
+#ifdef MODLE_COUNT_PRIMARY_FAR
+              n_dev |= 1u << j;
+#endif
+#ifdef MODLE_EMU_TRACE_PRIMARY  // (emulator only: which search a test exercises)
+              fprintf(stderr, "detect_primary: rank %u device memory\n", k0 + j);
+#endif
+            }
+#ifdef MODLE_EMU_TRACE_PRIMARY
+            fprintf(stderr, "detect_primary: rank %u rest of the slice\n", k0 + j);
+#endif
+          }
+          // (the loads of this rare path end HERE: where a value loaded on a rare path merges with the
+          // common path the compiler waits for everything in flight -- the next block's loads -- on both)
+          wave::pin(pf[j]);
           wave::pin(F[j]);
         }
-      }
-      bool cand[2];
+#ifdef MODLE_COUNT_PRIMARY_FAR
 #pragma unroll
-      for (u32 j = 0; j < 2; ++j) {
-        const u32 Rprev = j == 0 ? Rprev0 : R[0];
-        const bool first_after = (k[j] == first) || Rprev <= F[j];
+        for (u32 j = 0; j < 4; ++j) c.ph[15] += static_cast<u32>(wave::popc64(wave::ballot(((n_dev >> j) & 1u) != 0)));
+#endif
+      }
+      bool cand[4];
+      u32 lane_cnt = 0;
+#pragma unroll
+      for (u32 j = 0; j < 4; ++j) {
+        const bool has = act[j] && pf[j] >= 1 && pf[j] < i2;
+        const u32 Rprev = j == 0 ? Rprev0 : R[j - 1];
+        const bool first_after = (k0 + j == first) || Rprev <= F[j];
         const u32 delta = R[j] - F[j];  // > 0 by construction (where it is used)
-        cand[j] = has[j] && first_after && static_cast<u64>(delta) < static_cast<u64>(rev_move[j]) + fwd_reach;
+        cand[j] = has && first_after && static_cast<u64>(delta) < static_cast<u64>(rev_move[j]) + fwd_reach;
+        lane_cnt += cand[j] ? 1u : 0u;
       }
-      const u64 cm0 = wave::ballot(cand[0]), cm1 = wave::ballot(cand[1]);
-      {
-        // rank order: unit (lane, j) after the units of the lanes before it and after unit 0 of its
-        // own lane
-        const u64 lt = lanemask_lt(lane);
-        const u32 e0 = n_cand + static_cast<u32>(wave::popc64(cm0 & lt) + wave::popc64(cm1 & lt));
-        const u32 e1 = e0 + (cand[0] ? 1u : 0u);
-        *(cand[0] ? &q_k[e0] : dump) = k[0];
-        *(cand[0] ? &q_pf[e0] : dump + 1) = pf[0];
-        *(cand[1] ? &q_k[e1] : dump) = k[1];
-        *(cand[1] ? &q_pf[e1] : dump + 1) = pf[1];
+      // rank order: the units of the lanes before this one, then its own in turn
+      const u32 ps = wave_prefix_sum_u32(lane_cnt);
+      u32 e = n_cand + ps - lane_cnt;
+#pragma unroll
+      for (u32 j = 0; j < 4; ++j) {
+        *(cand[j] ? &q_k[e] : dump) = k0 + j;
+        *(cand[j] ? &q_pf[e] : dump + 1) = pf[j];
+        e += cand[j] ? 1u : 0u;
       }
-      n_cand += static_cast<u32>(wave::popc64(cm0) + wave::popc64(cm1));
-      carry_pos = wave::bcast(R[1], 63);
-    };
-    for (u32 base = b0; base < n; base += 256) {
-      block(pa, base);
-      if (base + 128 < n) block(pb, base + 128);
+      n_cand += wave::bcast(ps, 63);
+      carry_pos = wave::bcast(R[3], 63);
     }
   }
   wave::sync_mem();
+#ifdef MODLE_SUBTIMER_PRIMARY
+  const u64 t_pass2 = wave::clock();
+  c.ph[14] += t_pass2 - t_pass1;  // (pass 1: partners and the candidate list)
+#endif
   // ---- pass 2 ----------------------------------------------------------------------------------
   struct PairRegs {
     u32 k, pf, R, rev_move, rev_id, rc, rbp, F, fwd_move, fwd_id, fc, fbp;
@@ -1428,6 +1458,9 @@ MODLE_DEV_NOINLINE void detect_primary(Cell& c, BoundaryCounts bc, bool fuse_cor
     }
   }
   wave::sync_mem();
+#ifdef MODLE_SUBTIMER_PRIMARY
+  c.ph[15] += wave::clock() - t_pass2;  // (pass 2: the listed pairs)
+#endif
 }
 
 // correct_moves_for_primary_lef_lef_collisions (reference: simulation_correct_moves.cpp:53-121)

@@ -272,7 +272,11 @@ MODLE_DEV u32 simulate_cell(const Params& p, const Interval& iv, const Task& tas
             c.n_bound = c.n_active;
           });
     if (stats_due) {
+#ifdef MODLE_SUBTIMER_BURNIN  // (slot 14: the statistics and the push, slot 15: the stability test)
+      PHASE(c, 0, PHASE(c, 14, compute_loop_size_stats(c)); PHASE(c, 15, burnin_completed = evaluate_burnin(c)));
+#else
       PHASE(c, 0, compute_loop_size_stats(c); burnin_completed = evaluate_burnin(c));
+#endif
       burnin_completed = burnin_completed && epoch > p.min_burnin_epochs;
       if (!burnin_completed && epoch >= p.max_burnin_epochs) {
         burnin_completed = true;
