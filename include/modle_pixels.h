@@ -1,6 +1,6 @@
 /* modle_pixels.h -- C ABI of the sparse-pixel extraction (modle_amd/libmodle_pixels.so), of the
- * coarsening of a band, of its dense regions, of its marginals, of its insulation sums and of its
- * dot candidates (further down).
+ * coarsening of a band, of its dense regions, of its marginals, of its insulation sums, of its
+ * dot candidates and of its pileups (further down).
  *
  * The simulation leaves every interval as a dense band matrix in device memory
  * (modle_hip_interval_outputs).  A cooler file is made of the non-zero pixels only, sorted by
@@ -315,6 +315,62 @@ int modle_pixels_coarse_dots_to_host(modle_pixels_handle* h, const uint32_t* d_b
                                      const int64_t** bin2, const int32_t** count,
                                      const int64_t** bin1_offset, modle_pixels_stats* stats,
                                      void* stream, char* err, size_t errlen);
+
+/* ---- Pileups: windows around anchor pairs, summed ------------------------------------------------
+ *
+ * M(x, y) is the symmetric matrix of the band: M(x, y) = band[j * nrows + (j - i)], i = min(x, y),
+ * j = max(x, y).  For a flank `f`, S = 2 f + 1, 0 <= f <= MODLE_PIXELS_MAX_PILEUP_FLANK, and `n` anchors
+ * (a_t, b_t) = (bin1[t] - bin_offset, bin2[t] - bin_offset) from int64 arrays (modle_pixels_extract's or
+ * a dot caller's output feeds in as it is), anchor t is ACCEPTED when
+ *     a_t <= b_t,   a_t >= f,   b_t + f <= ncols - 1,   (b_t - a_t) + 2 f <= nrows - 1:
+ * every cell of its window lies in the matrix and in the band, so no word that is no pixel (left-edge
+ * triangle, trailing word) is ever read.  The rule is evaluated without signed overflow for any int64
+ * value and a `bin_offset` of either sign.  a == b is a legitimate anchor, an on-diagonal pileup: its
+ * window crosses the diagonal and is read through the symmetry.  The outputs are
+ *     pile[r][c] = sum over the accepted t of M(a_t - f + r, b_t - f + c)     uint64[S][S], row-major
+ *     n_used     = the number of accepted anchors                             uint64[1]
+ * (APA, `cooltools pileup`: the average loop; with a == b the average barrier).  Duplicates count as often
+ * as they are listed, the order of the anchors is free, and n == 0 or no accepted anchor gives zeros.
+ * EVERY output word is written exactly once, with a plain store: the caller does not pre-zero.  The sums
+ * are exact 64-bit integers, whatever the order of summation: n < 2^31 words below 2^32 cannot overflow.
+ * The anchors are spread over at most MODLE_PIXELS_PILEUP_GROUPS workgroups, whose partial sums meet in
+ * scratch of the context (grown on demand).
+ *
+ * MODLE_PIXELS_ERR_ARG, with nothing written: a null handle or band, null anchors with n > 0, f > 32,
+ * 2 f + 1 > nrows, nrows == 0, nrows > ncols, n >= 2^31, an output that is not 8-byte aligned or overlaps
+ * the band, the anchors or the other output. */
+#define MODLE_PIXELS_MAX_PILEUP_FLANK 32
+#define MODLE_PIXELS_PILEUP_GROUPS 256
+
+/* accept[t] = 1 when anchor t is accepted, else 0: the rule above on HOST arrays.  Host only: no device
+ * is needed.  The shapes and flanks modle_pixels_pileup refuses, and a null pointer with n > 0, are
+ * MODLE_PIXELS_ERR_ARG. */
+int modle_pixels_pileup_accepts(uint64_t nrows, uint64_t ncols, uint64_t flank, int64_t bin_offset,
+                                const int64_t* bin1, const int64_t* bin2, uint64_t n, uint8_t* accept);
+
+/* Enqueues the sums of the DEVICE anchors d_bin1, d_bin2 (int64[n]) into the device arrays d_pile
+ * (uint64[S * S]) and d_n_used (uint64[1]; may be NULL) on `stream`; the call does not wait. */
+int modle_pixels_pileup(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols,
+                        uint64_t flank, int64_t bin_offset, const int64_t* d_bin1, const int64_t* d_bin2,
+                        uint64_t n, uint64_t* d_pile, uint64_t* d_n_used, void* stream, char* err,
+                        size_t errlen);
+
+/* The same for HOST anchors, which are copied up, into pinned host buffers of the context (grown on
+ * demand, freed by modle_pixels_destroy): *pile (S * S entries) and *n_used (one) stay valid until the
+ * next call on the context.  Waits for `stream`. */
+int modle_pixels_pileup_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                                uint64_t ncols, uint64_t flank, int64_t bin_offset, const int64_t* bin1,
+                                const int64_t* bin2, uint64_t n, const uint64_t** pile,
+                                const uint64_t** n_used, void* stream, char* err, size_t errlen);
+
+/* One call at `factor` times the bin size: coarsens into the scratch band of the context (like
+ * modle_pixels_coarse_dots_to_host), then modle_pixels_pileup_to_host on it.  `flank` and the anchors
+ * count coarse bins, and the acceptance rule holds against nrows' / ncols' (modle_pixels_coarse_shape). */
+int modle_pixels_coarse_pileup_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                                       uint64_t ncols, uint64_t factor, uint64_t first_bin, uint64_t flank,
+                                       int64_t bin_offset, const int64_t* bin1, const int64_t* bin2,
+                                       uint64_t n, const uint64_t** pile, const uint64_t** n_used,
+                                       void* stream, char* err, size_t errlen);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,7 @@ the reference: `Config` (simulation_config.hpp), `Task` / `State` results (simul
 `run_simulate`'s task generation (scheduler_simulate.cpp:104-160).
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -189,6 +190,61 @@ def cluster_dots(bin1, bin2, count, radius):
         beats = (oc > sc[n]) | ((oc == sc[n]) & ((o1 < s1[n]) | ((o1 == s1[n]) & (o2 < s2[n]))))
         keep[n] = not bool((near & beats).any())
     return np.sort(order[keep])
+
+
+def pileup_expected_terms(dist_hist, diag_sum, ncols, flank):
+    """The terms of pileup_expected: a list of S * S lists (cell (r, c) at r * S + c), each holding
+    float(dist_hist[d]) * E[abs(d + c - r)] for the d with dist_hist[d] != 0, ascending in d, with
+    E[d] = float(diag_sum[d]) / float(ncols - d)."""
+    hist = [int(x) for x in np.asarray(dist_hist).reshape(-1)]
+    diag = [int(x) for x in np.asarray(diag_sum).reshape(-1)]
+    f, ncols = int(flank), int(ncols)
+    if f < 0 or len(hist) > len(diag) or ncols < len(diag):
+        raise ValueError(f"pileup_expected: flank {f}, {len(hist)} distances, {len(diag)} diagonals, {ncols} columns")
+    used = [d for d, k in enumerate(hist) if k != 0]
+    if used and used[-1] + 2 * f >= len(diag):
+        raise ValueError(f"pileup_expected: distance {used[-1]} with a flank of {f} leaves the {len(diag)} diagonals")
+    e = [float(s) / float(ncols - d) for d, s in enumerate(diag)]
+    s = 2 * f + 1
+    return [[float(hist[d]) * e[abs(d + c - r)] for d in used] for r in range(s) for c in range(s)]
+
+
+def pileup_expected(dist_hist, diag_sum, ncols, flank):
+    """What the distance-decay curve of the interval expects a pileup (Simulator.pileup) to hold, numpy
+    float64 [S, S], S = 2 * flank + 1: with E[d] = float(diag_sum[d]) / float(ncols - d) (one division),
+    cell (r, c) is math.fsum of float(dist_hist[d]) * E[abs(d + c - r)] over the d with dist_hist[d] != 0.
+    fsum is correctly rounded, so the result does not depend on the order of the terms."""
+    s = 2 * int(flank) + 1
+    terms = pileup_expected_terms(dist_hist, diag_sum, ncols, flank)
+    return np.array([math.fsum(t) for t in terms], dtype=np.float64).reshape(s, s)
+
+
+def apa_scores(pile, corner):
+    """The aggregate-peak-analysis scores of a pileup [S, S], S = 2 f + 1, as a dict of floats: `peak`, the
+    centre cell; `p2ll`, `p2ul`, `p2ur`, `p2lr`, the centre over the mean of the corner x corner block in
+    the lower-left (rows S - corner .., columns .. corner - 1: the corner nearest the diagonal), upper-left,
+    upper-right and lower-right corner, nan where that mean is 0; `z_ll`, the centre minus the mean of
+    the lower-left block over its population standard deviation, nan where that is 0.  Every cell is
+    turned into a float first; a mean is math.fsum of the block over corner^2, the variance math.fsum
+    of the squared differences from the mean over corner^2.  1 <= corner <= f."""
+    p = np.asarray(pile)
+    if p.ndim != 2 or p.shape[0] != p.shape[1] or p.shape[0] % 2 != 1:
+        raise ValueError(f"apa_scores: a pile of shape {p.shape} is not [2 f + 1, 2 f + 1]")
+    s, corner = p.shape[0], int(corner)
+    f = s // 2
+    if not 1 <= corner <= f:
+        raise ValueError(f"apa_scores: the corner {corner} is not in [1, flank {f}]")
+    peak = float(p[f, f])
+    lo, hi = slice(0, corner), slice(s - corner, s)
+    out = {"peak": peak}
+    for name, rows, cols in (("p2ll", hi, lo), ("p2ul", lo, lo), ("p2ur", lo, hi), ("p2lr", hi, hi)):
+        block = [float(x) for x in p[rows, cols].reshape(-1)]
+        mean = math.fsum(block) / float(corner * corner)
+        out[name] = peak / mean if mean != 0.0 else math.nan
+        if name == "p2ll":
+            sd = math.sqrt(math.fsum((x - mean) * (x - mean) for x in block) / float(corner * corner))
+            out["z_ll"] = (peak - mean) / sd if sd != 0.0 else math.nan
+    return out
 
 
 # ---------------------------------------------------------------------------------------------
@@ -550,6 +606,60 @@ class Simulator:
         if keep is not None:  # the scratch band goes when this returns
             torch.cuda.synchronize(out.device)
         return out
+
+    def pileup(self, interval_id, bin1, bin2, flank, factor=1, first_bin=0, bin_offset=0):
+        """The pileup of the interval around the anchors (bin1[t] - bin_offset, bin2[t] - bin_offset):
+        (pile, n_used, dist_hist).  pile, numpy uint64 [S, S] with S = 2 * flank + 1, is the sum of the
+        windows of the symmetric matrix around the accepted anchors (a, b) -- those with a <= b whose
+        window lies in the matrix and in the band (pixels.pileup_accepts) --, pile[r][c] the sum of
+        M(a - flank + r, b - flank + c), formed on the device from the band where it lies
+        (pixels.pileup); n_used is their number and dist_hist[d], numpy uint64 [nrows], the number of
+        them with b - a == d, which pileup_expected() wants.  a == b piles windows on the diagonal.
+        Only the anchors and the pile cross between host and device.  Call it after wait().  With
+        `factor` > 1 the band is first coarsened on the device (`first_bin` as for pixels()) and
+        `flank` and the anchors count coarse bins."""
+        from . import pixels
+
+        d_band, _, nrows, ncols = self.outputs(interval_id)
+        if int(factor) == 1:
+            nr, nc = nrows, ncols
+            pile, n_used = pixels.pileup(d_band, nrows, ncols, flank, bin1, bin2, bin_offset, device=self.device)
+        else:
+            nr, nc = pixels.coarse_shape(nrows, ncols, factor, first_bin)
+            pile, n_used = pixels.coarse_pileup(d_band, nrows, ncols, factor, first_bin, flank, bin1, bin2,
+                                                bin_offset, device=self.device)
+        b1 = np.asarray(bin1, dtype=np.int64).reshape(-1)
+        b2 = np.asarray(bin2, dtype=np.int64).reshape(-1)
+        ok = pixels.pileup_accepts(nr, nc, flank, b1, b2, bin_offset)
+        dist_hist = np.bincount(b2[ok] - b1[ok], minlength=nr).astype(np.uint64)
+        return pile, n_used, dist_hist
+
+    def pileup_tensors(self, interval_id, bin1, bin2, flank, bin_offset=0, stream=None):
+        """(pile, n_used) of pileup() for anchors that are torch int64 tensors on the simulator's
+        device, as two torch int64 tensors, [S, S] and [1], on that device, filled there by the
+        kernels: nothing crosses to the host, so dots_tensors() feeds in as it is.  The words hold the
+        uint64 sums bit for bit.  The work is enqueued on `stream` (None: the default stream, on which
+        torch orders its own work) and not waited for."""
+        import torch
+
+        from . import pixels
+
+        d_band, _, nrows, ncols = self.outputs(interval_id)
+        dev = torch.device("cuda", self.device)
+        for t in (bin1, bin2):
+            if t.dtype != torch.int64 or t.device != dev or t.dim() != 1:
+                raise ValueError("pileup_tensors: the anchors must be one-dimensional int64 tensors on the "
+                                 "simulator's device")
+        if bin1.numel() != bin2.numel():
+            raise ValueError(f"pileup_tensors: {bin1.numel()} first and {bin2.numel()} second anchors")
+        bin1, bin2 = bin1.contiguous(), bin2.contiguous()
+        s = 2 * int(flank) + 1
+        pile = torch.empty((s, s), dtype=torch.int64, device=dev)
+        n_used = torch.empty(1, dtype=torch.int64, device=dev)
+        n = bin1.numel()
+        pixels.pileup_into(d_band, nrows, ncols, flank, bin1.data_ptr() if n else None, bin2.data_ptr() if n else None,
+                           n, pile.data_ptr(), n_used.data_ptr(), bin_offset, stream, device=self.device)
+        return pile, n_used
 
     def simulate_interval(self, start, end, bar_pos, bar_dir, stp_active, stp_inactive, tasks):
         """One-call seam (modle_hip_simulate_interval): returns contacts, missed, occupancy,

@@ -12,7 +12,8 @@ square matrices of the named regions, unpacked on the GPU; with --expected `<pre
 contacts per diagonal, and with --coverage `<prefix>_coverage.bedgraph`, the contacts per bin, both
 summed on the GPU; with --insulation-windows `<prefix>_insulation.tsv`, the insulation sums and scores
 per bin over sliding diamond windows, summed on the GPU; with --dots `<prefix>_dots.bedpe`, the pixels
-enriched over their four HiCCUPS neighbourhoods, found on the GPU.  Everything heavy is native: parsing and
+enriched over their four HiCCUPS neighbourhoods, found on the GPU; with --pileup-at `<prefix>_pileup.tsv`,
+the windows around the dots, the barriers or the pairs of a BEDPE file, summed on the GPU.  Everything heavy is native: parsing and
 task generation in libmodle_hip.so (host), the simulation on the MI355X (one process per GPU;
 under torch.distributed.run the cells are sharded over the ranks and the matrices are summed
 with RCCL, or with --dist-backend gloo on host copies), the writers in libmodle_cooler.so.  `-t/--threads` is accepted and ignored."""
@@ -102,6 +103,7 @@ def window_list(text):
 
 
 MAX_DOT_WINDOW_BINS = 20  # include/modle_pixels.h
+MAX_PILEUP_FLANK_BINS = 32  # include/modle_pixels.h
 DOT_FOLDS = (1.75, 1.75, 1.5, 1.5)  # HiCCUPS': donut, lower-left, horizontal, vertical
 
 
@@ -161,6 +163,10 @@ def insulation_path(prefix):
 
 def dots_path(prefix):
     return prefix + "_dots.bedpe"
+
+
+def pileup_path(prefix):
+    return prefix + "_pileup.tsv"
 
 
 def build_parser():
@@ -231,6 +237,24 @@ def build_parser():
                     help="with --dots: a candidate is dropped when a better one lies within this distance on "
                          "both axes (a multiple of the dots resolution; 0 keeps all; default 20kb, rounded down "
                          "to whole bins, at least one bin)")
+    io.add_argument("--pileup-at", action="append", default=None, metavar="WHAT",
+                    help="also write <prefix>_pileup.tsv: the windows of the symmetric matrix around a list of "
+                         "anchor pairs, summed on the GPU into one observed pile, with the pile the interval's "
+                         "distance-decay curve expects and the APA scores.  WHAT is `dots` (the run's own dots: "
+                         "needs --dots at the pileup resolution), `barriers` (every barrier, on the diagonal) or "
+                         "the path of a BEDPE file (cis pairs, placed by the midpoints of their sides); may be "
+                         "given several times")
+    io.add_argument("--pileup-flank", type=genomic_distance, default=None, metavar="SIZE",
+                    help="with --pileup-at: the window reaches SIZE to every side of an anchor (a positive "
+                         "multiple of the pileup resolution, at most 32 bins; 2 f + 1 diagonals must fit -w; "
+                         "default 10 bins)")
+    io.add_argument("--pileup-resolution", type=genomic_distance, default=None, metavar="R",
+                    help="with --pileup-at: the bin size of the pileup (a multiple of -r, coarsened on the GPU; "
+                         "default -r)")
+    io.add_argument("--pileup-corner", type=genomic_distance, default=None, metavar="SIZE",
+                    help="with --pileup-at: the side of the corner blocks of the APA scores (a positive multiple "
+                         "of the pileup resolution, at most the flank; default a third of the flank's bins, at "
+                         "least one)")
     io.add_argument("--log-model-internal-state", action="store_true",
                     help="write <prefix>_internal_state.log.gz: one line of statistics per task and "
                          "epoch (uses the diagnostic build libmodle_hip_statelog.so)")
@@ -361,9 +385,46 @@ Insulation = collections.namedtuple("Insulation", "path resolution windows min_d
 # what --dots asks for: the file (None with --skip-output), the bin size, window, peak and cluster radius
 # in base pairs, the smallest count, the four folds and the diagonals no window may reach below
 Dots = collections.namedtuple("Dots", "path resolution window peak min_count folds min_diag radius")
-# (`insulation` and `dots` came later: at the end, and None unless asked for)
-Preflight = collections.namedtuple("Preflight", "bin_sizes outputs rank world device insulation dots",
-                                   defaults=(None, None))
+# what --pileup-at asks for: the file (None with --skip-output), the bin size, the flank and the corner of
+# the APA scores in base pairs, and the sources in the order given (`dots`, `barriers` or a BEDPE path)
+Pileup = collections.namedtuple("Pileup", "path resolution flank corner sources")
+# (`insulation`, `dots` and `pileup` came later: at the end, and None unless asked for)
+Preflight = collections.namedtuple("Preflight", "bin_sizes outputs rank world device insulation dots pileup",
+                                   defaults=(None, None, None))
+
+
+def pileup_options(a, cfg, dots):
+    """The pileups the arguments ask for, as a Pileup without a path, or None.  `dots`: what dots_options
+    returned.  SystemExit: a --pileup-* option without --pileup-at, a resolution that is no multiple of
+    -r, a flank or corner that is no positive multiple of the pileup resolution, a flank above 32 bins, a
+    corner above the flank, the source `dots` without --dots or at another resolution than the dots'."""
+    if not a.pileup_at:
+        for name, v in (("--pileup-flank", a.pileup_flank), ("--pileup-resolution", a.pileup_resolution),
+                        ("--pileup-corner", a.pileup_corner)):
+            if v is not None:
+                raise SystemExit(f"{name} needs --pileup-at")
+        return None
+    base = int(cfg.bin_size)
+    res = base if a.pileup_resolution is None else int(a.pileup_resolution)
+    if res < base or res % base != 0:
+        raise SystemExit(f"--pileup-resolution: {res} is not a multiple of the resolution ({base})")
+    flank = 10 * res if a.pileup_flank is None else int(a.pileup_flank)
+    if flank < res or flank % res != 0:
+        raise SystemExit(f"--pileup-flank: {flank} is not a positive multiple of the pileup resolution ({res})")
+    if flank // res > MAX_PILEUP_FLANK_BINS:
+        raise SystemExit(f"--pileup-flank: {flank} is {flank // res} bins of {res}: at most {MAX_PILEUP_FLANK_BINS}")
+    corner = max(1, flank // res // 3) * res if a.pileup_corner is None else int(a.pileup_corner)
+    if corner < res or corner % res != 0:
+        raise SystemExit(f"--pileup-corner: {corner} is not a positive multiple of the pileup resolution ({res})")
+    if corner > flank:
+        raise SystemExit(f"--pileup-corner: {corner} is above the flank ({flank})")
+    if "dots" in a.pileup_at:
+        if dots is None:
+            raise SystemExit("--pileup-at dots needs --dots")
+        if int(dots.resolution) != res:
+            raise SystemExit(f"--pileup-at dots: the pileup resolution ({res}) is not the dots resolution "
+                             f"({int(dots.resolution)})")
+    return Pileup(None, res, flank, corner, list(a.pileup_at))
 
 
 def dots_options(a, cfg):
@@ -436,8 +497,9 @@ def insulation_options(a, cfg):
 def preflight(a, cfg):
     """What the arguments alone settle and refuse, without a genome or a GPU.  SystemExit: a bad
     --mcool-resolutions list; --coverage-ignore-diags without --coverage, or negative; what
-    insulation_options and dots_options refuse; on rank 0, an output that exists without --force (cooler
-    or .mcool, then bigwig, then .npz, then the expected, the coverage, the insulation and the dots file).  With
+    insulation_options, dots_options and pileup_options refuse; on rank 0, an output that exists without
+    --force (cooler or .mcool, then bigwig, then .npz, then the expected, the coverage, the insulation, the
+    dots and the pileup file).  With
     --skip-output no file is planned and none is looked at."""
     if a.coverage_ignore_diags is not None:
         if not a.coverage:
@@ -446,13 +508,14 @@ def preflight(a, cfg):
             raise SystemExit(f"--coverage-ignore-diags: {a.coverage_ignore_diags} is negative")
     ins = insulation_options(a, cfg)
     dots = dots_options(a, cfg)
+    pile = pileup_options(a, cfg, dots)
     # (a bad list ends the run here, before anything is imported or simulated)
     bin_sizes = None if a.mcool_resolutions is None else mcool_bin_sizes(a.mcool_resolutions, cfg.bin_size)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     device = a.device if a.device is not None else int(os.environ.get("LOCAL_RANK", "0"))
     if a.skip_output:
-        return Preflight(bin_sizes, Outputs(None, None, None, None), rank, world, device, ins, dots)
+        return Preflight(bin_sizes, Outputs(None, None, None, None), rank, world, device, ins, dots, pile)
     cool_path, bw_path = output_paths(a.output_prefix, mcool=bin_sizes is not None)
     log_path = state_log_path(a.output_prefix) if world == 1 else \
         f"{a.output_prefix}_internal_state.rank{rank}.log.gz"
@@ -465,13 +528,16 @@ def preflight(a, cfg):
         ins = ins._replace(path=insulation_path(a.output_prefix))
     if dots is not None:
         dots = dots._replace(path=dots_path(a.output_prefix))
+    if pile is not None:
+        pile = pile._replace(path=pileup_path(a.output_prefix))
     if rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(cool_path)), exist_ok=True)
         for p in (outputs.cooler, outputs.bigwig, outputs.dense, outputs.expected, outputs.coverage,
-                  None if ins is None else ins.path, None if dots is None else dots.path):
+                  None if ins is None else ins.path, None if dots is None else dots.path,
+                  None if pile is None else pile.path):
             if p and os.path.exists(p) and not a.force:
                 raise SystemExit(f"refusing to overwrite {p}: pass --force to overwrite")
-    return Preflight(bin_sizes, outputs, rank, world, device, ins, dots)
+    return Preflight(bin_sizes, outputs, rank, world, device, ins, dots, pile)
 
 
 def plan_run(a, cfg, pre, log):
@@ -501,6 +567,14 @@ def plan_run(a, cfg, pre, log):
             raise SystemExit(f"--dots-window: the window of {bad[1]} ({bad[2]} bins of {pre.dots.resolution}) with "
                              f"{pre.dots.min_diag} diagonals ignored does not fit the band of {bad[0]} ({bad[3]} "
                              f"diagonals): {fits}")
+    if pre.pileup is not None and pre.pileup.path is not None:
+        bad = driver.pileup_misfit(plan, int(cfg.bin_size), pre.pileup.resolution, pre.pileup.flank, pre.pileup.sources)
+        if bad is not None and bad[0] == "bedpe":
+            raise SystemExit(f"--pileup-at {bad[1]}: the file cannot be read as BEDPE: {bad[2]}")
+        if bad is not None:
+            raise SystemExit(f"--pileup-flank: the flank of {bad[2]} ({bad[3]} bins of {pre.pileup.resolution}) does "
+                             f"not fit the band of {bad[1]} ({bad[4]} diagonals): the largest flank that fits is "
+                             f"{bad[5]} ({bad[5] // pre.pileup.resolution} bins)")
     regions = driver.dense_regions(plan, int(cfg.bin_size), chroms, a.dense_region) if a.dense_region else []
     return chroms, plan, regions
 
@@ -564,7 +638,8 @@ def simulate(a, log=print):
                           sort_keys=True)
         occupancies = driver.write_outputs(
             sim, cfg, plan, ids, tensors, pre.outputs, pre.bin_sizes, regions, pre.rank, log, a.dist_backend,
-            coverage_min_diag=a.coverage_ignore_diags or 0, insulation=pre.insulation, dots=pre.dots, assembly=a.assembly_name,
+            coverage_min_diag=a.coverage_ignore_diags or 0, insulation=pre.insulation, dots=pre.dots, pileup=pre.pileup,
+            assembly=a.assembly_name,
             generated_by="modle_amd (MI355X)", metadata_json=meta,
             force_overwrite=a.force, chroms=chroms)
     finally:

@@ -11,6 +11,7 @@ the per-rank contact matrices are summed afterwards (`reduce_outputs`).
 `write_outputs` is the front end's output stage after the launch.
 """
 import functools
+import math
 
 import numpy as np
 
@@ -626,6 +627,219 @@ def _interval_dots(sim, plan, ids, w, p, min_count, folds, min_diag, radius, k, 
     return bin1[keep], bin2[keep], count[keep], expected[keep]
 
 
+def read_bedpe(path):
+    """The pairs of a BEDPE file as a list of (chrom1, mid1, chrom2, mid2): the first six columns of every
+    line that is neither empty nor starts with `#`, mid = (start + end) // 2 of each side.  OSError when
+    the file cannot be opened, ValueError, naming the line, for one with fewer than six columns or a
+    coordinate that is no non-negative integer or ends before it starts."""
+    pairs = []
+    with open(path) as fh:
+        for n, line in enumerate(fh, 1):
+            if not line.strip() or line.startswith("#"):
+                continue
+            cols = line.rstrip("\r\n").split("\t")
+            if len(cols) < 6:
+                cols = line.split()
+            try:
+                if len(cols) < 6:
+                    raise ValueError("fewer than six columns")
+                s1, e1, s2, e2 = int(cols[1]), int(cols[2]), int(cols[4]), int(cols[5])
+                if min(s1, s2) < 0 or e1 < s1 or e2 < s2:
+                    raise ValueError("a negative start or an end before its start")
+            except ValueError as e:
+                raise ValueError(f"{path}, line {n}: {e}") from None
+            pairs.append((cols[0], (s1 + e1) // 2, cols[3], (s2 + e2) // 2))
+    return pairs
+
+
+def place_pairs(plan, base, resolution, pairs):
+    """Where the pairs of read_bedpe lie in the plan at the bin size `resolution` (a multiple of `base`):
+    ({k: (a, b)}, trans, outside).  A cis pair goes to the first entry k of the plan that has a matrix, is
+    of its chromosome and contains both midpoints; its columns in that entry's band are mid // resolution
+    - (start // base) // factor, swapped so that a <= b (int64 arrays, in file order).  `trans` counts the
+    pairs of two chromosomes, `outside` the cis pairs that no such entry contains."""
+    base, res = int(base), int(resolution)
+    factor = res // base
+    placed, trans, outside = {}, 0, 0
+    for c1, m1, c2, m2 in pairs:
+        if c1 != c2:
+            trans += 1
+            continue
+        for k, entry in enumerate(plan):
+            iv = entry["interval"]
+            if entry["skipped"] or entry["ncols"] == 0 or iv["name"] != c1:
+                continue
+            if int(iv["start"]) <= min(m1, m2) and max(m1, m2) < int(iv["end"]):
+                first = (int(iv["start"]) // base) // factor
+                a, b = sorted((m1 // res - first, m2 // res - first))
+                placed.setdefault(k, ([], []))
+                placed[k][0].append(a), placed[k][1].append(b)
+                break
+        else:
+            outside += 1
+    return ({k: (np.array(a, dtype=np.int64), np.array(b, dtype=np.int64)) for k, (a, b) in placed.items()},
+            trans, outside)
+
+
+def barrier_anchors(iv, base, resolution):
+    """the on-diagonal anchors of an interval's barriers at the bin size `resolution`: a = b = the column
+    of every barrier in the interval's band, ascending (int64)"""
+    res = int(resolution)
+    first = (int(iv["start"]) // int(base)) // (res // int(base))
+    bins = np.sort(np.asarray(iv["bar_pos"], dtype=np.uint64).astype(np.int64) // res - first)
+    return bins, bins.copy()
+
+
+def pileup_misfit(plan, base, resolution, flank, sources=()):
+    """What refuses a pileup before anything is simulated, or None: ("bedpe", path, why) for the first
+    source (other than `dots` and `barriers`) that read_bedpe cannot read, else ("flank", name of the
+    interval, flank in bp, its bins, diagonals of the band, largest flank in bp that fits) for the first
+    entry of the plan that has a matrix in whose band at `resolution` no window of 2 f + 1 bins fits,
+    2 * f + 1 > nrows'."""
+    for what in sources:
+        if what not in ("dots", "barriers"):
+            try:
+                read_bedpe(what)
+            except (OSError, ValueError) as e:
+                return "bedpe", what, str(e)
+    base, res, f = int(base), int(resolution), int(flank) // int(resolution)
+    for entry in plan:
+        iv = entry["interval"]
+        if entry["skipped"] or entry["ncols"] == 0:
+            continue
+        nr, _ = insulation_shape(entry["nrows"], entry["ncols"], int(iv["start"]) // base, res // base)
+        if 2 * f + 1 > nr:
+            return "flank", interval_name(iv), int(flank), f, nr, (nr - 1) // 2 * res
+    return None
+
+
+def check_pileup(name, source, flank, pile, n_used, dist_hist, max_count, centre=None):
+    """What a pileup of a band (api.Simulator.pileup) must satisfy before a row is written, in exact
+    integers: n_used is the sum of dist_hist; the whole pile is at most n_used * S * S times the largest
+    pixel of the band, `max_count`; and, with `centre` (the on-diagonal anchors of `barriers`: the sum of
+    M(b, b) over the accepted barriers, from the extracted pixels), the centre cell equals it.
+    RuntimeError, naming the interval and the source, when one does not hold."""
+    f = int(flank)
+    s = 2 * f + 1
+    cells = [int(x) for x in np.asarray(pile).reshape(-1)]
+    if len(cells) != s * s:
+        raise RuntimeError(f"{name}: the pileup at {source} has {len(cells)} cells, not {s} x {s}")
+    total = sum(int(x) for x in dist_hist)
+    if int(n_used) != total:
+        raise RuntimeError(f"{name}: the pileup at {source} used {int(n_used)} anchors, their distances count {total}")
+    if sum(cells) > int(n_used) * s * s * int(max_count):
+        raise RuntimeError(f"{name}: the pileup at {source} sums to {sum(cells)}, above {int(n_used)} windows of "
+                           f"{s * s} pixels of at most {int(max_count)}")
+    if centre is not None and cells[f * s + f] != int(centre):
+        raise RuntimeError(f"{name}: the centre of the pileup at {source} is {cells[f * s + f]}, the diagonal "
+                           f"pixels of the used anchors add up to {int(centre)}")
+
+
+PILEUP_SCORES = ("peak", "p2ll", "p2ul", "p2ur", "p2lr", "z_ll")
+
+
+def pileup_header(source, resolution, flank, corner, given, placed, used, scores):
+    """the `#` line in front of a source's block of <prefix>_pileup.tsv: the source, the bin size, the
+    flank and the corner of the scores in base pairs, the anchors given, placed in an interval and used
+    (accepted by the kernel), and the six scores of api.apa_scores on the observed pile, as reprs"""
+    return (f"#source={source}\tresolution={int(resolution)}\tflank={int(flank)}\tcorner={int(corner)}"
+            f"\tgiven={int(given)}\tplaced={int(placed)}\tused={int(used)}" +
+            "".join(f"\t{key}={float(scores[key])!r}" for key in PILEUP_SCORES) + "\n")
+
+
+def pileup_lines(source, resolution, flank, observed, expected):
+    """the rows of a source's block, one per cell, row-major: source, the row's and the column's offset
+    from the anchor in base pairs, the observed sum (an integer) and the repr of the expected one.
+    `observed`, `expected`: S * S values, S = 2 * (flank // resolution) + 1."""
+    res, f = int(resolution), int(flank) // int(resolution)
+    s = 2 * f + 1
+    return [f"{source}\t{(q // s - f) * res}\t{(q % s - f) * res}\t{int(o)}\t{float(e)!r}\n"
+            for q, (o, e) in enumerate(zip(observed, expected))]
+
+
+def write_pileup(path, plan, base, resolution, flank, corner, sources, anchors, pileup, unplaced=None):
+    """<prefix>_pileup.tsv: one block per source of `sources` (names: `dots`, `barriers` or a BEDPE path), in
+    the order given: pileup_header, then pileup_lines, at the bin size `resolution` (a multiple of
+    `base`), `flank` and `corner` in base pairs.  `anchors(name, k, factor, first_bin)` returns the anchors
+    (a, b) of source `name` in plan entry k, columns of its band, or None; `pileup(name, k, factor,
+    first_bin, a, b)` returns (pile, n_used, terms) of them -- what api.Simulator.pileup returns and the
+    terms of api.pileup_expected_terms for its dist_hist -- or None for an entry without a matrix.  The
+    observed pile is the sum over the entries in Python ints, the expected one math.fsum over the entries
+    of the terms.  `unplaced`: {name: the pairs given that lie in no entry}.  Returns [(name, given,
+    placed, used)]."""
+    res, factor = int(resolution), int(resolution) // int(base)
+    s = 2 * (int(flank) // res) + 1
+    done = []
+    with open(path, "w") as fh:
+        for name in sources:
+            observed, terms = [0] * (s * s), [[] for _ in range(s * s)]
+            placed = used = 0
+            for k, entry in enumerate(plan):
+                if entry["skipped"]:
+                    continue
+                first_bin = int(entry["interval"]["start"]) // int(base)
+                ab = anchors(name, k, factor, first_bin)
+                if ab is None:
+                    continue
+                got = pileup(name, k, factor, first_bin, ab[0], ab[1])
+                if got is None:
+                    continue
+                placed += len(ab[0])
+                used += int(got[1])
+                for q, x in enumerate(np.asarray(got[0]).reshape(-1)):
+                    observed[q] += int(x)
+                for q, t in enumerate(got[2]):
+                    terms[q] += list(t)
+            given = placed + int((unplaced or {}).get(name, 0))
+            scores = api.apa_scores(np.array(observed, dtype=np.float64).reshape(s, s), int(corner) // res)
+            fh.write(pileup_header(name, res, flank, corner, given, placed, used, scores))
+            fh.writelines(pileup_lines(name, res, flank, observed, [math.fsum(t) for t in terms]))
+            done.append((name, given, placed, used))
+    return done
+
+
+def _interval_anchors(plan, ids, base, resolution, dots, placed, name, k, factor, first_bin):
+    """write_pileup's first callback: the run's own clustered dots (`dots`: write_dots' callback), the
+    interval's barriers, or the pairs of a BEDPE file that place_pairs put into entry k"""
+    if ids[k] is None:
+        return None
+    if name == "dots":
+        got = dots(k, factor, first_bin)
+        return None if got is None else (np.asarray(got[0], dtype=np.int64), np.asarray(got[1], dtype=np.int64))
+    if name == "barriers":
+        return barrier_anchors(plan[k]["interval"], base, resolution)
+    return placed[name].get(k, (np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)))
+
+
+def _interval_pileup(sim, plan, ids, marginals, cache, flank, name, k, factor, first_bin, a, b):
+    """write_pileup's second callback: summed on the device from the matrix where it lies (with several
+    ranks: the reduced tensor) for `flank` in bins, and verified (check_pileup) against the pixels of the
+    band at that bin size, extracted once per entry (`cache`): their largest count and, for `barriers`,
+    their diagonal.  The terms of the expected pile come from the diagonal sums of the marginals pass
+    (`marginals`: _interval_marginals)."""
+    from . import pixels
+
+    if ids[k] is None:
+        return None
+    entry = plan[k]
+    nr, nc = insulation_shape(entry["nrows"], entry["ncols"], first_bin, factor)
+    pile, n_used, dist_hist = sim.pileup(ids[k], a, b, flank, factor, first_bin)
+    if k not in cache:
+        px = sim.pixels(ids[k], 0, factor=factor, first_bin=first_bin)
+        diagonal = np.zeros(nc, dtype=np.int64)
+        on = px.bin1 == px.bin2
+        diagonal[px.bin1[on]] = px.count[on]
+        cache[k] = (int(px.stats.max_count), diagonal)
+    max_count, diagonal = cache[k]
+    centre = None
+    if name == "barriers":
+        ok = pixels.pileup_accepts(nr, nc, flank, a, b)
+        centre = sum(int(diagonal[x]) for x in np.asarray(a)[ok])
+    check_pileup(interval_name(entry["interval"]), name, flank, pile, n_used, dist_hist, max_count, centre)
+    diag_sum = marginals(k, factor, first_bin)[0]
+    return pile, n_used, api.pileup_expected_terms(dist_hist, diag_sum, nc, flank)
+
+
 def reduce_to_rank0(t, backend, rank):
     """Sum of the ranks' tensors `t` into rank 0's, in place (the other ranks' tensors are unspecified
     afterwards).  `nccl` (= RCCL): on the device tensors.  `gloo`: on host copies -- the rehearsal with
@@ -656,13 +870,14 @@ def reduce_missed(missed, backend, rank, device=None):
 
 
 def write_outputs(sim, cfg, plan, ids, tensors, outputs, bin_sizes=None, regions=(), rank=0, log=print,
-                  backend="nccl", coverage_min_diag=0, insulation=None, dots=None, **attrs):
+                  backend="nccl", coverage_min_diag=0, insulation=None, dots=None, pileup=None, **attrs):
     """What a finished launch writes while the simulator is open: the state log (every rank its
     own), then on rank 0 the cooler or .mcool with the missing-interactions warnings, the dense
     `regions` (of dense_regions), the distance-decay curves (at every bin size of the file) and the
     coverage without the diagonals below `coverage_min_diag`, and the insulation track `insulation` (a
     cli.Insulation: path, resolution, windows in base pairs, min_diag; None or without a path: not
-    written), and the dots `dots` (a cli.Dots; None or without a path: not written).  `outputs.state_log`, `.cooler`, `.dense`,
+    written), and the dots `dots` (a cli.Dots; None or without a path: not written),
+    and the pileups `pileup` (a cli.Pileup; likewise; its source `dots` piles the dots just written).  `outputs.state_log`, `.cooler`, `.dense`,
     `.expected`, `.coverage`: the paths, None for a file that is not written; without a cooler
     (--skip-output) the matrices are only summed, for the warnings.  `tensors`: with several ranks the (contacts, occupancy) torch tensors per plan entry;
     they are reduced in place onto rank 0 (reduce_to_rank0 with `backend`), which extracts from the
@@ -729,13 +944,30 @@ def write_outputs(sim, cfg, plan, ids, tensors, outputs, bin_sizes=None, regions
                          functools.partial(_interval_insulation, sim, plan, ids, bins, int(insulation.min_diag),
                                            marginals))
         log(f"written {insulation.path}")
+    interval_dots = None
     if dots is not None and dots.path is not None:
         res = int(dots.resolution)
-        write_dots(dots.path, plan, int(cfg.bin_size), res,
-                   functools.partial(_interval_dots, sim, plan, ids, int(dots.window) // res, int(dots.peak) // res,
-                                     int(dots.min_count), list(dots.folds), int(dots.min_diag),
-                                     int(dots.radius) // res))
+        # (kept per entry: a pileup at the dots reads them again)
+        interval_dots = functools.lru_cache(maxsize=None)(
+            functools.partial(_interval_dots, sim, plan, ids, int(dots.window) // res, int(dots.peak) // res,
+                              int(dots.min_count), list(dots.folds), int(dots.min_diag), int(dots.radius) // res))
+        write_dots(dots.path, plan, int(cfg.bin_size), res, interval_dots)
         log(f"written {dots.path}")
+    if pileup is not None and pileup.path is not None:
+        base, res = int(cfg.bin_size), int(pileup.resolution)
+        placed, unplaced = {}, {}
+        for what in pileup.sources:
+            if what not in ("dots", "barriers") and what not in placed:
+                placed[what], trans, outside = place_pairs(plan, base, res, read_bedpe(what))
+                unplaced[what] = trans + outside
+                if trans + outside:
+                    log(f"--pileup-at {what}: {trans + outside} pairs are not placed ({trans} between two "
+                        f"chromosomes, {outside} in no simulated interval)")
+        write_pileup(pileup.path, plan, base, res, pileup.flank, pileup.corner, pileup.sources,
+                     functools.partial(_interval_anchors, plan, ids, base, res, interval_dots, placed),
+                     functools.partial(_interval_pileup, sim, plan, ids, marginals, {}, int(pileup.flank) // res),
+                     unplaced)
+        log(f"written {pileup.path}")
     return occupancies
 
 

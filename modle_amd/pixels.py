@@ -2,7 +2,8 @@
 built by `make -C modle_amd/pixels`): the non-zero pixels of a band matrix that lies in device
 memory, in cooler order, found on the GPU; the band at a multiple of its bin size; square regions
 of it as dense matrices; its marginals, the sums per diagonal and per bin; its insulation sums
-over sliding diamond windows; and its dots, the pixels enriched over their HiCCUPS neighbourhoods.
+over sliding diamond windows; its dots, the pixels enriched over their HiCCUPS neighbourhoods; and
+its pileups, the windows around anchor pairs summed into one.
 There is no host fallback: without the library or
 without a device the calls fail."""
 import ctypes as C
@@ -16,6 +17,7 @@ SO_PATH = os.path.join(_HERE, "libmodle_pixels.so")
 ERR_ARG, ERR_DEVICE, ERR_RANGE = -1, -2, -3
 MAX_WINDOW, MAX_WINDOWS = 1024, 8  # MODLE_PIXELS_MAX_WINDOW, MODLE_PIXELS_MAX_WINDOWS
 MAX_DOT_WINDOW = 20  # MODLE_PIXELS_MAX_DOT_WINDOW
+MAX_PILEUP_FLANK, PILEUP_GROUPS = 32, 256  # MODLE_PIXELS_MAX_PILEUP_FLANK, MODLE_PIXELS_PILEUP_GROUPS
 DOT_FOLDS = (1.75, 1.75, 1.5, 1.5)  # HiCCUPS' thresholds: donut, lower-left, horizontal, vertical
 EXPORTS = ["modle_pixels_create", "modle_pixels_destroy", "modle_pixels_count", "modle_pixels_extract",
            "modle_pixels_to_host", "modle_pixels_coarse_shape", "modle_pixels_coarsen",
@@ -23,7 +25,9 @@ EXPORTS = ["modle_pixels_create", "modle_pixels_destroy", "modle_pixels_count", 
            "modle_pixels_dense_to_host", "modle_pixels_marginals", "modle_pixels_marginals_to_host",
            "modle_pixels_coarse_marginals_to_host", "modle_pixels_insulation_n_valid", "modle_pixels_insulation",
            "modle_pixels_insulation_to_host", "modle_pixels_coarse_insulation_to_host", "modle_pixels_dots",
-           "modle_pixels_dots_to_host", "modle_pixels_coarse_dots_to_host"]  # every symbol include/modle_pixels.h declares
+           "modle_pixels_dots_to_host", "modle_pixels_coarse_dots_to_host", "modle_pixels_pileup_accepts",
+           "modle_pixels_pileup", "modle_pixels_pileup_to_host",
+           "modle_pixels_coarse_pileup_to_host"]  # every symbol include/modle_pixels.h declares
 
 _LIB = None
 _EXTRACTORS = {}
@@ -88,6 +92,15 @@ def lib():
         lb.modle_pixels_dots.argtypes = shape + dots + [C.c_void_p, C.c_void_p, C.c_void_p] + err
         lb.modle_pixels_dots_to_host.argtypes = shape + dots + pix
         lb.modle_pixels_coarse_dots_to_host.argtypes = shape + [C.c_uint64] * 2 + dots + pix
+        i64p = C.POINTER(C.c_int64)
+        piled = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p] + err  # pile, n_used, stream
+        lb.modle_pixels_pileup_accepts.argtypes = [C.c_uint64] * 3 + [C.c_int64, i64p, i64p, C.c_uint64,
+                                                                      C.POINTER(C.c_uint8)]
+        lb.modle_pixels_pileup.argtypes = shape + [C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p] + err
+        lb.modle_pixels_pileup_to_host.argtypes = shape + [C.c_uint64, C.c_int64, i64p, i64p, C.c_uint64] + piled
+        lb.modle_pixels_coarse_pileup_to_host.argtypes = shape + [C.c_uint64] * 3 + [C.c_int64, i64p, i64p,
+                                                                                     C.c_uint64] + piled
         for name in EXPORTS:
             getattr(lb, name)  # raises AttributeError if a declared symbol is not exported
         _LIB = lb
@@ -231,6 +244,41 @@ def _scale_table(scale, nrows):
     if t.ndim != 2 or t.shape[0] != 4 or (nrows is not None and t.shape[1] != int(nrows)):
         raise PixelsError(ERR_ARG, f"dots: the scale table has shape {t.shape}, not (4, nrows)")
     return t, t.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _anchors(bin1, bin2):
+    """(the two contiguous int64 arrays to keep alive, their ctypes pointers or None, n) of host anchors"""
+    b1 = np.ascontiguousarray(bin1, dtype=np.int64).reshape(-1)
+    b2 = np.ascontiguousarray(bin2, dtype=np.int64).reshape(-1)
+    if len(b1) != len(b2):
+        raise PixelsError(ERR_ARG, f"pileup: {len(b1)} first and {len(b2)} second anchors")
+    if len(b1) == 0:
+        return (b1, b2), None, None, 0
+    i64p = C.POINTER(C.c_int64)
+    return (b1, b2), b1.ctypes.data_as(i64p), b2.ctypes.data_as(i64p), len(b1)
+
+
+def _flank(flank):
+    if int(flank) < 0:
+        raise PixelsError(ERR_ARG, "pileup: negative flank")
+    return int(flank)
+
+
+def pileup_accepts(nrows, ncols, flank, bin1, bin2, bin_offset=0):
+    """which anchors (bin1[t] - bin_offset, bin2[t] - bin_offset) = (a, b) a pileup of `flank` bins uses,
+    a numpy bool array: a <= b, a >= flank, b + flank <= ncols - 1, (b - a) + 2 * flank <= nrows - 1, for
+    any int64 values (modle_pixels_pileup_accepts; no device is needed)"""
+    if min(int(nrows), int(ncols)) < 0:
+        raise PixelsError(ERR_ARG, "pileup_accepts: negative shape")
+    keep, p1, p2, n = _anchors(bin1, bin2)
+    out = np.zeros(n, dtype=np.uint8)
+    rc = lib().modle_pixels_pileup_accepts(int(nrows), int(ncols), _flank(flank), int(bin_offset), p1, p2, n,
+                                           out.ctypes.data_as(C.POINTER(C.c_uint8)))
+    del keep
+    if rc != 0:
+        raise PixelsError(rc, "pileup_accepts: invalid argument (0 < nrows <= ncols, flank <= 32, "
+                              "2 * flank + 1 <= nrows, n < 2^31)")
+    return out.astype(bool)
 
 
 class Extractor:
@@ -422,6 +470,39 @@ class Extractor:
                              int(factor), int(first_bin), int(w), int(p), int(min_diag), int(min_count), ptr,
                              int(bin_offset), stream=stream)
 
+    def pileup_into(self, d_band, nrows, ncols, flank, d_bin1, d_bin2, n, d_pile, d_n_used=None, bin_offset=0,
+                    stream=None):
+        """enqueues the pileup of the `n` anchors in the device arrays `d_bin1`, `d_bin2` (int64) into the
+        caller-owned device arrays `d_pile` (uint64[2 * flank + 1][2 * flank + 1]) and `d_n_used`
+        (uint64[1], or None), both 8-byte aligned; every word is written (modle_pixels_pileup)"""
+        _call(self._L.modle_pixels_pileup, self._h, d_band, int(nrows), int(ncols), _flank(flank), int(bin_offset),
+              d_bin1, d_bin2, int(n), d_pile, d_n_used, _stream_ptr(stream))
+
+    def _pileup(self, fn, flank, bin1, bin2, bin_offset, *args, stream=None):
+        """a to-host form `fn(handle, *args, flank, bin_offset, anchors, n, two pointers, stream, err)`:
+        (pile as a numpy uint64[S, S] copy, n_used)"""
+        keep, p1, p2, n = _anchors(bin1, bin2)
+        pp, pn = C.c_void_p(), C.c_void_p()
+        _call(fn, self._h, *args, _flank(flank), int(bin_offset), p1, p2, n, C.byref(pp), C.byref(pn),
+              _stream_ptr(stream))
+        del keep
+        s = 2 * int(flank) + 1
+        return _host_array(pp.value, s * s, np.uint64).reshape(s, s), int(_host_array(pn.value, 1, np.uint64)[0])
+
+    def pileup(self, d_band, nrows, ncols, flank, bin1, bin2, bin_offset=0, stream=None):
+        """(pile, n_used): the sum of the (2 * flank + 1)^2 windows of the symmetric matrix around the
+        accepted ones of the host anchors (bin1[t] - bin_offset, bin2[t] - bin_offset), numpy
+        uint64[S, S], and how many were accepted (pileup_accepts), summed on the device
+        (modle_pixels_pileup_to_host)"""
+        return self._pileup(self._L.modle_pixels_pileup_to_host, flank, bin1, bin2, bin_offset, d_band, int(nrows),
+                            int(ncols), stream=stream)
+
+    def coarse_pileup(self, d_band, nrows, ncols, factor, first_bin, flank, bin1, bin2, bin_offset=0, stream=None):
+        """`pileup` of the band at `factor` times its bin size, coarsened on the device
+        (modle_pixels_coarse_pileup_to_host): `flank` and the anchors count coarse bins"""
+        return self._pileup(self._L.modle_pixels_coarse_pileup_to_host, flank, bin1, bin2, bin_offset, d_band,
+                            int(nrows), int(ncols), int(factor), int(first_bin), stream=stream)
+
 
 def extractor(device=0):
     """the process-wide context of `device`"""
@@ -510,3 +591,23 @@ def coarse_dots(d_band, nrows, ncols, factor, first_bin, w, p, min_diag, min_cou
     coarsened and found on the device."""
     return extractor(device).coarse_dots(d_band, nrows, ncols, factor, first_bin, w, p, min_diag, min_count, scale,
                                          bin_offset, stream)
+
+
+def pileup_into(d_band, nrows, ncols, flank, d_bin1, d_bin2, n, d_pile, d_n_used=None, bin_offset=0, stream=None,
+                device=0):
+    """The pileup of the band at device pointer `d_band` around `n` anchors in device arrays, into the
+    device arrays `d_pile` and `d_n_used`; enqueued on `stream`, nothing crosses to the host."""
+    extractor(device).pileup_into(d_band, nrows, ncols, flank, d_bin1, d_bin2, n, d_pile, d_n_used, bin_offset, stream)
+
+
+def pileup(d_band, nrows, ncols, flank, bin1, bin2, bin_offset=0, stream=None, device=0):
+    """(pile, n_used) of the band at device pointer `d_band` around host anchors: numpy uint64[S, S] and
+    an int, summed on the device."""
+    return extractor(device).pileup(d_band, nrows, ncols, flank, bin1, bin2, bin_offset, stream)
+
+
+def coarse_pileup(d_band, nrows, ncols, factor, first_bin, flank, bin1, bin2, bin_offset=0, stream=None, device=0):
+    """(pile, n_used) of the band at device pointer `d_band` at `factor` times its bin size, coarsened
+    and summed on the device."""
+    return extractor(device).coarse_pileup(d_band, nrows, ncols, factor, first_bin, flank, bin1, bin2, bin_offset,
+                                           stream)

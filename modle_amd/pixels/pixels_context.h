@@ -85,6 +85,11 @@ struct modle_pixels_handle {
   GrowBuf<uint32_t> dot_cand;
   GrowBuf<double, true> dot_scale;
   hipEvent_t dot_scale_copied = nullptr;
+  // modle_pixels_pileup*: the workgroups' partial sums (S * S words each, then their counts), and of the
+  // to-host forms the anchors (bin1, then bin2) and the pile with n_used behind it (modle_pileup.hip)
+  GrowBuf<uint64_t> pile_partial;
+  GrowBuf<int64_t> pile_anchors;
+  GrowBuf<uint64_t, true> pile_out;
 };
 
 #endif
