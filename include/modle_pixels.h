@@ -1,6 +1,6 @@
 /* modle_pixels.h -- C ABI of the sparse-pixel extraction (modle_amd/libmodle_pixels.so), of the
  * coarsening of a band, of its dense regions, of its marginals, of its insulation sums, of its
- * dot candidates and of its pileups (further down).
+ * dot candidates, of its pileups and of its random sampling (further down).
  *
  * The simulation leaves every interval as a dense band matrix in device memory
  * (modle_hip_interval_outputs).  A cooler file is made of the non-zero pixels only, sorted by
@@ -371,6 +371,81 @@ int modle_pixels_coarse_pileup_to_host(modle_pixels_handle* h, const uint32_t* d
                                        int64_t bin_offset, const int64_t* bin1, const int64_t* bin2,
                                        uint64_t n, const uint64_t** pile, const uint64_t** n_used,
                                        void* stream, char* err, size_t errlen);
+
+/* ---- Random sampling: binomial thinning of the band -----------------------------------------------
+ *
+ * Every contact of the band is kept with one probability, independently of the others (the default mode
+ * of `cooltools random-sample`): the same matrix at a lower depth, or two disjoint pseudo-replicates.
+ * Which contacts are kept is defined by a counter-based generator keyed by the pixel's coordinates.  A
+ * pixel is (i, j) with the count n = band[j * nrows + (j - i)]; its absolute ids are I = i + bin_offset
+ * and J = j + bin_offset, both in [0, 2^32).  For trial t in [0, n):
+ *     word(t) = philox4x32_10(counter = (I, J, t >> 2, salt), key = (seed & 0xFFFFFFFF, seed >> 32))[t & 3]
+ *     kept    = #{ t < n : word(t) < threshold },   rest = n - kept
+ * (Philox4x32-10 of Salmon et al., SC'11: Random123's and rocRAND's function.)  `threshold` is a uint64
+ * in [0, 2^32]: the probability is threshold / 2^32, 2^32 keeps every contact and 0 keeps none; `seed` is
+ * a uint64 and `salt` a uint32 (another salt: another, independent draw of the same seed).  No float
+ * crosses this interface.  What follows from the definition:
+ *   - kept depends on nothing but (I, J, n, threshold, seed, salt): not on nrows, not on how the genome
+ *     was cut into intervals (give `bin_offset` the interval's first bin in the file), not on the stream
+ *     or the launch;
+ *   - kept at threshold a <= kept at threshold b for a <= b, pixel by pixel: a series of depths is nested;
+ *   - kept + rest == n word for word: the two outputs are disjoint pseudo-replicates;
+ *   - every trial is an independent Bernoulli draw, so kept is Binomial(n, threshold / 2^32) and the total
+ *     is random around its target, not equal to it.  There is no exact-total mode.
+ * The work is one Philox call per four contacts: the cost of a call is proportional to the sum of the
+ * band, and a band of more than MODLE_PIXELS_MAX_SAMPLE_TRIALS contacts is refused: about two seconds of
+ * one MI355X at the 520 G trials/s measured on a band with a distance decay
+ * (profiles/sample/sample_vs_torch.txt) -- a mistaken call must not hold a shared GPU for minutes.  A lane
+ * of the kernel draws the first MODLE_PIXELS_SAMPLE_TIER1_TRIALS trials of its own pixel; what a pixel has
+ * beyond them is drawn by its whole wave, and by that wave alone (1.45 G trials/s: a pixel of 2^32 - 1
+ * contacts takes three seconds whatever the sum).
+ *
+ * The outputs d_kept and d_rest are uint32[nrows * ncols + 1] in the band's layout; either may be NULL,
+ * not both.  EVERY word of an output that is given is written exactly once, with a plain store: pixels
+ * hold their counts, the words that are no pixels (left-edge triangle, trailing word) hold 0; the caller
+ * does not pre-zero.  The words of the band that are no pixels are never read.
+ *
+ * There is no coarse form: a sampled band is a band in device memory, which modle_pixels_coarsen and every
+ * other call of this header take as it is.  Sample at the base bin size and coarsen the result -- then the
+ * levels of a sampled .mcool agree with each other, which sampling every level on its own would not give.
+ *
+ * MODLE_PIXELS_ERR_ARG, with nothing written: a null handle, band or stats, both outputs null, threshold >
+ * 2^32, nrows == 0, nrows > ncols, an output that overlaps the band or the other output.
+ * MODLE_PIXELS_ERR_RANGE, with nothing written: bin_offset < 0 or bin_offset + ncols > 2^32; a sum above
+ * MODLE_PIXELS_MAX_SAMPLE_TRIALS. */
+#define MODLE_PIXELS_SAMPLE_TIER1_TRIALS 64
+#define MODLE_PIXELS_MAX_SAMPLE_TRIALS (1ull << 40)
+#define MODLE_PIXELS_SAMPLE_KEPT 0
+#define MODLE_PIXELS_SAMPLE_REST 1
+
+/* kept[t] of the `n` pixels (bin1[t] + bin_offset, bin2[t] + bin_offset) with count[t] trials: the
+ * definition above on HOST arrays, compiled from the same Philox function as the kernel.  Host only: no
+ * device is needed.  threshold > 2^32 and a null pointer with n > 0 are MODLE_PIXELS_ERR_ARG, an id outside
+ * [0, 2^32) is MODLE_PIXELS_ERR_RANGE; nothing is written then. */
+int modle_pixels_sample_pixels(uint64_t seed, uint32_t salt, uint64_t threshold, int64_t bin_offset,
+                               const int64_t* bin1, const int64_t* bin2, const uint32_t* count, uint64_t n,
+                               uint32_t* kept);
+
+/* Enqueues the sampling of the band into the device arrays d_kept and / or d_rest on `stream`; the call
+ * does not wait.  `stats` is the HOST modle_pixels_stats of the same band from modle_pixels_count: its sum
+ * is held against MODLE_PIXELS_MAX_SAMPLE_TRIALS and decides nothing else -- a caller who passes a smaller
+ * sum than the band has gets the correct result later, not a wrong one. */
+int modle_pixels_sample(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols,
+                        int64_t bin_offset, uint64_t threshold, uint64_t seed, uint32_t salt,
+                        const modle_pixels_stats* stats, uint32_t* d_kept, uint32_t* d_rest, void* stream,
+                        char* err, size_t errlen);
+
+/* One call: modle_pixels_count on the band (whose sum is held against the cap), the sampling into a
+ * scratch band of the context (grown on demand, freed by modle_pixels_destroy; one for the kept and one
+ * for the rest band), then modle_pixels_to_host on the kept (`which` == MODLE_PIXELS_SAMPLE_KEPT) or the
+ * rest (MODLE_PIXELS_SAMPLE_REST) band: its sorted non-zero pixels with `bin_offset` added to the ids and
+ * its statistics in *stats_out (pinned buffers of the context, valid until the next call on it).  Any
+ * other `which` is MODLE_PIXELS_ERR_ARG.  Waits for `stream`. */
+int modle_pixels_sample_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols,
+                                int64_t bin_offset, uint64_t threshold, uint64_t seed, uint32_t salt, int which,
+                                const int64_t** bin1, const int64_t** bin2, const int32_t** count,
+                                const int64_t** bin1_offset, modle_pixels_stats* stats_out, void* stream,
+                                char* err, size_t errlen);
 
 #ifdef __cplusplus
 }

@@ -661,6 +661,55 @@ class Simulator:
                            n, pile.data_ptr(), n_used.data_ptr(), bin_offset, stream, device=self.device)
         return pile, n_used
 
+    def sample_tensors(self, interval_id, frac, seed, salt=0, bin_offset=0, rest=False, stream=None):
+        """The interval's matrix at the fraction `frac` of its depth: every contact is kept with
+        probability floor(frac * 2^32) / 2^32, independently (binomial thinning, the default mode of
+        `cooltools random-sample`: the total is random around its target, not equal to it).  Returns the
+        kept band as a torch int32 tensor of nrows * ncols + 1 words on the simulator's device, in the
+        band's layout; with `rest` the pair (kept, rest), rest = band - kept, two disjoint
+        pseudo-replicates.  Trial t of pixel (i, j) is decided by the Philox word keyed by (i + bin_offset,
+        j + bin_offset, t, salt) and `seed` (pixels.sample_pixels states it on the host): the same seed at
+        a larger fraction keeps a superset, another salt draws anew.  Only the band's statistics cross to
+        the host (the call waits for them); the kernel is enqueued on `stream` and not waited for.  A
+        tensor is a band like the interval's own, and its data_ptr() goes where that goes:
+
+            kept = sim.sample_tensors(iid, 0.25, seed=1)
+            d_band, _, nrows, ncols = sim.outputs(iid)
+            tiles = torch.empty((n, 256, 256), dtype=torch.int32, device=kept.device)
+            pixels.dense_tiles_into(kept.data_ptr(), nrows, ncols, 0, 256, 128, n, tiles.data_ptr(), tiles.numel())
+            pixels.marginals_into(kept.data_ptr(), nrows, ncols, 0, diag_sum.data_ptr(), coverage.data_ptr())
+            pixels.pileup_into(kept.data_ptr(), nrows, ncols, flank, bin1.data_ptr(), bin2.data_ptr(), len(bin1),
+                               pile.data_ptr())"""
+        import torch
+
+        from . import pixels
+
+        d_band, _, nrows, ncols = self.outputs(interval_id)
+        threshold = pixels.sample_threshold(frac)
+        ex = pixels.extractor(self.device)
+        stats = ex.count(d_band, nrows, ncols, stream=stream)
+        dev = torch.device("cuda", self.device)
+        kept = torch.empty(nrows * ncols + 1, dtype=torch.int32, device=dev)
+        others = torch.empty(nrows * ncols + 1, dtype=torch.int32, device=dev) if rest else None
+        ex.sample_into(d_band, nrows, ncols, threshold, seed, stats, kept.data_ptr(),
+                       None if others is None else others.data_ptr(), salt, bin_offset, stream)
+        return (kept, others) if rest else kept
+
+    def sample(self, interval_id, frac, seed, salt=0, bin_offset=0, rest=False):
+        """The non-zero pixels of the interval's matrix at the fraction `frac` of its depth, a
+        pixels.Pixels like pixels() returns, with `bin_offset` added to the ids; with `rest` the pair
+        (kept, rest) of two disjoint matrices that add up to the interval's.  Drawn on the device as
+        sample_tensors() describes, from one draw; only the pixels cross to the host.  Call it after
+        wait()."""
+        from . import pixels
+
+        d_band, _, nrows, ncols = self.outputs(interval_id)
+        if not rest:
+            return pixels.sample(d_band, nrows, ncols, pixels.sample_threshold(frac), seed, salt, bin_offset,
+                                 device=self.device)
+        bands = self.sample_tensors(interval_id, frac, seed, salt, bin_offset, rest=True)
+        return tuple(pixels.extract(t.data_ptr(), nrows, ncols, bin_offset, device=self.device) for t in bands)
+
     def simulate_interval(self, start, end, bar_pos, bar_dir, stp_active, stp_inactive, tasks):
         """One-call seam (modle_hip_simulate_interval): returns contacts, missed, occupancy,
         results."""

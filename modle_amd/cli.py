@@ -13,7 +13,9 @@ contacts per diagonal, and with --coverage `<prefix>_coverage.bedgraph`, the con
 summed on the GPU; with --insulation-windows `<prefix>_insulation.tsv`, the insulation sums and scores
 per bin over sliding diamond windows, summed on the GPU; with --dots `<prefix>_dots.bedpe`, the pixels
 enriched over their four HiCCUPS neighbourhoods, found on the GPU; with --pileup-at `<prefix>_pileup.tsv`,
-the windows around the dots, the barriers or the pairs of a BEDPE file, summed on the GPU.  Everything heavy is native: parsing and
+the windows around the dots, the barriers or the pairs of a BEDPE file, summed on the GPU; with
+--subsample-frac or --subsample-to `<prefix>_sampled.cool`, the matrix with every contact kept with one
+probability, drawn on the GPU (with --subsample-split also `<prefix>_sampled_rest.cool`, the others).  Everything heavy is native: parsing and
 task generation in libmodle_hip.so (host), the simulation on the MI355X (one process per GPU;
 under torch.distributed.run the cells are sharded over the ranks and the matrices are summed
 with RCCL, or with --dist-backend gloo on host copies), the writers in libmodle_cooler.so.  `-t/--threads` is accepted and ignored."""
@@ -169,6 +171,12 @@ def pileup_path(prefix):
     return prefix + "_pileup.tsv"
 
 
+def sampled_paths(prefix, mcool=False):
+    """(the file of the kept contacts, the file of the others) of --subsample-frac / --subsample-to"""
+    ext = ".mcool" if mcool else ".cool"
+    return prefix + "_sampled" + ext, prefix + "_sampled_rest" + ext
+
+
 def build_parser():
     ap = argparse.ArgumentParser(prog="modle_amd", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -255,6 +263,23 @@ def build_parser():
                     help="with --pileup-at: the side of the corner blocks of the APA scores (a positive multiple "
                          "of the pileup resolution, at most the flank; default a third of the flank's bins, at "
                          "least one)")
+    depth = io.add_mutually_exclusive_group()
+    depth.add_argument("--subsample-frac", type=float, default=None, metavar="F",
+                       help="also write <prefix>_sampled.cool (.mcool with --mcool-resolutions): the matrix with "
+                            "every contact kept with probability F, 0 < F <= 1, independently (binomial thinning, "
+                            "the default mode of `cooltools random-sample`: the total is random around F times "
+                            "the matrix's, not equal to it), drawn on the GPU at -r by a generator keyed by the "
+                            "pixel's bin ids in the file; the other resolutions are coarsened from the sampled one")
+    depth.add_argument("--subsample-to", type=int, default=None, metavar="N",
+                       help="like --subsample-frac with the fraction that brings the contacts of the whole "
+                            "matrix to about N; with N at or above them the unsampled matrix is written, with a "
+                            "warning")
+    io.add_argument("--subsample-seed", type=int, default=None, metavar="S",
+                    help="with --subsample-frac / --subsample-to: the seed of the draw (default --seed); the same "
+                         "seed at a larger fraction keeps a superset")
+    io.add_argument("--subsample-split", action="store_true",
+                    help="with --subsample-frac / --subsample-to: also write <prefix>_sampled_rest.cool, the "
+                         "contacts that were not kept: two disjoint pseudo-replicates that add up to the matrix")
     io.add_argument("--log-model-internal-state", action="store_true",
                     help="write <prefix>_internal_state.log.gz: one line of statistics per task and "
                          "epoch (uses the diagnostic build libmodle_hip_statelog.so)")
@@ -388,9 +413,50 @@ Dots = collections.namedtuple("Dots", "path resolution window peak min_count fol
 # what --pileup-at asks for: the file (None with --skip-output), the bin size, the flank and the corner of
 # the APA scores in base pairs, and the sources in the order given (`dots`, `barriers` or a BEDPE path)
 Pileup = collections.namedtuple("Pileup", "path resolution flank corner sources")
-# (`insulation`, `dots` and `pileup` came later: at the end, and None unless asked for)
+# what --subsample-frac / --subsample-to ask for: the files of the kept and of the other contacts (None
+# with --skip-output, which is refused), the fraction or the target (one of them None), the seed, and
+# whether the second file is written
+Subsample = collections.namedtuple("Subsample", "path rest_path frac target seed split")
+# (`insulation`, `dots` and `pileup` came later: at the end, and None unless asked for; the sampled files
+# are not among the fields: subsample_plan, which preflight calls for its refusals, plans them)
 Preflight = collections.namedtuple("Preflight", "bin_sizes outputs rank world device insulation dots pileup",
                                    defaults=(None, None, None))
+
+
+def subsample_options(a, cfg):
+    """The sampled matrix the arguments ask for, as a Subsample without paths, or None.  SystemExit:
+    --subsample-seed or --subsample-split without a depth, both depths (the parser refuses that already),
+    a fraction outside (0, 1] or NaN, a negative target, a seed that is no uint64, --skip-output (both
+    depths need the cooler: its sums set the target, and the sampled file is a cooler)."""
+    frac, target = a.subsample_frac, a.subsample_to
+    if frac is None and target is None:
+        if a.subsample_seed is not None:
+            raise SystemExit("--subsample-seed needs --subsample-frac or --subsample-to")
+        if a.subsample_split:
+            raise SystemExit("--subsample-split needs --subsample-frac or --subsample-to")
+        return None
+    if frac is not None and target is not None:
+        raise SystemExit("--subsample-frac excludes --subsample-to")
+    if frac is not None and not 0.0 < frac <= 1.0:  # (false for NaN)
+        raise SystemExit(f"--subsample-frac: {frac} is not in (0, 1]")
+    if target is not None and target < 0:
+        raise SystemExit(f"--subsample-to: {target} is negative")
+    seed = int(cfg.seed) if a.subsample_seed is None else a.subsample_seed
+    if not 0 <= seed < 1 << 64:
+        raise SystemExit(f"--subsample-seed: {seed} is no unsigned 64-bit number")
+    if a.skip_output:
+        raise SystemExit(f"--subsample-{'frac' if target is None else 'to'} needs the cooler: it excludes --skip-output")
+    return Subsample(None, None, frac, target, seed, bool(a.subsample_split))
+
+
+def subsample_plan(a, cfg):
+    """subsample_options with the paths of the files: `<prefix>_sampled.cool` and `<prefix>_sampled_rest.cool`,
+    .mcool with --mcool-resolutions"""
+    sub = subsample_options(a, cfg)
+    if sub is None:
+        return None
+    kept_path, rest_path = sampled_paths(a.output_prefix, mcool=a.mcool_resolutions is not None)
+    return sub._replace(path=kept_path, rest_path=rest_path)
 
 
 def pileup_options(a, cfg, dots):
@@ -497,9 +563,9 @@ def insulation_options(a, cfg):
 def preflight(a, cfg):
     """What the arguments alone settle and refuse, without a genome or a GPU.  SystemExit: a bad
     --mcool-resolutions list; --coverage-ignore-diags without --coverage, or negative; what
-    insulation_options, dots_options and pileup_options refuse; on rank 0, an output that exists without
-    --force (cooler or .mcool, then bigwig, then .npz, then the expected, the coverage, the insulation, the
-    dots and the pileup file).  With
+    insulation_options, dots_options, pileup_options and subsample_options refuse; on rank 0, an output that
+    exists without --force (cooler or .mcool, then bigwig, then .npz, then the expected, the coverage, the
+    insulation, the dots and the pileup file, then the sampled files).  With
     --skip-output no file is planned and none is looked at."""
     if a.coverage_ignore_diags is not None:
         if not a.coverage:
@@ -509,6 +575,7 @@ def preflight(a, cfg):
     ins = insulation_options(a, cfg)
     dots = dots_options(a, cfg)
     pile = pileup_options(a, cfg, dots)
+    sub = subsample_plan(a, cfg)
     # (a bad list ends the run here, before anything is imported or simulated)
     bin_sizes = None if a.mcool_resolutions is None else mcool_bin_sizes(a.mcool_resolutions, cfg.bin_size)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -534,7 +601,8 @@ def preflight(a, cfg):
         os.makedirs(os.path.dirname(os.path.abspath(cool_path)), exist_ok=True)
         for p in (outputs.cooler, outputs.bigwig, outputs.dense, outputs.expected, outputs.coverage,
                   None if ins is None else ins.path, None if dots is None else dots.path,
-                  None if pile is None else pile.path):
+                  None if pile is None else pile.path, None if sub is None else sub.path,
+                  None if sub is None or not sub.split else sub.rest_path):
             if p and os.path.exists(p) and not a.force:
                 raise SystemExit(f"refusing to overwrite {p}: pass --force to overwrite")
     return Preflight(bin_sizes, outputs, rank, world, device, ins, dots, pile)
@@ -639,6 +707,7 @@ def simulate(a, log=print):
         occupancies = driver.write_outputs(
             sim, cfg, plan, ids, tensors, pre.outputs, pre.bin_sizes, regions, pre.rank, log, a.dist_backend,
             coverage_min_diag=a.coverage_ignore_diags or 0, insulation=pre.insulation, dots=pre.dots, pileup=pre.pileup,
+            subsample=subsample_plan(a, cfg),
             assembly=a.assembly_name,
             generated_by="modle_amd (MI355X)", metadata_json=meta,
             force_overwrite=a.force, chroms=chroms)

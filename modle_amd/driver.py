@@ -350,7 +350,88 @@ def _interval_pixels(sim, plan, ids, missed, log, k, factor, first_bin, bin_offs
     return px
 
 
-EXPECTED_HEADER = "chrom\tstart\tend\tbin_size\tdist\tdist_bp\tn_valid\tcount_sum\tcount_avg\n"
+def subsample_threshold(target, total):
+    """The threshold (of 2^32) that brings a job of `total` contacts to about `target`: floor(target *
+    2^32 / total) in integers; 2^32, which keeps everything, when the target is not below the total (an
+    empty job included).  The kept total is binomial around the target, not equal to it."""
+    target, total = int(target), int(total)
+    if target < 0:
+        raise ValueError(f"subsample: the target {target} is negative")
+    return 1 << 32 if target >= total else (target << 32) // total
+
+
+SAMPLE_CHECKED_PIXELS = 4096  # how many kept pixels of an interval check_sample draws again on the host
+
+
+def check_sample(name, stats, kept, rest, threshold, seed, salt=0):
+    """What the kept and the rest pixels of an interval (pixels.Pixels with the file's global bin ids)
+    must satisfy before they are written, against the pixels.Stats `stats` of the interval's matrix: the
+    two sums add up to the interval's, neither has more pixels than the interval, and for up to
+    SAMPLE_CHECKED_PIXELS evenly spaced kept pixels the count n = kept + rest, with the rest looked up in
+    the rest pixels, gives the kept count again through the host statement of the draw
+    (pixels.sample_pixels).  RuntimeError, naming the interval and what fails."""
+    from . import pixels
+
+    k_sum, r_sum = int(kept.count.sum(dtype=np.int64)), int(rest.count.sum(dtype=np.int64))
+    if k_sum + r_sum != int(stats.sum):
+        raise RuntimeError(f"{name}: the sampled halves hold {k_sum} + {r_sum} contacts, the interval {int(stats.sum)}")
+    for what, px in (("kept", kept), ("other", rest)):
+        if len(px.count) > int(stats.nnz):
+            raise RuntimeError(f"{name}: {len(px.count)} {what} pixels, the interval has {int(stats.nnz)}")
+    n = len(kept.count)
+    if n == 0:
+        return
+    pick = np.unique(np.linspace(0, n - 1, min(n, SAMPLE_CHECKED_PIXELS)).astype(np.int64))
+    b1, b2, c = kept.bin1[pick], kept.bin2[pick], kept.count[pick].astype(np.int64)
+    key = (rest.bin1.astype(np.uint64) << np.uint64(32)) | rest.bin2.astype(np.uint64)  # (sorted: cooler order)
+    want = (b1.astype(np.uint64) << np.uint64(32)) | b2.astype(np.uint64)
+    at = np.searchsorted(key, want)
+    found = at < len(key)
+    found[found] = key[at[found]] == want[found]
+    others = np.zeros(len(pick), dtype=np.int64)
+    others[found] = rest.count[at[found]]
+    again = pixels.sample_pixels(b1, b2, c + others, threshold, seed, salt).astype(np.int64)
+    bad = np.nonzero(again != c)[0]
+    if len(bad):
+        t = int(bad[0])
+        raise RuntimeError(f"{name}: pixel ({int(b1[t])}, {int(b2[t])}) of {int(c[t] + others[t])} contacts keeps "
+                           f"{int(c[t])} in the file and {int(again[t])} by the definition")
+
+
+def _interval_sampled(sim, plan, ids, threshold, seed, cache, want_rest, k, factor, first_bin, bin_offset):
+    """write_pixels' callback for a sampled file (`want_rest`: for the file of the other half).  At the
+    base bin size, which write_pixels asks for first, plan entry k is sampled once with the file's global
+    bin ids -- `bin_offset` is the interval's first bin in the file, so a pixel's draw does not depend on
+    how the genome was cut into intervals --, both halves are extracted and checked (check_sample) and the
+    bands are kept in `cache`; the other levels are coarsened from the kept (or the other) band, so that
+    the levels of the file agree.  `cache` holds the two bands of one interval at a time."""
+    if ids[k] is None:
+        return None
+    import torch
+
+    from . import pixels
+
+    d_band, _, nrows, ncols = sim.outputs(ids[k])
+    ex = pixels.extractor(sim.device)
+    if factor != 1:
+        if cache.get("k") != k:
+            raise RuntimeError("a sampled file is written from its base bin size upwards")
+        band = cache["bands"][1 if want_rest else 0]
+        return ex.coarse_extract(band.data_ptr(), nrows, ncols, factor, first_bin, bin_offset)
+    cache.clear()  # (the bands of the interval before go)
+    dev = torch.device("cuda", sim.device)
+    bands = (torch.empty(nrows * ncols + 1, dtype=torch.int32, device=dev),
+             torch.empty(nrows * ncols + 1, dtype=torch.int32, device=dev))
+    stats = ex.count(d_band, nrows, ncols)
+    ex.sample_into(d_band, nrows, ncols, threshold, seed, stats, bands[0].data_ptr(), bands[1].data_ptr(), 0,
+                   bin_offset)
+    halves = tuple(ex.extract(b.data_ptr(), nrows, ncols, bin_offset) for b in bands)
+    check_sample(interval_name(plan[k]["interval"]), stats, halves[0], halves[1], threshold, seed)
+    cache.update(k=k, bands=bands)
+    return halves[1 if want_rest else 0]
+
+
+EXPECTED_HEADER ="chrom\tstart\tend\tbin_size\tdist\tdist_bp\tn_valid\tcount_sum\tcount_avg\n"
 
 
 def interval_name(iv):
@@ -840,6 +921,31 @@ def _interval_pileup(sim, plan, ids, marginals, cache, flank, name, k, factor, f
     return pile, n_used, api.pileup_expected_terms(dist_hist, diag_sum, nc, flank)
 
 
+def sample_matrices(sim, cfg, plan, ids, total, subsample, bin_sizes, log, **attrs):
+    """Writes `subsample.path`, the cooler (or .mcool) of the kept contacts, and with `subsample.split`
+    `subsample.rest_path`, that of the others.  The threshold is that of `subsample.frac`, or with
+    `subsample.target` the one that brings the job's `total` contacts at the base bin size to about the
+    target; a target that is not below the total keeps everything, with a warning.  The ids of the draw
+    are the file's global bin ids, the salt is 0, the seed `subsample.seed`.  With --subsample-split every
+    interval is drawn a second time, for the second file: the draw is a function of its arguments."""
+    from . import pixels
+
+    if subsample.target is not None:
+        threshold = subsample_threshold(subsample.target, total)
+        if int(subsample.target) >= int(total):
+            log(f"warning: --subsample-to {int(subsample.target)} is not below the {int(total)} contacts of the "
+                "matrix: the sampled file holds the unsampled matrix")
+    else:
+        threshold = pixels.sample_threshold(subsample.frac)
+    for path, want_rest in ((subsample.path, False), (subsample.rest_path, True)):
+        if want_rest and not subsample.split:
+            continue
+        write_pixels(path, cfg, plan,
+                     functools.partial(_interval_sampled, sim, plan, ids, threshold, int(subsample.seed), {}, want_rest),
+                     bin_sizes, **attrs)
+        log(f"written {path} (threshold {threshold} of 2^32)")
+
+
 def reduce_to_rank0(t, backend, rank):
     """Sum of the ranks' tensors `t` into rank 0's, in place (the other ranks' tensors are unspecified
     afterwards).  `nccl` (= RCCL): on the device tensors.  `gloo`: on host copies -- the rehearsal with
@@ -870,14 +976,16 @@ def reduce_missed(missed, backend, rank, device=None):
 
 
 def write_outputs(sim, cfg, plan, ids, tensors, outputs, bin_sizes=None, regions=(), rank=0, log=print,
-                  backend="nccl", coverage_min_diag=0, insulation=None, dots=None, pileup=None, **attrs):
+                  backend="nccl", coverage_min_diag=0, insulation=None, dots=None, pileup=None, subsample=None, **attrs):
     """What a finished launch writes while the simulator is open: the state log (every rank its
     own), then on rank 0 the cooler or .mcool with the missing-interactions warnings, the dense
     `regions` (of dense_regions), the distance-decay curves (at every bin size of the file) and the
     coverage without the diagonals below `coverage_min_diag`, and the insulation track `insulation` (a
     cli.Insulation: path, resolution, windows in base pairs, min_diag; None or without a path: not
     written), and the dots `dots` (a cli.Dots; None or without a path: not written),
-    and the pileups `pileup` (a cli.Pileup; likewise; its source `dots` piles the dots just written).  `outputs.state_log`, `.cooler`, `.dense`,
+    and the pileups `pileup` (a cli.Pileup; likewise; its source `dots` piles the dots just written),
+    and the sampled matrix `subsample` (a cli.Subsample; likewise): the same file as the cooler from the kept
+    half of a binomial thinning of every interval (sample_matrices), and with its `split` the other half.  `outputs.state_log`, `.cooler`, `.dense`,
     `.expected`, `.coverage`: the paths, None for a file that is not written; without a cooler
     (--skip-output) the matrices are only summed, for the warnings.  `tensors`: with several ranks the (contacts, occupancy) torch tensors per plan entry;
     they are reduced in place onto rank 0 (reduce_to_rank0 with `backend`), which extracts from the
@@ -925,6 +1033,8 @@ def write_outputs(sim, cfg, plan, ids, tensors, outputs, bin_sizes=None, regions
     write_pixels(outputs.cooler, cfg, plan,
                  functools.partial(_interval_pixels, sim, plan, ids, missed, log, sums=sums), bin_sizes, **attrs)
     log(f"written {outputs.cooler}")
+    if subsample is not None and subsample.path is not None:
+        sample_matrices(sim, cfg, plan, ids, sum(sums.values()), subsample, bin_sizes, log, **attrs)
     if outputs.dense is not None:
         # (the cooler's INT32 range check has passed: the uint32 words are int32 counts; with
         # several ranks the region is unpacked from the reduced tensor, like the pixels)

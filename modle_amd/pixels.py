@@ -2,8 +2,9 @@
 built by `make -C modle_amd/pixels`): the non-zero pixels of a band matrix that lies in device
 memory, in cooler order, found on the GPU; the band at a multiple of its bin size; square regions
 of it as dense matrices; its marginals, the sums per diagonal and per bin; its insulation sums
-over sliding diamond windows; its dots, the pixels enriched over their HiCCUPS neighbourhoods; and
-its pileups, the windows around anchor pairs summed into one.
+over sliding diamond windows; its dots, the pixels enriched over their HiCCUPS neighbourhoods;
+its pileups, the windows around anchor pairs summed into one; and its random sampling, every contact
+kept with one probability by a generator keyed by the pixel's coordinates.
 There is no host fallback: without the library or
 without a device the calls fail."""
 import ctypes as C
@@ -18,6 +19,9 @@ ERR_ARG, ERR_DEVICE, ERR_RANGE = -1, -2, -3
 MAX_WINDOW, MAX_WINDOWS = 1024, 8  # MODLE_PIXELS_MAX_WINDOW, MODLE_PIXELS_MAX_WINDOWS
 MAX_DOT_WINDOW = 20  # MODLE_PIXELS_MAX_DOT_WINDOW
 MAX_PILEUP_FLANK, PILEUP_GROUPS = 32, 256  # MODLE_PIXELS_MAX_PILEUP_FLANK, MODLE_PIXELS_PILEUP_GROUPS
+SAMPLE_TIER1_TRIALS = 64  # MODLE_PIXELS_SAMPLE_TIER1_TRIALS: what a lane draws of its own pixel
+MAX_SAMPLE_TRIALS = 1 << 40  # MODLE_PIXELS_MAX_SAMPLE_TRIALS
+SAMPLE_KEPT, SAMPLE_REST = 0, 1  # MODLE_PIXELS_SAMPLE_KEPT, MODLE_PIXELS_SAMPLE_REST
 DOT_FOLDS = (1.75, 1.75, 1.5, 1.5)  # HiCCUPS' thresholds: donut, lower-left, horizontal, vertical
 EXPORTS = ["modle_pixels_create", "modle_pixels_destroy", "modle_pixels_count", "modle_pixels_extract",
            "modle_pixels_to_host", "modle_pixels_coarse_shape", "modle_pixels_coarsen",
@@ -27,7 +31,8 @@ EXPORTS = ["modle_pixels_create", "modle_pixels_destroy", "modle_pixels_count", 
            "modle_pixels_insulation_to_host", "modle_pixels_coarse_insulation_to_host", "modle_pixels_dots",
            "modle_pixels_dots_to_host", "modle_pixels_coarse_dots_to_host", "modle_pixels_pileup_accepts",
            "modle_pixels_pileup", "modle_pixels_pileup_to_host",
-           "modle_pixels_coarse_pileup_to_host"]  # every symbol include/modle_pixels.h declares
+           "modle_pixels_coarse_pileup_to_host", "modle_pixels_sample_pixels", "modle_pixels_sample",
+           "modle_pixels_sample_to_host"]  # every symbol include/modle_pixels.h declares
 
 _LIB = None
 _EXTRACTORS = {}
@@ -101,6 +106,13 @@ def lib():
         lb.modle_pixels_pileup_to_host.argtypes = shape + [C.c_uint64, C.c_int64, i64p, i64p, C.c_uint64] + piled
         lb.modle_pixels_coarse_pileup_to_host.argtypes = shape + [C.c_uint64] * 3 + [C.c_int64, i64p, i64p,
                                                                                      C.c_uint64] + piled
+        u32p = C.POINTER(C.c_uint32)
+        draw = [C.c_int64, C.c_uint64, C.c_uint64, C.c_uint32]  # bin_offset, threshold, seed, salt
+        lb.modle_pixels_sample_pixels.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_int64, i64p, i64p, u32p,
+                                                  C.c_uint64, u32p]
+        lb.modle_pixels_sample.argtypes = shape + draw + [C.POINTER(_CStats), C.c_void_p, C.c_void_p, C.c_void_p] + err
+        lb.modle_pixels_sample_to_host.argtypes = shape + draw + [C.c_int] + [C.POINTER(C.c_void_p)] * 4 + \
+            [C.POINTER(_CStats), C.c_void_p] + err
         for name in EXPORTS:
             getattr(lb, name)  # raises AttributeError if a declared symbol is not exported
         _LIB = lb
@@ -279,6 +291,50 @@ def pileup_accepts(nrows, ncols, flank, bin1, bin2, bin_offset=0):
         raise PixelsError(rc, "pileup_accepts: invalid argument (0 < nrows <= ncols, flank <= 32, "
                               "2 * flank + 1 <= nrows, n < 2^31)")
     return out.astype(bool)
+
+
+def sample_threshold(frac):
+    """the threshold of the fraction `frac` of the contacts, floor(frac * 2^32), an int in [0, 2^32]: exact
+    in double (a multiplication by a power of two).  ValueError outside [0, 1] and for NaN.  No float goes
+    further than this."""
+    f = float(frac)
+    if not 0.0 <= f <= 1.0:  # (false for NaN)
+        raise ValueError(f"sample: the fraction {frac!r} is not in [0, 1]")
+    return int(f * 4294967296.0)
+
+
+def _draw(threshold, seed, salt):
+    """the integers of a draw, refused outside their C types (ctypes would wrap them silently)"""
+    threshold, seed, salt = int(threshold), int(seed), int(salt)
+    if not 0 <= threshold <= 1 << 32:
+        raise PixelsError(ERR_ARG, f"sample: the threshold {threshold} is not in [0, 2^32]")
+    if not 0 <= seed < 1 << 64 or not 0 <= salt < 1 << 32:
+        raise PixelsError(ERR_ARG, f"sample: seed {seed} / salt {salt} is no uint64 / uint32")
+    return threshold, seed, salt
+
+
+def sample_pixels(bin1, bin2, count, threshold, seed, salt=0, bin_offset=0):
+    """kept[t] of the host pixels (bin1[t] + bin_offset, bin2[t] + bin_offset) with count[t] contacts, a
+    numpy uint32 array: trial t of a pixel is kept when word t & 3 of philox4x32_10((I, J, t >> 2, salt),
+    seed) is below `threshold` (sample_threshold) -- the host statement of what the kernel draws, compiled
+    from the same function (modle_pixels_sample_pixels; no device is needed)"""
+    threshold, seed, salt = _draw(threshold, seed, salt)
+    keep, p1, p2, n = _anchors(bin1, bin2)
+    cnt = np.asarray(count).reshape(-1)
+    if len(cnt) != n:
+        raise PixelsError(ERR_ARG, f"sample_pixels: {n} pixels and {len(cnt)} counts")
+    if n and (int(cnt.min()) < 0 or int(cnt.max()) >= 1 << 32):
+        raise PixelsError(ERR_RANGE, "sample_pixels: a count is no uint32")
+    cnt = np.ascontiguousarray(cnt, dtype=np.uint32)
+    out = np.zeros(n, dtype=np.uint32)
+    u32p = C.POINTER(C.c_uint32)
+    rc = lib().modle_pixels_sample_pixels(seed, salt, threshold, int(bin_offset), p1, p2,
+                                          cnt.ctypes.data_as(u32p) if n else None, n,
+                                          out.ctypes.data_as(u32p) if n else None)
+    del keep
+    if rc != 0:
+        raise PixelsError(rc, "sample_pixels: invalid argument (threshold <= 2^32, ids in [0, 2^32))")
+    return out
 
 
 class Extractor:
@@ -503,6 +559,28 @@ class Extractor:
         return self._pileup(self._L.modle_pixels_coarse_pileup_to_host, flank, bin1, bin2, bin_offset, d_band,
                             int(nrows), int(ncols), int(factor), int(first_bin), stream=stream)
 
+    def sample_into(self, d_band, nrows, ncols, threshold, seed, stats, d_kept, d_rest=None, salt=0, bin_offset=0,
+                    stream=None):
+        """enqueues the sampling of the band (modle_pixels_sample): of the n contacts of pixel (i, j) those
+        trials t are kept whose Philox word, keyed by (i + bin_offset, j + bin_offset, t, salt) and `seed`,
+        is below `threshold` (sample_threshold).  The kept counts go to the caller-owned device array
+        `d_kept`, the others to `d_rest` (uint32[nrows * ncols + 1] each, the band's layout; either may be
+        None); every word is written.  `stats`: the Stats of the same band from count(); a sum above
+        MAX_SAMPLE_TRIALS raises PixelsError(ERR_RANGE)."""
+        threshold, seed, salt = _draw(threshold, seed, salt)
+        st = None if stats is None else _CStats(int(stats.nnz), int(stats.sum), int(stats.max_count), 0)
+        _call(self._L.modle_pixels_sample, self._h, d_band, int(nrows), int(ncols), int(bin_offset), threshold, seed,
+              salt, None if st is None else C.byref(st), d_kept, d_rest, _stream_ptr(stream))
+
+    def sample(self, d_band, nrows, ncols, threshold, seed, salt=0, bin_offset=0, rest=False, stream=None):
+        """the kept contacts of the band (`rest`: the others) as Pixels, what extract returns of the sampled
+        band: counted, sampled into a scratch band of the context and extracted on the device
+        (modle_pixels_sample_to_host).  The total is binomial around threshold / 2^32 of the band's sum."""
+        threshold, seed, salt = _draw(threshold, seed, salt)
+        return self._to_host(self._L.modle_pixels_sample_to_host, lambda: int(ncols), d_band, int(nrows), int(ncols),
+                             int(bin_offset), threshold, seed, salt, SAMPLE_REST if rest else SAMPLE_KEPT,
+                             stream=stream)
+
 
 def extractor(device=0):
     """the process-wide context of `device`"""
@@ -611,3 +689,17 @@ def coarse_pileup(d_band, nrows, ncols, factor, first_bin, flank, bin1, bin2, bi
     and summed on the device."""
     return extractor(device).coarse_pileup(d_band, nrows, ncols, factor, first_bin, flank, bin1, bin2, bin_offset,
                                            stream)
+
+
+def sample_into(d_band, nrows, ncols, threshold, seed, stats, d_kept, d_rest=None, salt=0, bin_offset=0, stream=None,
+                device=0):
+    """The band at device pointer `d_band` thinned into the device arrays `d_kept` and / or `d_rest`;
+    enqueued on `stream`, nothing crosses to the host."""
+    extractor(device).sample_into(d_band, nrows, ncols, threshold, seed, stats, d_kept, d_rest, salt, bin_offset,
+                                  stream)
+
+
+def sample(d_band, nrows, ncols, threshold, seed, salt=0, bin_offset=0, rest=False, stream=None, device=0):
+    """The kept contacts (`rest`: the others) of the band at device pointer `d_band` as Pixels, sampled and
+    extracted on the device."""
+    return extractor(device).sample(d_band, nrows, ncols, threshold, seed, salt, bin_offset, rest, stream)

@@ -90,6 +90,8 @@ struct modle_pixels_handle {
   GrowBuf<uint64_t> pile_partial;
   GrowBuf<int64_t> pile_anchors;
   GrowBuf<uint64_t, true> pile_out;
+  // modle_pixels_sample_to_host: the kept band and the rest band (modle_sample.hip)
+  GrowBuf<uint32_t> sample_kept, sample_rest;
 };
 
 #endif
