@@ -389,10 +389,7 @@ class Simulator:
         from . import pixels
 
         d_contacts, _, nrows, ncols = self.outputs(interval_id)
-        if int(factor) == 1:
-            return pixels.extract(d_contacts, nrows, ncols, bin_offset, stream, device=self.device)
-        return pixels.coarse_extract(d_contacts, nrows, ncols, factor, first_bin, bin_offset, stream,
-                                     device=self.device)
+        return pixels.extractor(self.device).extract(d_contacts, nrows, ncols, bin_offset, stream, factor, first_bin)
 
     def coarse_pixels(self, interval_id, factor, first_bin, bin_offset=0, stream=None):
         """`pixels` at `factor` times the bin size"""
@@ -405,16 +402,8 @@ class Simulator:
         (`first_bin` as for coarse_pixels) and `lo`, `hi` are column indexes of that coarse band."""
         from . import pixels
 
-        d_band, _, nrows, ncols = self.outputs(interval_id)
-        if int(factor) == 1:
-            return pixels.dense(d_band, nrows, ncols, lo, hi, stream, device=self.device)
-        import torch
-
-        nr, nc = pixels.coarse_shape(nrows, ncols, factor, first_bin)
-        scratch = torch.empty(nr * nc + 1, dtype=torch.int32, device=torch.device("cuda", self.device))
-        ex = pixels.extractor(self.device)
-        ex.coarsen_into(d_band, nrows, ncols, factor, first_bin, scratch.data_ptr(), nr * nc + 1, stream)
-        return ex.dense(scratch.data_ptr(), nr, nc, lo, hi, stream)  # (waits: the scratch may go)
+        d_band, nrows, ncols, _keep = self._band(interval_id, factor, first_bin, stream)
+        return pixels.dense(d_band, nrows, ncols, lo, hi, stream, device=self.device)  # (waits: a scratch may go)
 
     def dense_tiles(self, interval_id, first, size, step, count=None, stream=None):
         """`count` square windows of the interval (window t: the bins first + t * step .. + size - 1;
@@ -442,10 +431,7 @@ class Simulator:
         from . import pixels
 
         d_band, _, nrows, ncols = self.outputs(interval_id)
-        if int(factor) == 1:
-            return pixels.marginals(d_band, nrows, ncols, min_diag, stream, device=self.device)
-        return pixels.coarse_marginals(d_band, nrows, ncols, factor, first_bin, min_diag, stream,
-                                       device=self.device)
+        return pixels.extractor(self.device).marginals(d_band, nrows, ncols, min_diag, stream, factor, first_bin)
 
     def expected(self, interval_id, factor=1, first_bin=0):
         """The distance-decay curve of the interval, summed on the device from the band where it lies
@@ -490,11 +476,8 @@ class Simulator:
         from . import pixels
 
         d_band, _, nrows, ncols = self.outputs(interval_id)
-        if int(factor) == 1:
-            ins_sum = pixels.insulation(d_band, nrows, ncols, windows, min_diag, stream, device=self.device)
-        else:
-            ins_sum = pixels.coarse_insulation(d_band, nrows, ncols, factor, first_bin, windows, min_diag, stream,
-                                               device=self.device)
+        ins_sum = pixels.extractor(self.device).insulation(d_band, nrows, ncols, windows, min_diag, stream, factor,
+                                                           first_bin)
         n_valid = np.stack([pixels.insulation_n_valid(ins_sum.shape[1], w, min_diag) for w in windows])
         return ins_sum, n_valid
 
@@ -513,7 +496,7 @@ class Simulator:
                                device=self.device)
         return out
 
-    def _dot_band(self, interval_id, factor, first_bin, stream):
+    def _band(self, interval_id, factor, first_bin, stream):
         """(device pointer, nrows, ncols, what keeps it alive) of the interval's band at `factor` times
         the bin size: the band itself, or a torch scratch band the coarsening is enqueued into"""
         from . import pixels
@@ -557,11 +540,8 @@ class Simulator:
 
         scale, e = self.dot_table(interval_id, w, p, folds, min_diag, factor, first_bin, stream)
         d_band, _, nrows, ncols = self.outputs(interval_id)
-        if int(factor) == 1:
-            px = pixels.dots(d_band, nrows, ncols, w, p, min_diag, min_count, scale, 0, stream, device=self.device)
-        else:
-            px = pixels.coarse_dots(d_band, nrows, ncols, factor, first_bin, w, p, min_diag, min_count, scale, 0,
-                                    stream, device=self.device)
+        px = pixels.extractor(self.device).dots(d_band, nrows, ncols, w, p, min_diag, min_count, scale, 0, stream,
+                                                factor, first_bin)
         return px.bin1, px.bin2, px.count, e[px.bin2 - px.bin1]
 
     def dots_tensors(self, interval_id, w=5, p=2, min_count=1, folds=None, min_diag=2, factor=1, first_bin=0,
@@ -574,7 +554,7 @@ class Simulator:
         from . import pixels
 
         scale, _ = self.dot_table(interval_id, w, p, folds, min_diag, factor, first_bin, stream)
-        d_band, nrows, ncols, keep = self._dot_band(interval_id, factor, first_bin, stream)
+        d_band, nrows, ncols, keep = self._band(interval_id, factor, first_bin, stream)
         dev = torch.device("cuda", self.device)
         ex = pixels.extractor(self.device)
         cand = torch.empty(nrows * ncols + 1, dtype=torch.int32, device=dev)
@@ -599,7 +579,7 @@ class Simulator:
 
         from . import pixels
 
-        d_band, nrows, ncols, keep = self._dot_band(interval_id, factor, first_bin, stream)
+        d_band, nrows, ncols, keep = self._band(interval_id, factor, first_bin, stream)
         out = torch.empty((4, ncols, nrows), dtype=torch.int64, device=torch.device("cuda", self.device))
         pixels.dots_into(d_band, nrows, ncols, w, p, min_diag, 1, None, None, out.data_ptr(), stream,
                          device=self.device)
@@ -621,13 +601,9 @@ class Simulator:
         from . import pixels
 
         d_band, _, nrows, ncols = self.outputs(interval_id)
-        if int(factor) == 1:
-            nr, nc = nrows, ncols
-            pile, n_used = pixels.pileup(d_band, nrows, ncols, flank, bin1, bin2, bin_offset, device=self.device)
-        else:
-            nr, nc = pixels.coarse_shape(nrows, ncols, factor, first_bin)
-            pile, n_used = pixels.coarse_pileup(d_band, nrows, ncols, factor, first_bin, flank, bin1, bin2,
-                                                bin_offset, device=self.device)
+        nr, nc = pixels.band_shape(nrows, ncols, factor, first_bin)
+        pile, n_used = pixels.extractor(self.device).pileup(d_band, nrows, ncols, flank, bin1, bin2, bin_offset, None,
+                                                            factor, first_bin)
         b1 = np.asarray(bin1, dtype=np.int64).reshape(-1)
         b2 = np.asarray(bin2, dtype=np.int64).reshape(-1)
         ok = pixels.pileup_accepts(nr, nc, flank, b1, b2, bin_offset)

@@ -459,21 +459,33 @@ def subsample_plan(a, cfg):
     return sub._replace(path=kept_path, rest_path=rest_path)
 
 
+def _needs(option, given):
+    """SystemExit for the first (name, value) of `given` that is set while `option`, which it needs, is not"""
+    for name, v in given:
+        if v is not None:
+            raise SystemExit(f"{name} needs {option}")
+
+
+def _analysis_resolution(name, value, cfg):
+    """the bin size of an analysis: `value` of the option `name`, None: the resolution; SystemExit unless it is
+    a multiple of the resolution"""
+    base = int(cfg.bin_size)
+    res = base if value is None else int(value)
+    if res < base or res % base != 0:
+        raise SystemExit(f"{name}: {res} is not a multiple of the resolution ({base})")
+    return res
+
+
 def pileup_options(a, cfg, dots):
     """The pileups the arguments ask for, as a Pileup without a path, or None.  `dots`: what dots_options
     returned.  SystemExit: a --pileup-* option without --pileup-at, a resolution that is no multiple of
     -r, a flank or corner that is no positive multiple of the pileup resolution, a flank above 32 bins, a
     corner above the flank, the source `dots` without --dots or at another resolution than the dots'."""
     if not a.pileup_at:
-        for name, v in (("--pileup-flank", a.pileup_flank), ("--pileup-resolution", a.pileup_resolution),
-                        ("--pileup-corner", a.pileup_corner)):
-            if v is not None:
-                raise SystemExit(f"{name} needs --pileup-at")
+        _needs("--pileup-at", (("--pileup-flank", a.pileup_flank), ("--pileup-resolution", a.pileup_resolution),
+                               ("--pileup-corner", a.pileup_corner)))
         return None
-    base = int(cfg.bin_size)
-    res = base if a.pileup_resolution is None else int(a.pileup_resolution)
-    if res < base or res % base != 0:
-        raise SystemExit(f"--pileup-resolution: {res} is not a multiple of the resolution ({base})")
+    res = _analysis_resolution("--pileup-resolution", a.pileup_resolution, cfg)
     flank = 10 * res if a.pileup_flank is None else int(a.pileup_flank)
     if flank < res or flank % res != 0:
         raise SystemExit(f"--pileup-flank: {flank} is not a positive multiple of the pileup resolution ({res})")
@@ -502,9 +514,7 @@ def dots_options(a, cfg):
              ("--dots-min-count", a.dots_min_count), ("--dots-folds", a.dots_folds),
              ("--dots-ignore-diags", a.dots_ignore_diags), ("--dots-cluster-radius", a.dots_cluster_radius))
     if not a.dots:
-        for name, v in given:
-            if v is not None:
-                raise SystemExit(f"{name} needs --dots")
+        _needs("--dots", given)
         return None
     min_diag = 2 if a.dots_ignore_diags is None else a.dots_ignore_diags
     if min_diag < 0:
@@ -512,10 +522,7 @@ def dots_options(a, cfg):
     min_count = 1 if a.dots_min_count is None else a.dots_min_count
     if min_count < 1:
         raise SystemExit(f"--dots-min-count: {min_count} is below 1")
-    base = int(cfg.bin_size)
-    res = base if a.dots_resolution is None else int(a.dots_resolution)
-    if res < base or res % base != 0:
-        raise SystemExit(f"--dots-resolution: {res} is not a multiple of the resolution ({base})")
+    res = _analysis_resolution("--dots-resolution", a.dots_resolution, cfg)
     window = 5 * res if a.dots_window is None else int(a.dots_window)
     peak = min(2 * res, window - res) if a.dots_peak is None else int(a.dots_peak)
     radius = max(1, 20_000 // res) * res if a.dots_cluster_radius is None else int(a.dots_cluster_radius)
@@ -538,18 +545,13 @@ def insulation_options(a, cfg):
     negative number of diagonals, a resolution that is no multiple of -r, a window that is no positive
     multiple of the insulation resolution or has more than 1024 bins."""
     if a.insulation_windows is None:
-        for name, v in (("--insulation-resolution", a.insulation_resolution),
-                        ("--insulation-ignore-diags", a.insulation_ignore_diags)):
-            if v is not None:
-                raise SystemExit(f"{name} needs --insulation-windows")
+        _needs("--insulation-windows", (("--insulation-resolution", a.insulation_resolution),
+                                        ("--insulation-ignore-diags", a.insulation_ignore_diags)))
         return None
     min_diag = 2 if a.insulation_ignore_diags is None else a.insulation_ignore_diags
     if min_diag < 0:
         raise SystemExit(f"--insulation-ignore-diags: {min_diag} is negative")
-    base = int(cfg.bin_size)
-    res = base if a.insulation_resolution is None else int(a.insulation_resolution)
-    if res < base or res % base != 0:
-        raise SystemExit(f"--insulation-resolution: {res} is not a multiple of the resolution ({base})")
+    res = _analysis_resolution("--insulation-resolution", a.insulation_resolution, cfg)
     for w in a.insulation_windows:
         if w <= 0 or w % res != 0:
             raise SystemExit(f"--insulation-windows: {w} is not a positive multiple of the insulation "

@@ -11,6 +11,7 @@ the per-rank contact matrices are summed afterwards (`reduce_outputs`).
 `write_outputs` is the front end's output stage after the launch.
 """
 import functools
+import inspect
 import math
 
 import numpy as np
@@ -336,12 +337,23 @@ def warn_missing(name, total, missed, log):
         log(f"warning: {100.0 * missed / (total + missed):.2f}% missing interactions for {name}")
 
 
+def _needs_matrix(fn):
+    """An _interval_* callback answers None for a plan entry without a matrix, `ids[k] is None`; the two
+    are found by name among its positional arguments."""
+    names = list(inspect.signature(fn).parameters)
+    at_ids, at_k = names.index("ids"), names.index("k")
+
+    @functools.wraps(fn)
+    def guarded(*args, **kw):
+        return None if args[at_ids][args[at_k]] is None else fn(*args, **kw)
+    return guarded
+
+
+@_needs_matrix
 def _interval_pixels(sim, plan, ids, missed, log, k, factor, first_bin, bin_offset, sums=None):
     """write_pixels' callback: every resolution from the same matrix on the device (with several
     ranks: the reduced tensor); the base resolution's sum feeds the missing-interactions warning and
     is kept in `sums[k]`, for the check of the marginals"""
-    if ids[k] is None:
-        return None
     px = sim.pixels(ids[k], bin_offset, factor=factor, first_bin=first_bin)
     if factor == 1:
         warn_missing(plan[k]["interval"]["name"], px.stats.sum, missed[k], log)
@@ -398,6 +410,7 @@ def check_sample(name, stats, kept, rest, threshold, seed, salt=0):
                            f"{int(c[t])} in the file and {int(again[t])} by the definition")
 
 
+@_needs_matrix
 def _interval_sampled(sim, plan, ids, threshold, seed, cache, want_rest, k, factor, first_bin, bin_offset):
     """write_pixels' callback for a sampled file (`want_rest`: for the file of the other half).  At the
     base bin size, which write_pixels asks for first, plan entry k is sampled once with the file's global
@@ -405,8 +418,6 @@ def _interval_sampled(sim, plan, ids, threshold, seed, cache, want_rest, k, fact
     how the genome was cut into intervals --, both halves are extracted and checked (check_sample) and the
     bands are kept in `cache`; the other levels are coarsened from the kept (or the other) band, so that
     the levels of the file agree.  `cache` holds the two bands of one interval at a time."""
-    if ids[k] is None:
-        return None
     import torch
 
     from . import pixels
@@ -478,37 +489,31 @@ def write_expected(path, plan, base, bin_sizes, marginals):
     matrix; the number of pixels of diagonal d is the number of bins less d."""
     with open(path, "w") as fh:
         fh.write(EXPECTED_HEADER)
-        for k, entry in enumerate(plan):
-            if entry["skipped"]:
-                continue
-            iv = entry["interval"]
+        for k, entry, first_bin, _, _ in plan_bands(plan, base):
             for b in (bin_sizes or [int(base)]):
-                got = marginals(k, int(b) // int(base), int(iv["start"]) // int(base))
+                got = marginals(k, int(b) // int(base), first_bin)
                 if got is not None:
                     diag_sum, coverage = got
                     n_valid = api.expected_n_valid(len(diag_sum), len(coverage))
-                    fh.writelines(expected_lines(iv, b, diag_sum, n_valid))
+                    fh.writelines(expected_lines(entry["interval"], b, diag_sum, n_valid))
 
 
 def write_coverage(path, plan, base, marginals):
     """<prefix>_coverage.bedgraph: the coverage of every bin of every entry of the plan that is not
     skipped, in plan order, at the bin size `base`; `marginals` as for write_expected"""
     with open(path, "w") as fh:
-        for k, entry in enumerate(plan):
-            if entry["skipped"]:
-                continue
-            got = marginals(k, 1, int(entry["interval"]["start"]) // int(base))
+        for k, entry, first_bin, factor, _ in plan_bands(plan, base):
+            got = marginals(k, factor, first_bin)
             if got is not None:
                 fh.writelines(coverage_lines(entry["interval"], base, got[1]))
 
 
+@_needs_matrix
 def _interval_marginals(sim, plan, ids, sums, min_diag, cache, k, factor, first_bin):
     """write_expected's and write_coverage's callback: summed on the device from the matrix where it
     lies (with several ranks: the reduced tensor) and checked against the sum of the interval's
     pixels.  `min_diag` holds at the base bin size, whose result both files share (the diagonal sums
     do not depend on it); a coarse level keeps every diagonal."""
-    if ids[k] is None:
-        return None
     if factor == 1 and k in cache:
         return cache[k]
     m = min_diag if factor == 1 else 0
@@ -529,19 +534,26 @@ def insulation_shape(nrows, ncols, first_bin, factor):
     return min(nc, (int(nrows) - 1 + int(factor) - 1) // int(factor) + 1), nc
 
 
+def plan_bands(plan, base, resolution=None):
+    """(k, entry, first_bin, factor, (nrows', ncols')) of every entry of the plan that is not skipped, in plan
+    order: the interval's first bin of `base` bp within its chromosome, `resolution` // `base` (None: 1) and
+    the shape of its band at that factor (insulation_shape)"""
+    base, factor = int(base), 1 if resolution is None else int(resolution) // int(base)
+    for k, entry in enumerate(plan):
+        if not entry["skipped"]:
+            first_bin = int(entry["interval"]["start"]) // base
+            yield k, entry, first_bin, factor, insulation_shape(entry["nrows"], entry["ncols"], first_bin, factor)
+
+
 def insulation_misfit(plan, base, resolution, windows):
     """The first (name of the interval, window in bp, its bins, diagonals of the band, largest window
     in bp that fits) of an entry of the plan that has a matrix and a window of `windows` (bp, multiples
     of `resolution`) whose diamond leaves the band at `resolution`, 2 * w - 1 > nrows' -- or None."""
-    base, res = int(base), int(resolution)
-    for entry in plan:
-        iv = entry["interval"]
-        if entry["skipped"] or entry["ncols"] == 0:
-            continue
-        nr, _ = insulation_shape(entry["nrows"], entry["ncols"], int(iv["start"]) // base, res // base)
+    res = int(resolution)
+    for _, entry, _, _, (nr, _) in plan_bands(plan, base, res):
         for w in windows:
-            if 2 * (int(w) // res) - 1 > nr:
-                return interval_name(iv), int(w), int(w) // res, nr, (nr + 1) // 2 * res
+            if entry["ncols"] != 0 and 2 * (int(w) // res) - 1 > nr:
+                return interval_name(entry["interval"]), int(w), int(w) // res, nr, (nr + 1) // 2 * res
     return None
 
 
@@ -590,27 +602,22 @@ def write_insulation(path, plan, base, resolution, windows, insulation):
     that is not skipped, in plan order, at the bin size `resolution` (a multiple of `base`) for the
     `windows` in base pairs.  `insulation(k, factor, first_bin)` returns (ins_sum, n_valid) of plan
     entry k -- what api.Simulator.insulation returns -- or None for an entry without a matrix."""
-    factor = int(resolution) // int(base)
     with open(path, "w") as fh:
         fh.write(insulation_header(windows))
-        for k, entry in enumerate(plan):
-            if entry["skipped"]:
-                continue
-            iv = entry["interval"]
-            got = insulation(k, factor, int(iv["start"]) // int(base))
+        for k, entry, first_bin, factor, _ in plan_bands(plan, base, resolution):
+            got = insulation(k, factor, first_bin)
             if got is not None:
                 ins_sum, n_valid = got
-                fh.writelines(insulation_lines(iv, base, factor, ins_sum, n_valid,
+                fh.writelines(insulation_lines(entry["interval"], base, factor, ins_sum, n_valid,
                                                api.insulation_score(ins_sum, n_valid)))
 
 
+@_needs_matrix
 def _interval_insulation(sim, plan, ids, windows, min_diag, marginals, k, factor, first_bin):
     """write_insulation's callback: summed on the device from the matrix where it lies (with several
     ranks: the reduced tensor) for the `windows` in bins, and checked against the diagonal sums of the
     marginals pass at the same bin size (`marginals`: _interval_marginals, whose base result the
     expected and the coverage file share)"""
-    if ids[k] is None:
-        return None
     ins_sum, n_valid = sim.insulation(ids[k], windows, min_diag, factor, first_bin)
     check_insulation(interval_name(plan[k]["interval"]), windows, min_diag, ins_sum,
                      marginals(k, factor, first_bin)[0])
@@ -622,14 +629,10 @@ def dots_misfit(plan, base, resolution, window, min_diag):
     bp that fits or 0) of an entry of the plan that has a matrix in whose band at `resolution` no pixel
     can hold the whole window of `window` bp (a multiple of `resolution`) on or above diagonal
     `min_diag`, 4 * w + 1 + min_diag > nrows' -- or None."""
-    base, res, w = int(base), int(resolution), int(window) // int(resolution)
-    for entry in plan:
-        iv = entry["interval"]
-        if entry["skipped"] or entry["ncols"] == 0:
-            continue
-        nr, _ = insulation_shape(entry["nrows"], entry["ncols"], int(iv["start"]) // base, res // base)
-        if 4 * w + 1 + int(min_diag) > nr:
-            return interval_name(iv), int(window), w, nr, max(0, (nr - 1 - int(min_diag)) // 4) * res
+    res, w = int(resolution), int(window) // int(resolution)
+    for _, entry, _, _, (nr, _) in plan_bands(plan, base, res):
+        if entry["ncols"] != 0 and 4 * w + 1 + int(min_diag) > nr:
+            return interval_name(entry["interval"]), int(window), w, nr, max(0, (nr - 1 - int(min_diag)) // 4) * res
     return None
 
 
@@ -681,24 +684,19 @@ def write_dots(path, plan, base, resolution, dots):
     plan order, at the bin size `resolution` (a multiple of `base`).  `dots(k, factor, first_bin)`
     returns (bin1, bin2, count, expected) of plan entry k -- the clustered candidates, interval-relative
     bins -- or None for an entry without a matrix."""
-    factor = int(resolution) // int(base)
     with open(path, "w") as fh:
         fh.write(dots_header())
-        for k, entry in enumerate(plan):
-            if entry["skipped"]:
-                continue
-            iv = entry["interval"]
-            got = dots(k, factor, int(iv["start"]) // int(base))
+        for k, entry, first_bin, factor, _ in plan_bands(plan, base, resolution):
+            got = dots(k, factor, first_bin)
             if got is not None:
-                fh.writelines(dots_lines(iv, base, factor, *got))
+                fh.writelines(dots_lines(entry["interval"], base, factor, *got))
 
 
+@_needs_matrix
 def _interval_dots(sim, plan, ids, w, p, min_count, folds, min_diag, radius, k, factor, first_bin):
     """write_dots' callback: the candidates found on the device in the matrix where it lies (with several
     ranks: the reduced tensor) for `w`, `p`, `radius` in bins, verified (check_dots) and thinned to local
     maxima (api.cluster_dots)"""
-    if ids[k] is None:
-        return None
     bin1, bin2, count, expected = sim.dots(ids[k], w=w, p=p, min_count=min_count, folds=folds, min_diag=min_diag,
                                            factor=factor, first_bin=first_bin)
     entry = plan[k]
@@ -783,14 +781,10 @@ def pileup_misfit(plan, base, resolution, flank, sources=()):
                 read_bedpe(what)
             except (OSError, ValueError) as e:
                 return "bedpe", what, str(e)
-    base, res, f = int(base), int(resolution), int(flank) // int(resolution)
-    for entry in plan:
-        iv = entry["interval"]
-        if entry["skipped"] or entry["ncols"] == 0:
-            continue
-        nr, _ = insulation_shape(entry["nrows"], entry["ncols"], int(iv["start"]) // base, res // base)
-        if 2 * f + 1 > nr:
-            return "flank", interval_name(iv), int(flank), f, nr, (nr - 1) // 2 * res
+    res, f = int(resolution), int(flank) // int(resolution)
+    for _, entry, _, _, (nr, _) in plan_bands(plan, base, res):
+        if entry["ncols"] != 0 and 2 * f + 1 > nr:
+            return "flank", interval_name(entry["interval"]), int(flank), f, nr, (nr - 1) // 2 * res
     return None
 
 
@@ -848,17 +842,14 @@ def write_pileup(path, plan, base, resolution, flank, corner, sources, anchors, 
     observed pile is the sum over the entries in Python ints, the expected one math.fsum over the entries
     of the terms.  `unplaced`: {name: the pairs given that lie in no entry}.  Returns [(name, given,
     placed, used)]."""
-    res, factor = int(resolution), int(resolution) // int(base)
+    res = int(resolution)
     s = 2 * (int(flank) // res) + 1
     done = []
     with open(path, "w") as fh:
         for name in sources:
             observed, terms = [0] * (s * s), [[] for _ in range(s * s)]
             placed = used = 0
-            for k, entry in enumerate(plan):
-                if entry["skipped"]:
-                    continue
-                first_bin = int(entry["interval"]["start"]) // int(base)
+            for k, _, first_bin, factor, _ in plan_bands(plan, base, res):
                 ab = anchors(name, k, factor, first_bin)
                 if ab is None:
                     continue
@@ -879,11 +870,10 @@ def write_pileup(path, plan, base, resolution, flank, corner, sources, anchors, 
     return done
 
 
+@_needs_matrix
 def _interval_anchors(plan, ids, base, resolution, dots, placed, name, k, factor, first_bin):
     """write_pileup's first callback: the run's own clustered dots (`dots`: write_dots' callback), the
     interval's barriers, or the pairs of a BEDPE file that place_pairs put into entry k"""
-    if ids[k] is None:
-        return None
     if name == "dots":
         got = dots(k, factor, first_bin)
         return None if got is None else (np.asarray(got[0], dtype=np.int64), np.asarray(got[1], dtype=np.int64))
@@ -892,6 +882,7 @@ def _interval_anchors(plan, ids, base, resolution, dots, placed, name, k, factor
     return placed[name].get(k, (np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)))
 
 
+@_needs_matrix
 def _interval_pileup(sim, plan, ids, marginals, cache, flank, name, k, factor, first_bin, a, b):
     """write_pileup's second callback: summed on the device from the matrix where it lies (with several
     ranks: the reduced tensor) for `flank` in bins, and verified (check_pileup) against the pixels of the
@@ -900,8 +891,6 @@ def _interval_pileup(sim, plan, ids, marginals, cache, flank, name, k, factor, f
     (`marginals`: _interval_marginals)."""
     from . import pixels
 
-    if ids[k] is None:
-        return None
     entry = plan[k]
     nr, nc = insulation_shape(entry["nrows"], entry["ncols"], first_bin, factor)
     pile, n_used, dist_hist = sim.pileup(ids[k], a, b, flank, factor, first_bin)

@@ -70,14 +70,14 @@ def lib():
         lb.modle_pixels_count.argtypes = shape + [C.c_void_p, C.POINTER(_CStats), C.c_void_p] + err
         lb.modle_pixels_extract.argtypes = shape + [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.c_uint64, C.c_void_p] + err
-        lb.modle_pixels_to_host.argtypes = shape + [C.c_int64] + [C.POINTER(C.c_void_p)] * 4 + \
-            [C.POINTER(_CStats), C.c_void_p] + err
+        # bin_offset, bin1, bin2, count, bin1_offset, stats, stream: the tail of every form that returns pixels
+        pix = [C.c_int64] + [C.POINTER(C.c_void_p)] * 4 + [C.POINTER(_CStats), C.c_void_p] + err
+        lb.modle_pixels_to_host.argtypes = shape + pix
         u64p = C.POINTER(C.c_uint64)
         lb.modle_pixels_coarse_shape.argtypes = [C.c_uint64] * 4 + [u64p, u64p]
         lb.modle_pixels_coarsen.argtypes = shape + [C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64,
                                                     C.c_void_p] + err
-        lb.modle_pixels_coarse_to_host.argtypes = shape + [C.c_uint64, C.c_uint64, C.c_int64] + \
-            [C.POINTER(C.c_void_p)] * 4 + [C.POINTER(_CStats), C.c_void_p] + err
+        lb.modle_pixels_coarse_to_host.argtypes = shape + [C.c_uint64] * 2 + pix
         lb.modle_pixels_tiles_fit.argtypes = [C.c_uint64] * 4 + [u64p]
         lb.modle_pixels_dense_tiles.argtypes = shape + [C.c_uint64] * 4 + [C.c_void_p, C.c_uint64, C.c_void_p] + err
         lb.modle_pixels_dense_to_host.argtypes = shape + [C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p),
@@ -93,7 +93,6 @@ def lib():
         lb.modle_pixels_coarse_insulation_to_host.argtypes = shape + [C.c_uint64] * 2 + wins + \
             [C.POINTER(C.c_void_p), C.c_void_p] + err
         dots = [C.c_uint64] * 4 + [C.POINTER(C.c_double)]  # w, p, min_diag, min_count, scale (a host table)
-        pix = [C.c_int64] + [C.POINTER(C.c_void_p)] * 4 + [C.POINTER(_CStats), C.c_void_p] + err
         lb.modle_pixels_dots.argtypes = shape + dots + [C.c_void_p, C.c_void_p, C.c_void_p] + err
         lb.modle_pixels_dots_to_host.argtypes = shape + dots + pix
         lb.modle_pixels_coarse_dots_to_host.argtypes = shape + [C.c_uint64] * 2 + dots + pix
@@ -111,8 +110,7 @@ def lib():
         lb.modle_pixels_sample_pixels.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_int64, i64p, i64p, u32p,
                                                   C.c_uint64, u32p]
         lb.modle_pixels_sample.argtypes = shape + draw + [C.POINTER(_CStats), C.c_void_p, C.c_void_p, C.c_void_p] + err
-        lb.modle_pixels_sample_to_host.argtypes = shape + draw + [C.c_int] + [C.POINTER(C.c_void_p)] * 4 + \
-            [C.POINTER(_CStats), C.c_void_p] + err
+        lb.modle_pixels_sample_to_host.argtypes = shape + draw + [C.c_int] + pix[1:]
         for name in EXPORTS:
             getattr(lb, name)  # raises AttributeError if a declared symbol is not exported
         _LIB = lb
@@ -150,6 +148,11 @@ def coarse_shape(nrows, ncols, factor, first_bin=0):
     if rc != 0:
         raise PixelsError(rc, "coarse_shape: invalid argument (factor >= 2, 0 < nrows <= ncols)")
     return nr.value, nc.value
+
+
+def band_shape(nrows, ncols, factor=1, first_bin=0):
+    """(nrows, ncols) of the band at `factor` times its bin size: its own at factor 1, else coarse_shape"""
+    return (int(nrows), int(ncols)) if int(factor) == 1 else coarse_shape(nrows, ncols, factor, first_bin)
 
 
 def tiles_fit(ncols, first, size, step):
@@ -382,25 +385,39 @@ class Extractor:
         _call(self._L.modle_pixels_extract, self._h, d_band, int(nrows), int(ncols), int(bin_offset),
               d_bin1_offset, d_bin1, d_bin2, d_count, int(nnz), _stream_ptr(stream))
 
-    def _to_host(self, fn, ncols_out, *args, stream=None):
+    def _form(self, stem, d_band, nrows, ncols, factor, first_bin, coarse):
+        """The one place that chooses between the one-call form modle_pixels_<stem>to_host on the band and
+        modle_pixels_coarse_<stem>to_host at `factor` times its bin size: (the C function, its arguments
+        from d_band to the analysis' own, shape), where shape() is (nrows, ncols) of the band the analysis
+        sees.  `coarse` None: the coarse form unless factor is 1; True, what the coarse_* methods pass:
+        always, so that the library refuses a factor of 1."""
+        if coarse or (coarse is None and int(factor) != 1):
+            return getattr(self._L, f"modle_pixels_coarse_{stem}to_host"), \
+                (d_band, int(nrows), int(ncols), int(factor), int(first_bin)), \
+                lambda: coarse_shape(nrows, ncols, factor, first_bin)
+        return getattr(self._L, f"modle_pixels_{stem}to_host"), (d_band, int(nrows), int(ncols)), \
+            lambda: (int(nrows), int(ncols))
+
+    def _to_host(self, fn, shape, *args, stream=None):
         """a one-call form `fn(handle, *args, four array pointers, stats, stream, err)`: the
-        context's pinned arrays, copied into numpy arrays the caller owns.  `ncols_out()` is asked
-        for the columns of the extracted band once the library has accepted the arguments."""
+        context's pinned arrays, copied into numpy arrays the caller owns.  `shape()` is asked
+        for the shape of the extracted band once the library has accepted the arguments."""
         p1, p2, pc, po = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
         st = _CStats()
         _call(fn, self._h, *args, C.byref(p1), C.byref(p2), C.byref(pc), C.byref(po), C.byref(st),
               _stream_ptr(stream))
         n = int(st.nnz)
         return Pixels(_host_array(p1.value, n, np.int64), _host_array(p2.value, n, np.int64),
-                      _host_array(pc.value, n, np.int32), _host_array(po.value, ncols_out() + 1, np.int64),
+                      _host_array(pc.value, n, np.int32), _host_array(po.value, shape()[1] + 1, np.int64),
                       Stats(st.nnz, st.sum, st.max_count))
 
-    def extract(self, d_band, nrows, ncols, bin_offset=0, stream=None):
+    def extract(self, d_band, nrows, ncols, bin_offset=0, stream=None, factor=1, first_bin=0, coarse=None):
         """one-call form: Pixels of numpy bin1, bin2 (int64), count (int32), bin1_offset
         (int64[ncols + 1]) and Stats(nnz, sum, max_count).  A count above INT32_MAX raises
-        PixelsError(ERR_RANGE)."""
-        return self._to_host(self._L.modle_pixels_to_host, lambda: int(ncols), d_band, int(nrows), int(ncols),
-                             int(bin_offset), stream=stream)
+        PixelsError(ERR_RANGE).  `factor`, `first_bin`, here and in the four analyses below: of the band
+        at `factor` times its bin size, see the coarse_* method."""
+        fn, band, shape = self._form("", d_band, nrows, ncols, factor, first_bin, coarse)
+        return self._to_host(fn, shape, *band, int(bin_offset), stream=stream)
 
     def coarsen_into(self, d_band, nrows, ncols, factor, first_bin, d_out, out_words, stream=None):
         """enqueues the coarsening of the band by `factor` into the caller-owned device array
@@ -414,9 +431,7 @@ class Extractor:
         """one-call form at `factor` times the bin size (modle_pixels_coarse_to_host): what
         extract returns, for the coarse band; bin1_offset has ncols' + 1 entries and `bin_offset`
         counts coarse bins.  A sum above INT32_MAX raises PixelsError(ERR_RANGE)."""
-        return self._to_host(self._L.modle_pixels_coarse_to_host,
-                             lambda: coarse_shape(nrows, ncols, factor, first_bin)[1], d_band, int(nrows),
-                             int(ncols), int(factor), int(first_bin), int(bin_offset), stream=stream)
+        return self.extract(d_band, nrows, ncols, bin_offset, stream, factor, first_bin, True)
 
     def dense_tiles_into(self, d_band, nrows, ncols, first, size, step, count, d_out, out_words, stream=None):
         """enqueues the unpacking of `count` square tiles (tile t: the bins first + t * step ..
@@ -442,28 +457,22 @@ class Extractor:
         _call(self._L.modle_pixels_marginals, self._h, d_band, int(nrows), int(ncols), int(min_diag), d_diag_sum,
               d_coverage, _stream_ptr(stream))
 
-    def _marginals(self, fn, shape_out, *args, stream=None):
-        """a to-host form `fn(handle, *args, two array pointers, stream, err)`: numpy copies"""
-        pd, pc = C.c_void_p(), C.c_void_p()
-        _call(fn, self._h, *args, C.byref(pd), C.byref(pc), _stream_ptr(stream))
-        nr, nc = shape_out()
-        return _host_array(pd.value, nr, np.uint64), _host_array(pc.value, nc, np.uint64)
-
-    def marginals(self, d_band, nrows, ncols, min_diag=0, stream=None):
+    def marginals(self, d_band, nrows, ncols, min_diag=0, stream=None, factor=1, first_bin=0, coarse=None):
         """(diag_sum, coverage) as numpy uint64[nrows] and uint64[ncols] the caller owns, summed on
         the device in one pass over the band (modle_pixels_marginals_to_host): diag_sum[d] is the sum
         of diagonal d, coverage[i] the sum of row i of the symmetric matrix without the diagonals
         below `min_diag`"""
-        return self._marginals(self._L.modle_pixels_marginals_to_host, lambda: (int(nrows), int(ncols)), d_band,
-                               int(nrows), int(ncols), int(min_diag), stream=stream)
+        fn, band, shape = self._form("marginals_", d_band, nrows, ncols, factor, first_bin, coarse)
+        pd, pc = C.c_void_p(), C.c_void_p()
+        _call(fn, self._h, *band, int(min_diag), C.byref(pd), C.byref(pc), _stream_ptr(stream))
+        nr, nc = shape()
+        return _host_array(pd.value, nr, np.uint64), _host_array(pc.value, nc, np.uint64)
 
     def coarse_marginals(self, d_band, nrows, ncols, factor, first_bin, min_diag=0, stream=None):
         """`marginals` of the band at `factor` times its bin size, coarsened on the device
         (modle_pixels_coarse_marginals_to_host): uint64[nrows'] and uint64[ncols'] of coarse_shape;
         `min_diag` counts coarse diagonals"""
-        return self._marginals(self._L.modle_pixels_coarse_marginals_to_host,
-                               lambda: coarse_shape(nrows, ncols, factor, first_bin), d_band, int(nrows),
-                               int(ncols), int(factor), int(first_bin), int(min_diag), stream=stream)
+        return self.marginals(d_band, nrows, ncols, min_diag, stream, factor, first_bin, True)
 
     def insulation_into(self, d_band, nrows, ncols, windows, min_diag, d_out, out_words, stream=None):
         """enqueues the insulation sums of the `windows` (1 to 8 sizes in bins, 2 * w - 1 <= nrows,
@@ -474,28 +483,22 @@ class Extractor:
         _call(self._L.modle_pixels_insulation, self._h, d_band, int(nrows), int(ncols), ws, n, int(min_diag), d_out,
               int(out_words), _stream_ptr(stream))
 
-    def _insulation(self, fn, ncols_out, windows, min_diag, *args, stream=None):
-        """a to-host form `fn(handle, *args, windows, n, min_diag, one array pointer, stream, err)`: a
-        numpy copy"""
-        ws, n = _windows(windows)
-        ptr = C.c_void_p()
-        _call(fn, self._h, *args, ws, n, int(min_diag), C.byref(ptr), _stream_ptr(stream))
-        return _host_array(ptr.value, n * ncols_out(), np.uint64).reshape(n, -1)
-
-    def insulation(self, d_band, nrows, ncols, windows, min_diag=2, stream=None):
+    def insulation(self, d_band, nrows, ncols, windows, min_diag=2, stream=None, factor=1, first_bin=0,
+                   coarse=None):
         """the insulation sums as a numpy uint64[len(windows), ncols] the caller owns: for every window
         w and bin b the sum of the pixels (a, c), b - w < a <= b <= c < b + w, c - a >= min_diag, formed
         on the device (modle_pixels_insulation_to_host)"""
-        return self._insulation(self._L.modle_pixels_insulation_to_host, lambda: int(ncols), windows, min_diag,
-                                d_band, int(nrows), int(ncols), stream=stream)
+        fn, band, shape = self._form("insulation_", d_band, nrows, ncols, factor, first_bin, coarse)
+        ws, n = _windows(windows)
+        ptr = C.c_void_p()
+        _call(fn, self._h, *band, ws, n, int(min_diag), C.byref(ptr), _stream_ptr(stream))
+        return _host_array(ptr.value, n * shape()[1], np.uint64).reshape(n, -1)
 
     def coarse_insulation(self, d_band, nrows, ncols, factor, first_bin, windows, min_diag=2, stream=None):
         """`insulation` of the band at `factor` times its bin size, coarsened on the device
         (modle_pixels_coarse_insulation_to_host): uint64[len(windows), ncols'] of coarse_shape; the
         windows and `min_diag` count coarse bins"""
-        return self._insulation(self._L.modle_pixels_coarse_insulation_to_host,
-                                lambda: coarse_shape(nrows, ncols, factor, first_bin)[1], windows, min_diag,
-                                d_band, int(nrows), int(ncols), int(factor), int(first_bin), stream=stream)
+        return self.insulation(d_band, nrows, ncols, windows, min_diag, stream, factor, first_bin, True)
 
     def dots_into(self, d_band, nrows, ncols, w, p, min_diag, min_count, scale, d_cand, d_sums, stream=None):
         """enqueues the dot kernel (modle_pixels_dots): into the caller-owned device array `d_cand`
@@ -508,23 +511,22 @@ class Extractor:
               int(min_count), ptr, d_cand, d_sums, _stream_ptr(stream))
         del keep
 
-    def dots(self, d_band, nrows, ncols, w, p, min_diag, min_count, scale, bin_offset=0, stream=None):
+    def dots(self, d_band, nrows, ncols, w, p, min_diag, min_count, scale, bin_offset=0, stream=None, factor=1,
+             first_bin=0, coarse=None):
         """the candidates as Pixels, what extract returns of the candidate band
         (modle_pixels_dots_to_host)"""
-        keep, ptr = _scale_table(scale, nrows)
-        return self._to_host(self._L.modle_pixels_dots_to_host, lambda: int(ncols), d_band, int(nrows), int(ncols),
-                             int(w), int(p), int(min_diag), int(min_count), ptr, int(bin_offset), stream=stream)
+        fn, band, shape = self._form("dots_", d_band, nrows, ncols, factor, first_bin, coarse)
+        keep, ptr = _scale_table(scale, shape()[0])
+        return self._to_host(fn, shape, *band, int(w), int(p), int(min_diag), int(min_count), ptr, int(bin_offset),
+                             stream=stream)
 
     def coarse_dots(self, d_band, nrows, ncols, factor, first_bin, w, p, min_diag, min_count, scale, bin_offset=0,
                     stream=None):
         """`dots` of the band at `factor` times its bin size, coarsened on the device
         (modle_pixels_coarse_dots_to_host): `w`, `p`, `min_diag` count coarse bins, `scale` is
         float64 [4, nrows'] of coarse_shape and `bin_offset` counts coarse bins"""
-        nr, nc = coarse_shape(nrows, ncols, factor, first_bin)
-        keep, ptr = _scale_table(scale, nr)
-        return self._to_host(self._L.modle_pixels_coarse_dots_to_host, lambda: nc, d_band, int(nrows), int(ncols),
-                             int(factor), int(first_bin), int(w), int(p), int(min_diag), int(min_count), ptr,
-                             int(bin_offset), stream=stream)
+        return self.dots(d_band, nrows, ncols, w, p, min_diag, min_count, scale, bin_offset, stream, factor,
+                         first_bin, True)
 
     def pileup_into(self, d_band, nrows, ncols, flank, d_bin1, d_bin2, n, d_pile, d_n_used=None, bin_offset=0,
                     stream=None):
@@ -534,30 +536,25 @@ class Extractor:
         _call(self._L.modle_pixels_pileup, self._h, d_band, int(nrows), int(ncols), _flank(flank), int(bin_offset),
               d_bin1, d_bin2, int(n), d_pile, d_n_used, _stream_ptr(stream))
 
-    def _pileup(self, fn, flank, bin1, bin2, bin_offset, *args, stream=None):
-        """a to-host form `fn(handle, *args, flank, bin_offset, anchors, n, two pointers, stream, err)`:
-        (pile as a numpy uint64[S, S] copy, n_used)"""
+    def pileup(self, d_band, nrows, ncols, flank, bin1, bin2, bin_offset=0, stream=None, factor=1, first_bin=0,
+               coarse=None):
+        """(pile, n_used): the sum of the (2 * flank + 1)^2 windows of the symmetric matrix around the
+        accepted ones of the host anchors (bin1[t] - bin_offset, bin2[t] - bin_offset), numpy
+        uint64[S, S], and how many were accepted (pileup_accepts), summed on the device
+        (modle_pixels_pileup_to_host)"""
+        fn, band, _ = self._form("pileup_", d_band, nrows, ncols, factor, first_bin, coarse)
         keep, p1, p2, n = _anchors(bin1, bin2)
         pp, pn = C.c_void_p(), C.c_void_p()
-        _call(fn, self._h, *args, _flank(flank), int(bin_offset), p1, p2, n, C.byref(pp), C.byref(pn),
+        _call(fn, self._h, *band, _flank(flank), int(bin_offset), p1, p2, n, C.byref(pp), C.byref(pn),
               _stream_ptr(stream))
         del keep
         s = 2 * int(flank) + 1
         return _host_array(pp.value, s * s, np.uint64).reshape(s, s), int(_host_array(pn.value, 1, np.uint64)[0])
 
-    def pileup(self, d_band, nrows, ncols, flank, bin1, bin2, bin_offset=0, stream=None):
-        """(pile, n_used): the sum of the (2 * flank + 1)^2 windows of the symmetric matrix around the
-        accepted ones of the host anchors (bin1[t] - bin_offset, bin2[t] - bin_offset), numpy
-        uint64[S, S], and how many were accepted (pileup_accepts), summed on the device
-        (modle_pixels_pileup_to_host)"""
-        return self._pileup(self._L.modle_pixels_pileup_to_host, flank, bin1, bin2, bin_offset, d_band, int(nrows),
-                            int(ncols), stream=stream)
-
     def coarse_pileup(self, d_band, nrows, ncols, factor, first_bin, flank, bin1, bin2, bin_offset=0, stream=None):
         """`pileup` of the band at `factor` times its bin size, coarsened on the device
         (modle_pixels_coarse_pileup_to_host): `flank` and the anchors count coarse bins"""
-        return self._pileup(self._L.modle_pixels_coarse_pileup_to_host, flank, bin1, bin2, bin_offset, d_band,
-                            int(nrows), int(ncols), int(factor), int(first_bin), stream=stream)
+        return self.pileup(d_band, nrows, ncols, flank, bin1, bin2, bin_offset, stream, factor, first_bin, True)
 
     def sample_into(self, d_band, nrows, ncols, threshold, seed, stats, d_kept, d_rest=None, salt=0, bin_offset=0,
                     stream=None):
@@ -577,7 +574,7 @@ class Extractor:
         band: counted, sampled into a scratch band of the context and extracted on the device
         (modle_pixels_sample_to_host).  The total is binomial around threshold / 2^32 of the band's sum."""
         threshold, seed, salt = _draw(threshold, seed, salt)
-        return self._to_host(self._L.modle_pixels_sample_to_host, lambda: int(ncols), d_band, int(nrows), int(ncols),
+        return self._to_host(self._L.modle_pixels_sample_to_host, lambda: (int(nrows), int(ncols)), d_band, int(nrows), int(ncols),
                              int(bin_offset), threshold, seed, salt, SAMPLE_REST if rest else SAMPLE_KEPT,
                              stream=stream)
 

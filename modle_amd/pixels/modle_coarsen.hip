@@ -117,6 +117,15 @@ int coarsen_impl(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
 
 }  // namespace
 
+int modle_pixels_detail::coarsen_to_scratch(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                                            uint64_t ncols, uint64_t factor, uint64_t first_bin, uint64_t nr,
+                                            uint64_t nc, hipStream_t stream, char* err, size_t errlen) {
+  PIX_TRY(hipSetDevice(h->device));
+  const int rc = h->coarse.ensure(nr * nc + 1, err, errlen);
+  if (rc != MODLE_PIXELS_OK) return rc;
+  return coarsen_impl(h, d_band, nrows, ncols, factor, first_bin, h->coarse.dev, nr, nc, stream, err, errlen);
+}
+
 extern "C" int modle_pixels_coarse_shape(uint64_t nrows, uint64_t ncols, uint64_t factor, uint64_t first_bin,
                                          uint64_t* nrows_out, uint64_t* ncols_out) {
   if (nrows_out == nullptr || ncols_out == nullptr || bad_coarsen_args(nrows, ncols, factor))
@@ -149,8 +158,10 @@ extern "C" int modle_pixels_coarse_to_host(modle_pixels_handle* h, const uint32_
                                            const int32_t** count, const int64_t** bin1_offset,
                                            modle_pixels_stats* stats, void* stream, char* err,
                                            size_t errlen) {
-  if (h == nullptr || d_band == nullptr || bin1 == nullptr || bin2 == nullptr || count == nullptr ||
-      bin1_offset == nullptr || stats == nullptr || bin_offset < 0 || bad_coarsen_args(nrows, ncols, factor)) {
+  uint64_t nr = 0, nc = 0;
+  if (h == nullptr || d_band == nullptr ||
+      modle_pixels_detail::bad_pixel_outputs(bin1, bin2, count, bin1_offset, stats, bin_offset) ||
+      modle_pixels_coarse_shape(nrows, ncols, factor, first_bin, &nr, &nc) != MODLE_PIXELS_OK) {
     modle_pixels_detail::set_err(
         err, errlen, "modle_pixels_coarse_to_host: invalid argument (factor >= 2, 0 < nrows <= ncols)");
     return MODLE_PIXELS_ERR_ARG;
@@ -158,14 +169,9 @@ extern "C" int modle_pixels_coarse_to_host(modle_pixels_handle* h, const uint32_
   *bin1 = *bin2 = nullptr;
   *count = nullptr;
   *bin1_offset = nullptr;
-  uint64_t nr = 0, nc = 0;
-  coarse_shape(nrows, ncols, factor, first_bin, &nr, &nc);
-  const uint64_t words = nr * nc + 1;
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  PIX_TRY(hipSetDevice(h->device));
-  int rc = h->coarse.ensure(words, err, errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  rc = coarsen_impl(h, d_band, nrows, ncols, factor, first_bin, h->coarse.dev, nr, nc, st, err, errlen);
+  const int rc = modle_pixels_detail::coarsen_to_scratch(h, d_band, nrows, ncols, factor, first_bin, nr, nc, st, err,
+                                                         errlen);
   if (rc != MODLE_PIXELS_OK) return rc;
   return modle_pixels_detail::to_host(h, h->coarse.dev, nr, nc, bin_offset, bin1, bin2, count, bin1_offset, stats,
                                       st, err, errlen);

@@ -165,8 +165,7 @@ extern "C" int modle_pixels_dense_tiles(modle_pixels_handle* h, const uint32_t* 
     set_err(err, errlen, "modle_pixels_dense_tiles: out_words is smaller than count * size * size");
     return MODLE_PIXELS_ERR_ARG;
   }
-  const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_band), o0 = reinterpret_cast<uintptr_t>(d_out);
-  if (o0 < b0 + (nrows * ncols + 1) * 4 && b0 < o0 + words * 4) {
+  if (modle_pixels_detail::overlap(d_out, words * 4, d_band, modle_pixels_detail::band_bytes(nrows, ncols))) {
     set_err(err, errlen, "modle_pixels_dense_tiles: d_out overlaps the band");
     return MODLE_PIXELS_ERR_ARG;
   }

@@ -156,6 +156,8 @@ __global__ __launch_bounds__(kDotThreads) void pixels_dots(const uint32_t* __res
   }
 }
 
+using modle_pixels_detail::bad_pixel_outputs;
+using modle_pixels_detail::overlap;
 using modle_pixels_detail::set_err;
 
 constexpr const char* kRule =
@@ -209,8 +211,6 @@ int dots_impl(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, ui
   return MODLE_PIXELS_OK;
 }
 
-bool overlap(uintptr_t a, uint64_t na, uintptr_t b, uint64_t nb) { return a < b + nb && b < a + na; }
-
 // the candidates of the band `d_band` into the scratch band of the context, then count / scan / extract
 int dots_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols, uint64_t w,
                  uint64_t p, uint64_t min_diag, uint64_t min_count, const double* scale, int64_t bin_offset,
@@ -236,11 +236,9 @@ extern "C" int modle_pixels_dots(modle_pixels_handle* h, const uint32_t* d_band,
     set_err(err, errlen, std::string("modle_pixels_dots: invalid argument ") + kRule);
     return MODLE_PIXELS_ERR_ARG;
   }
-  const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_band), c0 = reinterpret_cast<uintptr_t>(d_cand),
-                  s0 = reinterpret_cast<uintptr_t>(d_sums);
-  const uint64_t nb = (nrows * ncols + 1) * 4, ns = nrows * ncols * 32;
-  if ((d_cand != nullptr && overlap(c0, nb, b0, nb)) || (d_sums != nullptr && overlap(s0, ns, b0, nb)) ||
-      (d_cand != nullptr && d_sums != nullptr && overlap(c0, nb, s0, ns))) {
+  const uint64_t nb = modle_pixels_detail::band_bytes(nrows, ncols), ns = nrows * ncols * 32;
+  if ((d_cand != nullptr && overlap(d_cand, nb, d_band, nb)) || (d_sums != nullptr && overlap(d_sums, ns, d_band, nb)) ||
+      (d_cand != nullptr && d_sums != nullptr && overlap(d_cand, nb, d_sums, ns))) {
     set_err(err, errlen, "modle_pixels_dots: an output overlaps the band or the other output");
     return MODLE_PIXELS_ERR_ARG;
   }
@@ -254,8 +252,7 @@ extern "C" int modle_pixels_dots_to_host(modle_pixels_handle* h, const uint32_t*
                                          const int64_t** bin1, const int64_t** bin2, const int32_t** count,
                                          const int64_t** bin1_offset, modle_pixels_stats* stats, void* stream,
                                          char* err, size_t errlen) {
-  if (h == nullptr || d_band == nullptr || bin1 == nullptr || bin2 == nullptr || count == nullptr ||
-      bin1_offset == nullptr || stats == nullptr || bin_offset < 0 ||
+  if (h == nullptr || d_band == nullptr || bad_pixel_outputs(bin1, bin2, count, bin1_offset, stats, bin_offset) ||
       bad_dots(nrows, ncols, w, p, min_diag, min_count, scale, true)) {
     set_err(err, errlen, std::string("modle_pixels_dots_to_host: invalid argument ") + kRule);
     return MODLE_PIXELS_ERR_ARG;
@@ -273,20 +270,17 @@ extern "C" int modle_pixels_coarse_dots_to_host(modle_pixels_handle* h, const ui
                                                 void* stream, char* err, size_t errlen) {
   uint64_t nr = 0, nc = 0;
   // (modle_pixels_coarse_shape refuses what modle_pixels_coarsen refuses of shape and factor)
-  if (h == nullptr || d_band == nullptr || bin1 == nullptr || bin2 == nullptr || count == nullptr ||
-      bin1_offset == nullptr || stats == nullptr || bin_offset < 0 ||
+  if (h == nullptr || d_band == nullptr || bad_pixel_outputs(bin1, bin2, count, bin1_offset, stats, bin_offset) ||
       modle_pixels_coarse_shape(nrows, ncols, factor, first_bin, &nr, &nc) != MODLE_PIXELS_OK ||
       bad_dots(nr, nc, w, p, min_diag, min_count, scale, true)) {
     set_err(err, errlen, std::string("modle_pixels_coarse_dots_to_host: invalid argument (factor >= 2; of the "
                                      "coarse band:) ") + kRule);
     return MODLE_PIXELS_ERR_ARG;
   }
-  PIX_TRY(hipSetDevice(h->device));
-  int rc = h->coarse.ensure(nr * nc + 1, err, errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  rc = modle_pixels_coarsen(h, d_band, nrows, ncols, factor, first_bin, h->coarse.dev, nr * nc + 1, stream, err,
-                            errlen);
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = modle_pixels_detail::coarsen_to_scratch(h, d_band, nrows, ncols, factor, first_bin, nr, nc, st, err,
+                                                         errlen);
   if (rc != MODLE_PIXELS_OK) return rc;
   return dots_to_host(h, h->coarse.dev, nr, nc, w, p, min_diag, min_count, scale, bin_offset, bin1, bin2, count,
-                      bin1_offset, stats, static_cast<hipStream_t>(stream), err, errlen);
+                      bin1_offset, stats, st, err, errlen);
 }

@@ -203,8 +203,8 @@ extern "C" int modle_pixels_insulation(modle_pixels_handle* h, const uint32_t* d
     set_err(err, errlen, std::string("modle_pixels_insulation: invalid argument ") + kRule);
     return MODLE_PIXELS_ERR_ARG;
   }
-  const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_band), o0 = reinterpret_cast<uintptr_t>(d_out);
-  if (o0 < b0 + (nrows * ncols + 1) * 4 && b0 < o0 + n_windows * ncols * 8) {
+  if (modle_pixels_detail::overlap(d_out, n_windows * ncols * 8, d_band,
+                                   modle_pixels_detail::band_bytes(nrows, ncols))) {
     set_err(err, errlen, "modle_pixels_insulation: the output overlaps the band");
     return MODLE_PIXELS_ERR_ARG;
   }
@@ -242,12 +242,9 @@ extern "C" int modle_pixels_coarse_insulation_to_host(modle_pixels_handle* h, co
                                      "of the coarse band:) ") + kRule);
     return MODLE_PIXELS_ERR_ARG;
   }
-  PIX_TRY(hipSetDevice(h->device));
-  int rc = h->coarse.ensure(nr * nc + 1, err, errlen);
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = modle_pixels_detail::coarsen_to_scratch(h, d_band, nrows, ncols, factor, first_bin, nr, nc, st, err,
+                                                         errlen);
   if (rc != MODLE_PIXELS_OK) return rc;
-  rc = modle_pixels_coarsen(h, d_band, nrows, ncols, factor, first_bin, h->coarse.dev, nr * nc + 1, stream, err,
-                            errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  return insulation_to_host(h, h->coarse.dev, nr, nc, windows, n_windows, min_diag, ins_sum,
-                            static_cast<hipStream_t>(stream), err, errlen);
+  return insulation_to_host(h, h->coarse.dev, nr, nc, windows, n_windows, min_diag, ins_sum, st, err, errlen);
 }

@@ -114,16 +114,12 @@ __global__ __launch_bounds__(kDepth) void pixels_marginals(const uint32_t* __res
   }
 }
 
+using modle_pixels_detail::overlap;
 using modle_pixels_detail::set_err;
 
 // what the forms on the fine band refuse, whatever their outputs
 int bad_marginals_args(const modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols) {
   return h == nullptr || d_band == nullptr || nrows == 0 || modle_pixels_detail::bad_shape(nrows, ncols);
-}
-
-bool overlaps_band(const uint32_t* d_band, uint64_t nrows, uint64_t ncols, const void* out, uint64_t n) {
-  const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_band), o0 = reinterpret_cast<uintptr_t>(out);
-  return o0 < b0 + (nrows * ncols + 1) * 4 && b0 < o0 + n * 8;
 }
 
 // Clears the context's nrows + ncols sums (diag_sum first, then coverage) and enqueues the kernel;
@@ -172,8 +168,9 @@ extern "C" int modle_pixels_marginals(modle_pixels_handle* h, const uint32_t* d_
     set_err(err, errlen, "modle_pixels_marginals: invalid argument (0 < nrows <= ncols, an output)");
     return MODLE_PIXELS_ERR_ARG;
   }
-  if ((d_diag_sum != nullptr && overlaps_band(d_band, nrows, ncols, d_diag_sum, nrows)) ||
-      (d_coverage != nullptr && overlaps_band(d_band, nrows, ncols, d_coverage, ncols))) {
+  const uint64_t nb = modle_pixels_detail::band_bytes(nrows, ncols);
+  if ((d_diag_sum != nullptr && overlap(d_diag_sum, nrows * 8, d_band, nb)) ||
+      (d_coverage != nullptr && overlap(d_coverage, ncols * 8, d_band, nb))) {
     set_err(err, errlen, "modle_pixels_marginals: an output overlaps the band");
     return MODLE_PIXELS_ERR_ARG;
   }
@@ -217,12 +214,9 @@ extern "C" int modle_pixels_coarse_marginals_to_host(modle_pixels_handle* h, con
             "modle_pixels_coarse_marginals_to_host: invalid argument (factor >= 2, 0 < nrows <= ncols, an output)");
     return MODLE_PIXELS_ERR_ARG;
   }
-  PIX_TRY(hipSetDevice(h->device));
-  int rc = h->coarse.ensure(nr * nc + 1, err, errlen);
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = modle_pixels_detail::coarsen_to_scratch(h, d_band, nrows, ncols, factor, first_bin, nr, nc, st, err,
+                                                         errlen);
   if (rc != MODLE_PIXELS_OK) return rc;
-  rc = modle_pixels_coarsen(h, d_band, nrows, ncols, factor, first_bin, h->coarse.dev, nr * nc + 1, stream, err,
-                            errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  return marginals_to_host(h, h->coarse.dev, nr, nc, min_diag, diag_sum, coverage,
-                           static_cast<hipStream_t>(stream), err, errlen);
+  return marginals_to_host(h, h->coarse.dev, nr, nc, min_diag, diag_sum, coverage, st, err, errlen);
 }

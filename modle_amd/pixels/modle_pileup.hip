@@ -152,6 +152,7 @@ __global__ __launch_bounds__(4 * kSumCells) void pixels_pileup_sum(const u64* __
     *n_used = sum;
 }
 
+using modle_pixels_detail::overlap;
 using modle_pixels_detail::set_err;
 
 constexpr const char* kRule =
@@ -163,8 +164,6 @@ bool bad_pileup(uint64_t nrows, uint64_t ncols, uint64_t f, uint64_t n) {
   return nrows == 0 || modle_pixels_detail::bad_shape(nrows, ncols) || f > MODLE_PIXELS_MAX_PILEUP_FLANK ||
          2 * f + 1 > nrows || n >= (uint64_t{1} << 31);
 }
-
-bool overlap(uintptr_t a, uint64_t na, uintptr_t b, uint64_t nb) { return na != 0 && nb != 0 && a < b + nb && b < a + na; }
 
 // enqueues the two kernels on checked arguments; the anchors and the outputs are device arrays
 int pileup_impl(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols, uint64_t f,
@@ -248,12 +247,11 @@ extern "C" int modle_pixels_pileup(modle_pixels_handle* h, const uint32_t* d_ban
     set_err(err, errlen, std::string("modle_pixels_pileup: invalid argument ") + kRule);
     return MODLE_PIXELS_ERR_ARG;
   }
-  const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_band), p0 = reinterpret_cast<uintptr_t>(d_pile),
-                  u0 = reinterpret_cast<uintptr_t>(d_n_used), a1 = reinterpret_cast<uintptr_t>(d_bin1),
-                  a2 = reinterpret_cast<uintptr_t>(d_bin2);
-  const uint64_t nb = (nrows * ncols + 1) * 4, np = (2 * flank + 1) * (2 * flank + 1) * 8, nu = d_n_used != nullptr ? 8 : 0;
-  if (overlap(p0, np, b0, nb) || overlap(p0, np, a1, n * 8) || overlap(p0, np, a2, n * 8) || overlap(u0, nu, b0, nb) ||
-      overlap(u0, nu, a1, n * 8) || overlap(u0, nu, a2, n * 8) || overlap(u0, nu, p0, np)) {
+  const uint64_t nb = modle_pixels_detail::band_bytes(nrows, ncols), np = (2 * flank + 1) * (2 * flank + 1) * 8,
+                 nu = d_n_used != nullptr ? 8 : 0, na = n * 8;
+  if (overlap(d_pile, np, d_band, nb) || overlap(d_pile, np, d_bin1, na) || overlap(d_pile, np, d_bin2, na) ||
+      overlap(d_n_used, nu, d_band, nb) || overlap(d_n_used, nu, d_bin1, na) || overlap(d_n_used, nu, d_bin2, na) ||
+      overlap(d_n_used, nu, d_pile, np)) {
     set_err(err, errlen, "modle_pixels_pileup: an output overlaps the band, the anchors or the other output");
     return MODLE_PIXELS_ERR_ARG;
   }
@@ -292,12 +290,9 @@ extern "C" int modle_pixels_coarse_pileup_to_host(modle_pixels_handle* h, const 
                                      "coarse band:) ") + kRule);
     return MODLE_PIXELS_ERR_ARG;
   }
-  PIX_TRY(hipSetDevice(h->device));
-  int rc = h->coarse.ensure(nr * nc + 1, err, errlen);
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = modle_pixels_detail::coarsen_to_scratch(h, d_band, nrows, ncols, factor, first_bin, nr, nc, st, err,
+                                                         errlen);
   if (rc != MODLE_PIXELS_OK) return rc;
-  rc = modle_pixels_coarsen(h, d_band, nrows, ncols, factor, first_bin, h->coarse.dev, nr * nc + 1, stream, err,
-                            errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  return pileup_to_host(h, h->coarse.dev, nr, nc, flank, bin_offset, bin1, bin2, n, pile, n_used,
-                        static_cast<hipStream_t>(stream), err, errlen);
+  return pileup_to_host(h, h->coarse.dev, nr, nc, flank, bin_offset, bin1, bin2, n, pile, n_used, st, err, errlen);
 }

@@ -305,8 +305,8 @@ extern "C" int modle_pixels_to_host(modle_pixels_handle* h, const uint32_t* d_ba
                                     const int64_t** bin2, const int32_t** count,
                                     const int64_t** bin1_offset, modle_pixels_stats* stats, void* stream,
                                     char* err, size_t errlen) {
-  if (h == nullptr || bin1 == nullptr || bin2 == nullptr || count == nullptr || bin1_offset == nullptr ||
-      stats == nullptr || (d_band == nullptr && ncols != 0) || bad_shape(nrows, ncols) || bin_offset < 0) {
+  if (h == nullptr || modle_pixels_detail::bad_pixel_outputs(bin1, bin2, count, bin1_offset, stats, bin_offset) ||
+      (d_band == nullptr && ncols != 0) || bad_shape(nrows, ncols)) {
     set_err(err, errlen, "modle_pixels_to_host: invalid argument (0 < nrows <= ncols, or both 0)");
     return MODLE_PIXELS_ERR_ARG;
   }

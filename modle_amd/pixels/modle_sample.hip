@@ -154,6 +154,7 @@ __global__ __launch_bounds__(kThreads) void pixels_sample(const u32* __restrict_
   }
 }
 
+using modle_pixels_detail::overlap;
 using modle_pixels_detail::set_err;
 
 constexpr u64 kTwo32 = 1ull << 32;
@@ -163,8 +164,6 @@ Draw make_draw(u64 seed, u32 salt, u64 threshold) {
 }
 
 int mode_of(u64 threshold) { return threshold == 0 ? kKeepNone : threshold == kTwo32 ? kKeepAll : kDrawMode; }
-
-bool overlap(uintptr_t a, u64 na, uintptr_t b, u64 nb) { return a < b + nb && b < a + na; }
 
 constexpr const char* kRule =
     "(0 < nrows <= ncols, an output, threshold <= 2^32, a band, its stats; no output overlaps the band or the other)";
@@ -238,11 +237,9 @@ extern "C" int modle_pixels_sample(modle_pixels_handle* h, const uint32_t* d_ban
                   h == nullptr || d_band == nullptr || stats == nullptr || (d_kept == nullptr && d_rest == nullptr),
                   err, errlen);
   if (rc != MODLE_PIXELS_OK) return rc;
-  const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_band), k0 = reinterpret_cast<uintptr_t>(d_kept),
-                  r0 = reinterpret_cast<uintptr_t>(d_rest);
-  const u64 nb = (nrows * ncols + 1) * 4;
-  if ((d_kept != nullptr && overlap(k0, nb, b0, nb)) || (d_rest != nullptr && overlap(r0, nb, b0, nb)) ||
-      (d_kept != nullptr && d_rest != nullptr && overlap(k0, nb, r0, nb))) {
+  const u64 nb = modle_pixels_detail::band_bytes(nrows, ncols);
+  if ((d_kept != nullptr && overlap(d_kept, nb, d_band, nb)) || (d_rest != nullptr && overlap(d_rest, nb, d_band, nb)) ||
+      (d_kept != nullptr && d_rest != nullptr && overlap(d_kept, nb, d_rest, nb))) {
     set_err(err, errlen, "modle_pixels_sample: an output overlaps the band or the other output");
     return MODLE_PIXELS_ERR_ARG;
   }
@@ -258,9 +255,10 @@ extern "C" int modle_pixels_sample_to_host(modle_pixels_handle* h, const uint32_
                                            const int32_t** count, const int64_t** bin1_offset,
                                            modle_pixels_stats* stats_out, void* stream, char* err, size_t errlen) {
   int rc = refuse("modle_pixels_sample_to_host", nrows, ncols, bin_offset, threshold,
-                  h == nullptr || d_band == nullptr || stats_out == nullptr || bin1 == nullptr || bin2 == nullptr ||
-                      count == nullptr || bin1_offset == nullptr || (which != MODLE_PIXELS_SAMPLE_KEPT &&
-                                                                     which != MODLE_PIXELS_SAMPLE_REST),
+                  // (a negative bin_offset is refuse()'s own, with the range code: 0 stands in for it here)
+                  h == nullptr || d_band == nullptr ||
+                      modle_pixels_detail::bad_pixel_outputs(bin1, bin2, count, bin1_offset, stats_out, 0) ||
+                      (which != MODLE_PIXELS_SAMPLE_KEPT && which != MODLE_PIXELS_SAMPLE_REST),
                   err, errlen);
   if (rc != MODLE_PIXELS_OK) return rc;
   *bin1 = *bin2 = nullptr;

@@ -30,6 +30,32 @@ int to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint
             const int64_t** bin1_offset, modle_pixels_stats* stats, hipStream_t stream, char* err,
             size_t errlen);
 
+// The first step of every modle_pixels_coarse_*_to_host, on arguments modle_pixels_coarse_shape accepted with
+// the shape (nr, nc): sets the device, makes room in h->coarse and enqueues the coarsening into h->coarse.dev
+// (modle_coarsen.hip).  The fine form of the analysis on (h->coarse.dev, nr, nc) follows.  (Hidden: the
+// library's dynamic symbols stay as they are.)
+__attribute__((visibility("hidden")))
+int coarsen_to_scratch(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols,
+                       uint64_t factor, uint64_t first_bin, uint64_t nr, uint64_t nc, hipStream_t stream,
+                       char* err, size_t errlen);
+
+// the bytes of a band: its nrows * ncols words and the trailing word
+inline uint64_t band_bytes(uint64_t nrows, uint64_t ncols) { return (nrows * ncols + 1) * 4; }
+
+// Whether two byte ranges share a byte; a range that ends where the other begins does not, and an empty range
+// overlaps nothing (only modle_pixels_pileup passes an empty one: every other size is non-zero where this is called).
+inline bool overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a_bytes != 0 && b_bytes != 0 && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+// what the forms that return pixels refuse of their five outputs and of the id of the first bin
+inline bool bad_pixel_outputs(const int64_t** bin1, const int64_t** bin2, const int32_t** count,
+                              const int64_t** bin1_offset, const modle_pixels_stats* stats, int64_t bin_offset) {
+  return bin1 == nullptr || bin2 == nullptr || count == nullptr || bin1_offset == nullptr || stats == nullptr ||
+         bin_offset < 0;
+}
+
 }  // namespace modle_pixels_detail
 
 #define PIX_TRY(call)                                                                           \
