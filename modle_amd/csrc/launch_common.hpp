@@ -62,19 +62,30 @@ inline const char* check_limits(const modle_hip_config& c, uint64_t start, uint6
 }
 
 // Size class a set-up NEEDS (sim_types.h; modle_hip_size_class adds the environment's override).
-// NARROW (0): LEF ids and moves fit 16 bits.  Ids: fewer than 65 536 LEFs.  Moves: a draw is speed + std * z;
-// the move adjustment (reference: simulation.cpp:350-407) raises a move by at most one per link of a chain of
-// consecutive units, i.e. by less than the number of LEFs; clamping and the collision passes only shorten
-// moves.  z is bounded at 40 here -- the stream cannot produce it (the ziggurat's tail would need a uniform
-// below 2^-1000) -- and the kernel ends a cell with ERR_MOVE_RANGE should a move ever exceed the limit, instead
-// of truncating it.
+// NARROW (0): LEF ids and moves fit 16 bits.  Ids: fewer than 65 536 LEFs.  Moves: a draw is speed + std * z,
+// z bounded at 40 here -- the stream cannot produce it (the ziggurat's tail would need a uniform below 2^-1000).
+// Two things raise a move above its draw:
+//  - the move adjustment (reference: simulation.cpp:350-407), by at most one per link of a chain of consecutive
+//    units of the unit's direction, i.e. by less than the number of LEFs: speed + 40 std + LEFs + 2;
+//  - the correction for a primary LEF-LEF collision whose other unit stays stalled by a barrier (reference:
+//    simulation_correct_moves.cpp:83-96, 105-119): the unit is put next to the stalled one, whatever it drew
+//    itself.  The pair was tested with the moves both units had then, distance < rev move + fwd move, so the new
+//    move stays below the SUM of a rev and a fwd move: a rev unit drawn at 1 kb that meets a stalled fwd unit of
+//    a 64.9 kb direction may move 65.8 kb.  The chains that raised the two adjusted moves are fwd units upstream
+//    of the pair and rev units downstream of it, units of different LEFs (a LEF's rev unit is not downstream of
+//    its fwd unit), so both raises together stay below the number of LEFs:
+//    rev speed + fwd speed + 40 (rev std + fwd std) + LEFs.
+// Clamping and every other collision pass only shorten moves.  The kernel ends a cell with ERR_MOVE_RANGE should
+// a move ever exceed the limit, instead of truncating it.
 inline int size_class_required(const modle_hip_config& c, uint64_t max_lefs) {
   if (max_lefs >= 65536) return 1;
-  const double speed = static_cast<double>(std::max(std::max(c.rev_extrusion_speed, c.fwd_extrusion_speed),
-                                                    std::max(c.rev_extrusion_speed_burnin, c.fwd_extrusion_speed_burnin)));
-  const double sd = std::max(std::fabs(c.rev_extrusion_speed_std), std::fabs(c.fwd_extrusion_speed_std));
-  const double bound = speed + 40.0 * sd + static_cast<double>(max_lefs) + 2.0;
-  return bound <= 65533.0 ? 0 : 1;  // (MOVE_LIMIT of the NARROW class)
+  const double rev = static_cast<double>(std::max(c.rev_extrusion_speed, c.rev_extrusion_speed_burnin));
+  const double fwd = static_cast<double>(std::max(c.fwd_extrusion_speed, c.fwd_extrusion_speed_burnin));
+  const double rev_sd = std::fabs(c.rev_extrusion_speed_std), fwd_sd = std::fabs(c.fwd_extrusion_speed_std);
+  const double lefs = static_cast<double>(max_lefs);
+  const double own = std::max(rev, fwd) + 40.0 * std::max(rev_sd, fwd_sd) + lefs + 2.0;
+  const double pair = rev + fwd + 40.0 * (rev_sd + fwd_sd) + lefs;
+  return std::max(own, pair) <= 65533.0 ? 0 : 1;  // (MOVE_LIMIT of the NARROW class)
 }
 
 inline uint32_t pos_to_dev(uint64_t v) {

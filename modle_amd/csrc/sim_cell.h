@@ -45,6 +45,9 @@ struct Cell {
   bool disp_valid;
   // upper bound of the fwd moves of this epoch (0xFFFFFFFF: unknown), set by the move adjustment
   u32 max_fwd_move;
+  // ... and of the rev moves: detect_primary checks the moves it stores only when a rev and a fwd move together
+  // can exceed what the NARROW class holds
+  u32 max_rev_move;
   // ws.r_rank / ws.f_rank ([0] rev, [1] fwd) hold the complete inverse permutation.  The rank
   // update of the epoch loop does not write it (one scattered store per unit and epoch): the
   // sparse consumers -- bind, release, fix_secondary -- get the ranks of the few LEFs they need

@@ -1160,7 +1160,9 @@ struct PrimaryBlk {
   u32 sp[PRIMARY_SLICE_Q];
 };
 
-MODLE_DEV_NOINLINE void detect_primary(Cell& c, BoundaryCounts bc, bool fuse_correct) {
+// `CHECK`: the corrected moves are tested against MOVE_LIMIT (see detect_primary below)
+template <bool CHECK>
+MODLE_DEV_NOINLINE void detect_primary_impl(Cell& c, BoundaryCounts bc, bool fuse_correct) {
   Workspace& ws = c.ws;
   const Params& p = *c.p;
   const Interval& iv = *c.iv;
@@ -1377,6 +1379,7 @@ MODLE_DEV_NOINLINE void detect_primary(Cell& c, BoundaryCounts bc, bool fuse_cor
       np = list_pf(64);
     }
   }
+  bool over = false;  // a corrected move the NARROW class cannot hold
   for (u32 base = 0; base < n_cand; base += 64) {
     const PairRegs q = pcur;
     if (base + 64 < n_cand) {
@@ -1435,7 +1438,9 @@ MODLE_DEV_NOINLINE void detect_primary(Cell& c, BoundaryCounts bc, bool fuse_cor
         } else if (fuse_correct && cw_occurred_as(rc, EV_LEF_BAR)) {
           // fwd unit runs into a rev unit that stays stalled 1 bp downstream of its barrier
           const u32 rev_move_stalled = (R_h - barrier_pos) - 1;
-          ws.f_move[kf] = (R_h - rev_move_stalled) - F_h - 1;
+          const u32 fwd_move_new = (R_h - rev_move_stalled) - F_h - 1;
+          if (CHECK) over = over || fwd_move_new > MOVE_LIMIT;
+          ws.f_move[kf] = fwd_move_new;
         }
       } else if (!rev_occ && fwd_occ) {
         const u32 barrier_pos = fwd_odd ? fwd_other : fbp_s_h;
@@ -1445,10 +1450,13 @@ MODLE_DEV_NOINLINE void detect_primary(Cell& c, BoundaryCounts bc, bool fuse_cor
           both = true;
         } else if (fuse_correct && cw_occurred_as(fc, EV_LEF_BAR)) {
           const u32 fwd_move_stalled = (barrier_pos - F_h) - 1;
-          ws.r_move[k_h] = R_h - (F_h + fwd_move_stalled) - 1;
+          const u32 rev_move_new = R_h - (F_h + fwd_move_stalled) - 1;
+          if (CHECK) over = over || rev_move_new > MOVE_LIMIT;
+          ws.r_move[k_h] = rev_move_new;
         }
       }
       if (both && fuse_correct) {
+        if (CHECK) over = over || R_h - cpos_rev > MOVE_LIMIT || cpos_fwd - F_h > MOVE_LIMIT;
         ws.r_move[k_h] = R_h - cpos_rev;
         ws.f_move[kf] = cpos_fwd - F_h;
       }
@@ -1457,10 +1465,27 @@ MODLE_DEV_NOINLINE void detect_primary(Cell& c, BoundaryCounts bc, bool fuse_cor
       if (hit) handle_hit(q.pf, q.k, q.R, q.F, q.rev_move, q.fwd_move, q.rev_id, q.fwd_id, q.rc, q.fc, q.rbp, q.fbp);
     }
   }
+  if (CHECK && wave::any(over)) c.error = ERR_MOVE_RANGE;
   wave::sync_mem();
 #ifdef MODLE_SUBTIMER_PRIMARY
   c.ph[15] += wave::clock() - t_pass2;  // (pass 2: the listed pairs)
 #endif
+}
+
+// A unit that meets a unit stalled by a barrier is put next to it: a corrected move is bounded by the SUM of the
+// pair's rev and fwd move, not by the unit's own (launch_common.hpp: size_class_required).  The NARROW class tests
+// what it stores only when the largest rev and fwd moves of the epoch together can pass MOVE_LIMIT -- never in a
+// launch the rule has classed NARROW, short of a 40-sigma draw --, in an instance of its own: the instance every
+// epoch of a real chromosome runs carries no test.
+MODLE_DEV void detect_primary(Cell& c, BoundaryCounts bc, bool fuse_correct) {
+  if (NARROW_MOVES) {
+    const u64 reach = static_cast<u64>(wave::uniform(c.max_rev_move)) + wave::uniform(c.max_fwd_move);
+    if (reach > MOVE_LIMIT) {
+      detect_primary_impl<true>(c, bc, fuse_correct);
+      return;
+    }
+  }
+  detect_primary_impl<false>(c, bc, fuse_correct);
 }
 
 // correct_moves_for_primary_lef_lef_collisions (reference: simulation_correct_moves.cpp:53-121)
@@ -1471,6 +1496,7 @@ MODLE_DEV_NOINLINE void correct_moves_primary_standalone(Cell& c) {
   Workspace& ws = c.ws;
   const u32 n = wave::uniform(c.n_active);
   const u32 lane = wave::lane();
+  bool over = false;  // (a move the NARROW class cannot hold: see detect_primary)
   for (u32 base = 0; base < n; base += 64) {
     const u32 k = base + lane;
     if (k < n) {
@@ -1481,10 +1507,13 @@ MODLE_DEV_NOINLINE void correct_moves_primary_standalone(Cell& c) {
         if (cw_occurred_as(fc, EV_LEF_LEF_PRIMARY)) {
           u32 p1, p2;
           lef_lef_collision_pos(ws.r_pos[k], ws.f_pos[kf], ws.r_move[k], ws.f_move[kf], p1, p2);
+          over = over || ws.r_pos[k] - p1 > MOVE_LIMIT || p2 - ws.f_pos[kf] > MOVE_LIMIT;
           ws.r_move[k] = ws.r_pos[k] - p1;
           ws.f_move[kf] = p2 - ws.f_pos[kf];
         } else if (cw_occurred_as(fc, EV_LEF_BAR)) {
-          ws.r_move[k] = ws.r_pos[k] - (ws.f_pos[kf] + ws.f_move[kf]) - 1;
+          const u32 rev_move_new = ws.r_pos[k] - (ws.f_pos[kf] + ws.f_move[kf]) - 1;
+          over = over || rev_move_new > MOVE_LIMIT;
+          ws.r_move[k] = rev_move_new;
         }
       }
     }
@@ -1496,11 +1525,15 @@ MODLE_DEV_NOINLINE void correct_moves_primary_standalone(Cell& c) {
       const u32 fc = ws.f_coll[k];
       if (cw_occurred_as(fc, EV_LEF_LEF_PRIMARY)) {
         const u32 kr = ws.r_rank[cw_index(fc)];
-        if (cw_occurred_as(ws.r_coll[kr], EV_LEF_BAR))
-          ws.f_move[k] = (ws.r_pos[kr] - ws.r_move[kr]) - ws.f_pos[k] - 1;
+        if (cw_occurred_as(ws.r_coll[kr], EV_LEF_BAR)) {
+          const u32 fwd_move_new = (ws.r_pos[kr] - ws.r_move[kr]) - ws.f_pos[k] - 1;
+          over = over || fwd_move_new > MOVE_LIMIT;
+          ws.f_move[k] = fwd_move_new;
+        }
       }
     }
   }
+  if (NARROW_MOVES && wave::any(over)) c.error = ERR_MOVE_RANGE;
   wave::sync_mem();
 }
 

@@ -70,6 +70,7 @@ MODLE_DEV void init_cell(Cell& c, const Params& p, const Interval& iv, const Wor
   c.n_disp[1] = 0;
   c.disp_valid = true;  // (nothing has been ranked yet: nothing can be out of order)
   c.max_fwd_move = 0xFFFFFFFFu;
+  c.max_rev_move = 0xFFFFFFFFu;
   c.n_bound = 0;
   c.inv_valid[0] = true;  // (reset_cell_buffers / run_test_phases write complete permutations)
   c.inv_valid[1] = true;
@@ -313,6 +314,7 @@ MODLE_DEV u32 simulate_cell(const Params& p, const Interval& iv, const Task& tas
       // (a wait that fails -- the host raised the abort word, or the helper reported an error -- ends
       // the cell: what the helper was to deliver is not there)
       c.max_fwd_move = 0xFFFFFFFFu;
+      c.max_rev_move = 0xFFFFFFFFu;
       bool handed = false;
       PHASE(c, 5, handed = pair_wait(c, PAIR_MOVES));
       if (!handed) {

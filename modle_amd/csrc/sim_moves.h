@@ -644,6 +644,7 @@ MODLE_DEV_NOINLINE void adjust_moves_both_x4(Cell& c, const move_t* mv_rev, cons
   // the largest fwd move of the epoch bounds what a fwd unit can contribute to a primary collision
   // (detect_primary's filter pass); unknown when the sequential replay is going to change moves
   c.max_fwd_move = viol_fwd < 0 ? wave::bcast(wave_prefix_max_u32(f.lane_max), 63) : 0xFFFFFFFFu;
+  if (NARROW_MOVES) c.max_rev_move = viol_rev < 0 ? wave::bcast(wave_prefix_max_u32(r.lane_max), 63) : 0xFFFFFFFFu;
 }
 
 // `all_bound`: every active LEF is bound (the epoch loop's invariant at this point)
@@ -663,6 +664,7 @@ MODLE_DEV void phase_adjust_moves_by_id(Cell& c) {
 MODLE_DEV void phase_generate_moves(Cell& c, bool burnin_completed, bool all_bound = true) {
   const Params& p = *c.p;
   c.max_fwd_move = 0xFFFFFFFFu;  // (set by adjust_moves_both_x4 when it runs)
+  c.max_rev_move = 0xFFFFFFFFu;
   if (!all_bound) {
     PHASE(c, 5, generate_moves_dir<false>(c, burnin_completed ? p.rev_speed : p.rev_speed_burnin, p.rev_std);
           generate_moves_dir<true>(c, burnin_completed ? p.fwd_speed : p.fwd_speed_burnin, p.fwd_std);

@@ -223,6 +223,20 @@ MODLE_DEV_NOINLINE void phase_extrude_and_release(Cell& c, bool burnin_completed
       n_rel += static_cast<u32>(wave::popc64(rm));
     }
     wave::sync_lds();
+    if (n > RANK_FILTER_BITS) {
+      // More LEFs than the filter has bits: an id that shares its bit with a candidate had its rank reported too,
+      // hard-stall flag included, and is not in the list above that takes the flag off again.  A flagged entry
+      // is no rank: whoever reads it next (it stayed until the next rank update that rewrites the inverse) went
+      // wrong.  One more sweep, only here: no real chromosome has that many LEFs.
+      wave::sync_mem();
+      for (u32 base = 0; base < n; base += 64) {
+        const u32 i = base + lane;
+        if (i < n) {
+          ws.r_rank[i] &= ~RANK_HARD;
+          ws.f_rank[i] &= ~RANK_HARD;
+        }
+      }
+    }
     c.rel_valid = n_rel <= REL_CAP;
     c.n_rel = c.rel_valid ? n_rel : 0;
 #ifdef MODLE_EMU_TRACE_RANK  // (emulator only: which regime a test exercises)

@@ -13,8 +13,11 @@ f64p = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
 u32p = np.ctypeslib.ndpointer(dtype=np.uint32, flags="C_CONTIGUOUS")
 
 
-def simulate_interval(cfg, start, end, bar_pos, bar_dir, stp_active, stp_inactive, tasks, nrows,
-                      ncols, track_occupancy=True, variant=None):
+def simulate_interval_status(cfg, start, end, bar_pos, bar_dir, stp_active, stp_inactive, tasks, nrows,
+                             ncols, track_occupancy=True, variant=None, force_narrow=False):
+    """`force_narrow`: the NARROW build of the geometry runs the cells whatever class the rule gives them
+    (MODLE_EMU_FORCE_NARROW: a cell whose move the class cannot hold ends with an error).
+    Returns the status of the run (0, or a negative api.ERR_* code) in front of what simulate_interval returns."""
     from phase_backend import WIDE_VARIANT, emu_size_class
 
     # MODLE_EMU_VARIANT=w12: campaigns on the geometry of the 12-wave kernels (tools/emu_fuzz_campaign.py)
@@ -22,7 +25,8 @@ def simulate_interval(cfg, start, end, bar_pos, bar_dir, stp_active, stp_inactiv
         variant = os.environ["MODLE_EMU_VARIANT"]
 
     # the size class the product would run these cells in (NARROW builds refuse WIDE set-ups)
-    if variant in WIDE_VARIANT and emu_size_class(cfg, max(int(t.num_lefs) for t in tasks)) != 0:
+    if (not force_narrow and variant in WIDE_VARIANT
+            and emu_size_class(cfg, max(int(t.num_lefs) for t in tasks)) != 0):
         variant = WIDE_VARIANT[variant]
     L = emu_lib(variant)
     L.emu_simulate_interval.argtypes = [C.POINTER(Config), C.c_uint64, C.c_uint64, u64p, u8p,
@@ -35,11 +39,29 @@ def simulate_interval(cfg, start, end, bar_pos, bar_dir, stp_active, stp_inactiv
     missed = C.c_uint64(0)
     n = len(tasks)
     results = (CellResult * n)()
-    rc = L.emu_simulate_interval(
-        C.byref(cfg), start, end, np.ascontiguousarray(bar_pos, dtype=np.uint64),
-        np.ascontiguousarray(bar_dir, dtype=np.uint8),
-        np.ascontiguousarray(stp_active, dtype=np.float64),
-        np.ascontiguousarray(stp_inactive, dtype=np.float64), len(bar_pos), tasks, n, contacts,
-        nrows, ncols, C.byref(missed), occ.ctypes.data if occ is not None else None, results)
+    old = os.environ.get("MODLE_EMU_FORCE_NARROW")
+    if force_narrow:
+        os.environ["MODLE_EMU_FORCE_NARROW"] = "1"
+    try:
+        rc = L.emu_simulate_interval(
+            C.byref(cfg), start, end, np.ascontiguousarray(bar_pos, dtype=np.uint64),
+            np.ascontiguousarray(bar_dir, dtype=np.uint8),
+            np.ascontiguousarray(stp_active, dtype=np.float64),
+            np.ascontiguousarray(stp_inactive, dtype=np.float64), len(bar_pos), tasks, n, contacts,
+            nrows, ncols, C.byref(missed), occ.ctypes.data if occ is not None else None, results)
+    finally:
+        if force_narrow:
+            if old is None:
+                os.environ.pop("MODLE_EMU_FORCE_NARROW", None)
+            else:
+                os.environ["MODLE_EMU_FORCE_NARROW"] = old
+    return rc, contacts, missed.value, occ, results
+
+
+def simulate_interval(cfg, start, end, bar_pos, bar_dir, stp_active, stp_inactive, tasks, nrows,
+                      ncols, track_occupancy=True, variant=None):
+    rc, contacts, missed, occ, results = simulate_interval_status(
+        cfg, start, end, bar_pos, bar_dir, stp_active, stp_inactive, tasks, nrows, ncols,
+        track_occupancy=track_occupancy, variant=variant)
     assert rc == 0, f"emu_simulate_interval failed: {rc}"
-    return contacts, missed.value, occ, results
+    return contacts, missed, occ, results

@@ -106,6 +106,74 @@ def random_case_v3(seed):
                           lef_densities=(1.0, 5.0, 20.0, 64.0))
 
 
+def random_case_v5(seed):
+    """the top of the NARROW size class's 16-bit ranges (modle_amd/csrc/sim_types.h), which the first four
+    generators stay far below: unequal rev / fwd extrusion speeds up to 65 kb per epoch, no spread or a small one,
+    from a few dozen to tens of thousands of LEFs, the burn-in speed coefficient.  A third of the set-ups sit
+    exactly on the border of the size-class rule (launch_common.hpp: size_class_required: rev speed + fwd speed +
+    40 (rev sd + fwd sd) + LEFs = 65533, the move of a unit put next to a barrier-stalled one), a sixth on the border
+    of the rule as it was before that move was counted (the fast speed + 40 sd + LEFs + 2 = 65533: now WIDE), the
+    rest anywhere below the latter -- so both sides of the border are visited, each in the class the library picks.
+    The cells are kept short: `max_burnin_epochs` is bounded and the contact target is a few dozen epochs."""
+    rng = np.random.default_rng(seed ^ 0x16B17)
+    num_lefs = int(rng.choice([40, 200, 531, 1500, 6000, 20000, 45000]))
+    lefs_per_mbp = float(rng.choice([10.0, 30.0]) if num_lefs <= 1500 else rng.choice([150.0, 600.0]))
+    if num_lefs > 6000:
+        lefs_per_mbp = 600.0  # (at most 75 Mb: the matrices stay small)
+    size = int(round(num_lefs / lefs_per_mbp * 1.0e6))
+    sd_fast, sd_slow = [(0.0, 0.0), (0.0, 0.0), (10.0, 2.0), (120.0, 10.0)][int(rng.integers(0, 4))]
+    coefficient = float(rng.choice([1.0, 1.0, 0.5, 0.9, 1.02]))
+    scale = max(1.0, coefficient)  # (the rule counts the faster of a direction's two speeds)
+    slow = int(rng.choice([200, 1000, 5000]))
+    old_cap = int((65533 - 2 - num_lefs - 40.0 * sd_fast) / scale)
+    new_cap = int((65533 - num_lefs - 40.0 * (sd_fast + sd_slow)) / scale) - slow
+    where = rng.random()
+    if old_cap < 2 * slow:
+        fast = max(1, old_cap)  # (so many LEFs that little is left for the moves)
+        slow = min(slow, fast)
+    elif where < 0.33 and new_cap >= slow:
+        fast = new_cap
+    elif where < 0.5:
+        fast = old_cap
+    else:
+        fast = int(rng.integers(slow, old_cap + 1))
+    if rng.random() < 0.15:
+        slow = fast  # equal speeds
+    fast_is_fwd = bool(rng.random() < 0.5)
+    rev, fwd = (slow, fast) if fast_is_fwd else (fast, slow)
+    rev_sd, fwd_sd = (sd_slow, sd_fast) if fast_is_fwd else (sd_fast, sd_slow)
+    num_cells = 12
+    bin_size, diagonal_width = 5000, 3_000_000
+    ncols = (size + bin_size - 1) // bin_size
+    npixels = min(diagonal_width // bin_size, ncols) * ncols
+    per_epoch = max(1, round(num_lefs * (rev + fwd) / 50_000))
+    epochs = int(rng.choice([8, 30, 80])) if num_lefs <= 6000 else 6
+    skip_burnin = int(rng.random() < 0.2)
+    cfg_kw = dict(
+        num_cells=num_cells,
+        seed=int(rng.integers(0, 2**31)),
+        number_of_lefs_per_mbp=lefs_per_mbp,
+        rev_extrusion_speed=rev, fwd_extrusion_speed=fwd, rev_extrusion_speed_set=1, fwd_extrusion_speed_set=1,
+        rev_extrusion_speed_std=rev_sd, fwd_extrusion_speed_std=fwd_sd,
+        burnin_speed_coefficient=coefficient,
+        probability_of_extrusion_unit_bypass=float(rng.choice([0.0, 0.1, 0.3])),
+        lef_bar_major_collision_pblock=float(rng.choice([1.0, 0.9])),
+        lef_bar_minor_collision_pblock=float(rng.choice([0.0, 0.2])),
+        track_1d_lef_position=int(rng.integers(0, 2)),
+        target_contact_density=epochs * per_epoch * num_cells / npixels,
+        skip_burnin=skip_burnin,
+        simulate_chromosomes_wo_barriers=1,
+        max_burnin_epochs=int(rng.choice([40, 150, 300])) if num_lefs <= 6000 else 40,
+    )
+    cfg = api.make_config(**cfg_kw)
+    if num_lefs > 6000:
+        cfg.burnin_target_epochs_for_lef_activation = 20  # (the transform derives it: a short ramp for the many)
+    chrom = synthetic.synthetic_chromosome(f"chrN{seed}", size, seed=seed,
+                                           with_barriers=bool(rng.random() < 0.9),
+                                           spacing=int(rng.choice([79_564, 25_000])))
+    return _finish(cfg, chrom, cfg_kw, size)
+
+
 def random_case_v4(seed):
     """the burn-in machinery and the stopping rules, which the first three generators keep at their
     defaults: minimum burn-in length, history length and smoothing window of the stability test,

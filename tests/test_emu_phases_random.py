@@ -5,7 +5,7 @@ import functools
 import pytest
 
 from phase_backend import emu_phases
-from phase_random import run_sequences
+from phase_random import NEAR_LIMIT_SEQUENCES, run_sequences
 
 SEQUENCES = [
     (1, 300, 60, {}, False),
@@ -18,6 +18,7 @@ SEQUENCES = [
     (7, 300, 6000, {"minor": 1.0}, False),  # a block that falls back, then 44 ranks that restage the window
     (8, 40, 3000, {}, False),               # default probabilities: the two lists differ
 ]
+SEQUENCES += NEAR_LIMIT_SEQUENCES
 
 
 @pytest.mark.parametrize("seed,n,nb,kw,dense", SEQUENCES)

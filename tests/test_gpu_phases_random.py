@@ -2,7 +2,7 @@
 import pytest
 
 from phase_backend import _advance
-from phase_random import run_sequences
+from phase_random import NEAR_LIMIT_SEQUENCES, run_sequences
 
 pytestmark = pytest.mark.gpu
 
@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
     (6, 40, 3000, {"minor": 1.0}, False),   # one block spans both lists (about 2 400 entries each)
     (7, 300, 6000, {"minor": 1.0}, False),  # a block that falls back, then 44 ranks that restage the window
     (8, 40, 3000, {}, False),               # default probabilities: the two lists differ
-])
+] + NEAR_LIMIT_SEQUENCES)
 def test_random_phases_gpu(oracle, seed, n, nb, kw, dense):
     from modle_amd import api
 
@@ -26,7 +26,7 @@ def test_random_phases_gpu(oracle, seed, n, nb, kw, dense):
 
     def phases(cfg, mask, st, state, skip):
         key = (cfg.probability_of_extrusion_unit_bypass, cfg.lef_bar_major_collision_pblock,
-               cfg.lef_bar_minor_collision_pblock)
+               cfg.lef_bar_minor_collision_pblock, cfg.rev_extrusion_speed, cfg.fwd_extrusion_speed)
         if key not in sims:
             sims[key] = api.Simulator(cfg.copy(), 0)
         return sims[key].test_phases(mask, st, _advance(state, skip))

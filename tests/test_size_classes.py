@@ -33,11 +33,32 @@ def test_the_rule_at_its_borders(monkeypatch):
     assert _size_class(dense, 15933) == 0
     # ids: 65 536 LEFs and more need 32 bits
     assert _size_class(default, 65535) in (0, 1) and _size_class(default, 65536) == 1
-    # moves: speed + 40 sigma + LEFs + 2 must stay within 65 533
-    speed = int(max(default.rev_extrusion_speed, default.fwd_extrusion_speed))
-    sd = float(max(default.rev_extrusion_speed_std, default.fwd_extrusion_speed_std))
-    room = int(65533 - 2 - speed - 40.0 * sd)
+    # moves: a unit put next to a barrier-stalled unit of the other direction moves up to the sum of a rev and a
+    # fwd move: rev speed + fwd speed + 40 (rev sigma + fwd sigma) + LEFs must stay within 65 533 ...
+    rev, fwd = int(default.rev_extrusion_speed), int(default.fwd_extrusion_speed)
+    rev_sd, fwd_sd = float(default.rev_extrusion_speed_std), float(default.fwd_extrusion_speed_std)
+    room = int(65533 - rev - fwd - 40.0 * (rev_sd + fwd_sd))
+    assert room < int(65533 - 2 - max(rev, fwd) - 40.0 * max(rev_sd, fwd_sd))  # (the border of the rule as it was)
     assert _size_class(default, room) == 0 and _size_class(default, room + 1) == 1
+    # ... for unequal speeds too: 1 kb against 64 002 bp with 531 LEFs is the border, whichever direction is fast
+    for slow, fast_dir in (("rev", "fwd"), ("fwd", "rev")):
+        def unequal(fast):
+            return api.make_config(**{f"{slow}_extrusion_speed": 1000, f"{fast_dir}_extrusion_speed": fast,
+                                      "rev_extrusion_speed_set": 1, "fwd_extrusion_speed_set": 1,
+                                      "rev_extrusion_speed_std": 0.0, "fwd_extrusion_speed_std": 0.0})
+        assert _size_class(unequal(64002), 531) == 0 and _size_class(unequal(64003), 531) == 1
+        assert _size_class(unequal(64002), 532) == 1
+        assert _size_class(unequal(64900), 531) == 1  # (NARROW by the rule as it was: a rev unit moved 65.6 kb)
+    # ... and a unit's own move, speed + 40 sigma + LEFs + 2, where the other direction does not move
+    one_way = api.make_config(rev_extrusion_speed=0, fwd_extrusion_speed=65000, rev_extrusion_speed_set=1,
+                              fwd_extrusion_speed_set=1, rev_extrusion_speed_std=0.0, fwd_extrusion_speed_std=0.0)
+    assert _size_class(one_way, 531) == 0 and _size_class(one_way, 532) == 1
+    # the burn-in's speeds count
+    for coefficient, expect in ((1.0, 0), (2.0, 1)):
+        burnin = api.make_config(rev_extrusion_speed=1000, fwd_extrusion_speed=32000, rev_extrusion_speed_set=1,
+                                 fwd_extrusion_speed_set=1, rev_extrusion_speed_std=0.0,
+                                 fwd_extrusion_speed_std=0.0, burnin_speed_coefficient=coefficient)
+        assert _size_class(burnin, 531) == expect, coefficient
     fast = api.make_config(rev_extrusion_speed=70000, fwd_extrusion_speed=70000, rev_extrusion_speed_set=1,
                            fwd_extrusion_speed_set=1)
     assert _size_class(fast, 100) == 1
@@ -107,6 +128,22 @@ def test_a_move_the_narrow_class_cannot_hold_ends_the_cell_with_an_error(monkeyp
     assert run() == api.ERR_ARG  # refused: the set-up is of the WIDE class
     monkeypatch.setenv("MODLE_EMU_FORCE_NARROW", "1")
     assert run() == api.ERR_STATE  # run all the same: the first move beyond the limit ends the cell
+    monkeypatch.delenv("MODLE_EMU_FORCE_NARROW")
+
+    # The set-up that slipped through: every DRAW fits (1 kb and 64.9 kb per epoch, no spread, 531 LEFs: the rule
+    # as it was said NARROW), but a rev unit that meets a fwd unit stalled by a barrier is put next to it, a move
+    # of up to 1 kb + 64.9 kb.  The correction stored the low 16 bits of 65.6 kb; now it ends the cell.
+    import emu_sim
+    import narrow_range_cases as nrc
+
+    case = nrc.build("fwd_64900_sd0")
+    ch = case["chrom"]
+    slipped = api.slice_tasks(case["tasks"], 0, 1)
+    for geometry in (None, "w12"):
+        rc, *_ = emu_sim.simulate_interval_status(case["cfg"], ch["start"], ch["end"], ch["bar_pos"], ch["bar_dir"],
+                                                  case["stp_active"], case["stp_inactive"], slipped, case["nrows"],
+                                                  case["ncols"], variant=geometry, force_narrow=True)
+        assert rc == api.ERR_STATE, (geometry, rc)
 
 
 @pytest.mark.gpu

@@ -21,7 +21,8 @@ def run(args):
     from modle_amd import api
     from oracle import binding as oracle
     gen = {"v2": fuzz_cases.random_case_v2, "v3": fuzz_cases.random_case_v3,
-           "v4": getattr(fuzz_cases, "random_case_v4", None)}.get(gen_name, fuzz_cases.random_case)
+           "v4": getattr(fuzz_cases, "random_case_v4", None),
+           "v5": getattr(fuzz_cases, "random_case_v5", None)}.get(gen_name, fuzz_cases.random_case)
     case = gen(seed)
     cfg, chrom = case["cfg"], case["chrom"]
     tasks = api.slice_tasks(case["tasks"], 0, 1)

@@ -12,12 +12,12 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import numpy as np  # noqa: E402
 
-from fuzz_cases import random_case, random_case_v2, random_case_v3, random_case_v4  # noqa: E402
+from fuzz_cases import random_case, random_case_v2, random_case_v3, random_case_v4, random_case_v5  # noqa: E402
 from modle_amd import api  # noqa: E402
 from oracle import binding as oracle  # noqa: E402
 
 first, count = int(sys.argv[1]), int(sys.argv[2])
-gen = {"v2": random_case_v2, "v3": random_case_v3, "v4": random_case_v4}.get(sys.argv[3] if len(sys.argv) > 3 else "", random_case)
+gen = {"v2": random_case_v2, "v3": random_case_v3, "v4": random_case_v4, "v5": random_case_v5}.get(sys.argv[3] if len(sys.argv) > 3 else "", random_case)
 progress = open(os.environ["FUZZ_PROGRESS"], "w") if os.environ.get("FUZZ_PROGRESS") else None
 bad = 0
 skipped = 0
