@@ -1,6 +1,7 @@
 /* modle_pixels.h -- C ABI of the sparse-pixel extraction (modle_amd/libmodle_pixels.so), of the
  * coarsening of a band, of its dense regions, of its marginals, of its insulation sums, of its
- * dot candidates, of its pileups and of its random sampling (further down).
+ * dot candidates, of its pileups and of its random sampling, and of the way back from sorted pixels to
+ * a band (further down).
  *
  * The simulation leaves every interval as a dense band matrix in device memory
  * (modle_hip_interval_outputs).  A cooler file is made of the non-zero pixels only, sorted by
@@ -446,6 +447,86 @@ int modle_pixels_sample_to_host(modle_pixels_handle* h, const uint32_t* d_band, 
                                 const int64_t** bin1, const int64_t** bin2, const int32_t** count,
                                 const int64_t** bin1_offset, modle_pixels_stats* stats_out, void* stream,
                                 char* err, size_t errlen);
+
+/* ---- Pixels to band: the inverse of modle_pixels_extract --------------------------------------------
+ *
+ * A pixel list is three DEVICE arrays d_bin1, d_bin2 (int64[n], 8-byte aligned) and d_count (int32[n]),
+ * n < 2^31: what modle_pixels_extract writes and what a cooler holds.  With i = bin1 - bin_offset and
+ * j = bin2 - bin_offset a pixel is
+ *     IN       0 <= i <= j < ncols and j - i <  nrows: a word of the band;
+ *     BEYOND   0 <= i <= j < ncols and j - i >= nrows: a contact the band is too narrow for;
+ *     OUTSIDE  everything else: the bins of another chromosome (the trans pixels that end every row of a
+ *              cooler), i > j, a negative id.
+ * The rule is evaluated without signed overflow for any int64 value and a `bin_offset` of either sign, as
+ * modle_pixels_pileup's is.  Only IN pixels reach the band; the others are counted.
+ *
+ * The WHOLE list, whatever the classes, must be strictly increasing in (bin1, bin2) -- cooler's own
+ * invariant, which rules duplicates out --, else MODLE_PIXELS_ERR_ORDER; a negative count is
+ * MODLE_PIXELS_ERR_RANGE.  stats->first_bad is then the smallest index t whose pixel is not after pixel
+ * t - 1, or whose count is negative, and the code is that of the smaller index (ORDER where both name one).
+ * A count of 0 is legal and is stored as 0.
+ *
+ * Laws: for any band B, band_fill(extract(B)) equals B at every pixel word and is 0 at every word that is
+ * no pixel; modle_pixels_count of the result reports nnz == nnz_in, sum == sum_in and max_count ==
+ * max_count; the result does not depend on the launch.  No floating point is used, and the fill uses no
+ * atomics: a workgroup owns a tile of MODLE_PIXELS_BAND_TILE_COLS columns times
+ * MODLE_PIXELS_BAND_TILE_DIAGS diagonals of the band, gathers the tile's pixels in LDS and stores it whole.
+ *
+ * MODLE_PIXELS_ERR_ARG, with nothing written: a null handle, stats or output, null pixel arrays with n > 0,
+ * n >= 2^31, the shapes modle_pixels_count refuses, out_words < nrows * ncols + 1, an int64 array that is
+ * not 8-byte aligned, an output that overlaps an input.  d_out needs 4-byte alignment only.  n == 0 is legal
+ * and gives a band of zeros. */
+#define MODLE_PIXELS_ERR_ORDER (-4) /* a pixel list that is not strictly increasing in (bin1, bin2) */
+#define MODLE_PIXELS_BAND_IN 0
+#define MODLE_PIXELS_BAND_BEYOND 1
+#define MODLE_PIXELS_BAND_OUTSIDE 2
+#define MODLE_PIXELS_BAND_TILE_COLS 64
+#define MODLE_PIXELS_BAND_TILE_DIAGS 128
+
+typedef struct modle_pixels_band_stats {
+  uint64_t n_in, sum_in;           /* IN pixels and the sum of their counts */
+  uint64_t nnz_in;                 /* IN pixels with a count above 0: modle_pixels_count's nnz of the result */
+  uint64_t n_beyond, sum_beyond;   /* exact integer sums: n < 2^31 counts below 2^31 cannot overflow */
+  uint64_t n_outside, sum_outside;
+  int64_t first_bad;               /* -1 when the list is in order and no count is negative */
+  uint32_t max_count;              /* largest count of an IN pixel */
+  uint32_t reserved_;
+} modle_pixels_band_stats;
+
+/* cls[t] = MODLE_PIXELS_BAND_IN / _BEYOND / _OUTSIDE of pixel t: the rule above on HOST arrays.  Host only:
+ * no device is needed.  The shapes modle_pixels_count refuses, n >= 2^31 and a null pointer with n > 0 are
+ * MODLE_PIXELS_ERR_ARG. */
+int modle_pixels_band_classify(uint64_t nrows, uint64_t ncols, int64_t bin_offset, const int64_t* bin1,
+                               const int64_t* bin2, uint64_t n, uint8_t* cls);
+
+/* Step 1: one pass over the list -- class, order, sign and the reductions -- into *stats, which is filled
+ * on MODLE_PIXELS_ERR_ORDER and _RANGE as well (a negative count enters no sum).  Fills the device array
+ * d_row_start (int64[ncols + 1]; may be NULL when only the statistics are wanted): row_start[i] is the
+ * index of the first pixel with bin1 >= i + bin_offset, 0 <= i <= ncols.  Waits for `stream`. */
+int modle_pixels_band_check(modle_pixels_handle* h, const int64_t* d_bin1, const int64_t* d_bin2,
+                            const int32_t* d_count, uint64_t n, uint64_t nrows, uint64_t ncols,
+                            int64_t bin_offset, int64_t* d_row_start, modle_pixels_band_stats* stats,
+                            void* stream, char* err, size_t errlen);
+
+/* Step 2: enqueues the fill of d_out (uint32[nrows * ncols + 1], the band's layout, `out_words` words) on
+ * `stream`; the call does not wait.  EVERY word is defined by the call, the caller does not pre-zero: an IN
+ * pixel holds its count, every other pixel word, the left-edge triangle and the trailing word hold 0.  The
+ * result is the band of the list only when step 1 returned MODLE_PIXELS_OK on the same unchanged arrays.
+ * WHATEVER the arrays hold -- a stale d_row_start, a list changed in between --, nothing is stored outside
+ * d_out[0, nrows * ncols + 1) and nothing is read outside the n entries and the ncols + 1 row starts: the
+ * kernel clamps what it reads of d_row_start to [0, n] and derives (i, j) of every entry anew before it
+ * stores.  (bin1 is not needed: the row of an entry is the one whose range of d_row_start holds it.) */
+int modle_pixels_band_fill(modle_pixels_handle* h, const int64_t* d_bin2, const int32_t* d_count, uint64_t n,
+                           uint64_t nrows, uint64_t ncols, int64_t bin_offset, const int64_t* d_row_start,
+                           uint32_t* d_out, uint64_t out_words, void* stream, char* err, size_t errlen);
+
+/* One call for HOST pixel arrays: copies them into scratch of the context (grown on demand, freed by
+ * modle_pixels_destroy), then check and fill into the caller's device array d_out.  Fills *stats and waits
+ * for `stream`.  On MODLE_PIXELS_ERR_ORDER and _RANGE nothing is written to d_out. */
+int modle_pixels_band_from_host(modle_pixels_handle* h, const int64_t* bin1, const int64_t* bin2,
+                                const int32_t* count, uint64_t n, uint64_t nrows, uint64_t ncols,
+                                int64_t bin_offset, uint32_t* d_out, uint64_t out_words,
+                                modle_pixels_band_stats* stats, void* stream, char* err, size_t errlen);
 
 #ifdef __cplusplus
 }

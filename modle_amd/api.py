@@ -247,136 +247,10 @@ def apa_scores(pile, corner):
     return out
 
 
-# ---------------------------------------------------------------------------------------------
-# device path
-# ---------------------------------------------------------------------------------------------
-class Simulator:
-    """One simulation context bound to one GPU (one process per GPU)."""
-
-    def __init__(self, cfg, device=0):
-        err = _errbuf()
-        self._L = lib()
-        self.cfg = cfg
-        self.device = int(device)
-        self._h = self._L.modle_hip_create(C.byref(cfg), device, err, len(err))
-        if not self._h:
-            raise ModleHipError(f"modle_hip_create failed: {err.value.decode(errors='replace')}")
-        self._n_submitted = {}
-
-    def close(self):
-        if self._h:
-            self._L.modle_hip_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self):
-        self._L.modle_hip_reset(self._h)
-        self._n_submitted = {}
-
-    def add_interval(self, start, end, bar_pos, bar_dir, stp_active, stp_inactive,
-                     d_contacts=None, d_occupancy=None):
-        err = _errbuf()
-        rc = self._L.modle_hip_add_interval(
-            self._h, start, end, np.ascontiguousarray(bar_pos, dtype=np.uint64),
-            np.ascontiguousarray(bar_dir, dtype=np.uint8),
-            np.ascontiguousarray(stp_active, dtype=np.float64),
-            np.ascontiguousarray(stp_inactive, dtype=np.float64), len(bar_pos), d_contacts,
-            d_occupancy, err, len(err))
-        iv = _check(rc, err)
-        self._n_submitted[iv] = 0
-        return iv
-
-    def submit(self, interval_id, tasks):
-        err = _errbuf()
-        _check(self._L.modle_hip_submit_tasks(self._h, interval_id, tasks, len(tasks), err,
-                                              len(err)), err)
-        self._n_submitted[interval_id] += len(tasks)
-
-    def launch(self, stream=None):
-        err = _errbuf()
-        _check(self._L.modle_hip_launch(self._h, stream, err, len(err)), err)
-
-    def wait(self):
-        """collects the launch; raises ModleHipError with code ERR_TIMEOUT when the launch ran into
-        the deadline (set_wait_timeout / MODLE_HIP_WAIT_TIMEOUT_S) and was aborted"""
-        err = _errbuf()
-        _check(self._L.modle_hip_wait(self._h, err, len(err)), err)
-
-    def set_wait_timeout(self, seconds):
-        if self._L.modle_hip_set_wait_timeout(self._h, float(seconds)) < 0:
-            raise ModleHipError("modle_hip_set_wait_timeout: the deadline must be positive", ERR_ARG)
-
-    def launch_info(self):
-        """layout of the last launch (modle_hip_launch_info) as a dict"""
-        info = LaunchInfo()
-        if self._L.modle_hip_last_launch_info(self._h, C.byref(info)) < 0:
-            raise ModleHipError("modle_hip_last_launch_info failed")
-        return {name: int(getattr(info, name)) for name, _ in LaunchInfo._fields_}
-
-    def enable_state_log(self, max_epochs_per_task):
-        """--log-model-internal-state: needs the diagnostic build (MODLE_HIP_LIB=
-        libmodle_hip_statelog.so); the default build refuses"""
-        err = _errbuf()
-        _check(self._L.modle_hip_enable_state_log(self._h, int(max_epochs_per_task), err, len(err)), err)
-        self._state_log_cap = int(max_epochs_per_task)
-
-    def state_log(self, interval_id, task_index):
-        """records of one task of the last launch: uint64 array (n_epochs, 10), see
-        MODLE_HIP_STATE_LOG_WORDS in include/modle_hip.h"""
-        cap = getattr(self, "_state_log_cap", 0)
-        rec = np.zeros((cap, 10), dtype=np.uint64)
-        n = C.c_size_t(0)
-        err = _errbuf()
-        _check(self._L.modle_hip_get_state_log(self._h, interval_id, task_index, rec.ctypes.data, cap,
-                                               C.byref(n), err, len(err)), err)
-        return rec[:n.value]
-
-    def interval_done(self, interval_id):
-        """True when the launch in flight has finished every task of this interval."""
-        rc = self._L.modle_hip_interval_done(self._h, interval_id)
-        if rc < 0:
-            raise ModleHipError(f"modle_hip_interval_done failed: {rc}")
-        return rc == 1
-
-    def cancel(self):
-        err = _errbuf()
-        _check(self._L.modle_hip_cancel(self._h, err, len(err)), err)
-
-    def kernel_ms(self):
-        ms = C.c_float(0)
-        self._L.modle_hip_last_kernel_ms(self._h, C.byref(ms))
-        return ms.value
-
-    def results(self, interval_id):
-        n = self._n_submitted[interval_id]
-        res = (CellResult * n)()
-        rc = self._L.modle_hip_get_results(self._h, interval_id, res, n)
-        if rc < 0:
-            raise ModleHipError(f"modle_hip_get_results failed: {rc}")
-        return res
-
-    def outputs(self, interval_id):
-        dc, do = C.c_void_p(), C.c_void_p()
-        nr, nc = C.c_uint64(), C.c_uint64()
-        self._L.modle_hip_interval_outputs(self._h, interval_id, C.byref(dc), C.byref(do),
-                                           C.byref(nr), C.byref(nc))
-        return dc.value, do.value, nr.value, nc.value
-
-    def copy_outputs(self, interval_id, want_contacts=True):
-        _, d_occ, nrows, ncols = self.outputs(interval_id)
-        contacts = np.zeros(nrows * ncols + 1, dtype=np.uint32) if want_contacts else None
-        occ = np.zeros(ncols, dtype=np.uint64) if d_occ else None
-        missed = C.c_uint64(0)
-        err = _errbuf()
-        _check(self._L.modle_hip_copy_outputs(
-            self._h, interval_id, contacts.ctypes.data if contacts is not None else None,
-            C.byref(missed), occ.ctypes.data if occ is not None else None, err, len(err)), err)
-        return contacts, missed.value, occ
+class BandAnalyses:
+    """The analyses of a band matrix in device memory, for any owner of bands that has `device` and
+    `outputs(id)` -> (device pointer of the band, occupancy pointer or None, nrows, ncols): the Simulator, whose
+    bands the kernels have just written, and LoadedBands, whose bands come from a pixel list."""
 
     def pixels(self, interval_id, bin_offset=0, stream=None, factor=1, first_bin=0):
         """The interval's non-zero pixels in cooler order, extracted on the device from the band
@@ -686,6 +560,139 @@ class Simulator:
         bands = self.sample_tensors(interval_id, frac, seed, salt, bin_offset, rest=True)
         return tuple(pixels.extract(t.data_ptr(), nrows, ncols, bin_offset, device=self.device) for t in bands)
 
+
+
+# ---------------------------------------------------------------------------------------------
+# device path
+# ---------------------------------------------------------------------------------------------
+class Simulator(BandAnalyses):
+    """One simulation context bound to one GPU (one process per GPU)."""
+
+    def __init__(self, cfg, device=0):
+        err = _errbuf()
+        self._L = lib()
+        self.cfg = cfg
+        self.device = int(device)
+        self._h = self._L.modle_hip_create(C.byref(cfg), device, err, len(err))
+        if not self._h:
+            raise ModleHipError(f"modle_hip_create failed: {err.value.decode(errors='replace')}")
+        self._n_submitted = {}
+
+    def close(self):
+        if self._h:
+            self._L.modle_hip_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        self._L.modle_hip_reset(self._h)
+        self._n_submitted = {}
+
+    def add_interval(self, start, end, bar_pos, bar_dir, stp_active, stp_inactive,
+                     d_contacts=None, d_occupancy=None):
+        err = _errbuf()
+        rc = self._L.modle_hip_add_interval(
+            self._h, start, end, np.ascontiguousarray(bar_pos, dtype=np.uint64),
+            np.ascontiguousarray(bar_dir, dtype=np.uint8),
+            np.ascontiguousarray(stp_active, dtype=np.float64),
+            np.ascontiguousarray(stp_inactive, dtype=np.float64), len(bar_pos), d_contacts,
+            d_occupancy, err, len(err))
+        iv = _check(rc, err)
+        self._n_submitted[iv] = 0
+        return iv
+
+    def submit(self, interval_id, tasks):
+        err = _errbuf()
+        _check(self._L.modle_hip_submit_tasks(self._h, interval_id, tasks, len(tasks), err,
+                                              len(err)), err)
+        self._n_submitted[interval_id] += len(tasks)
+
+    def launch(self, stream=None):
+        err = _errbuf()
+        _check(self._L.modle_hip_launch(self._h, stream, err, len(err)), err)
+
+    def wait(self):
+        """collects the launch; raises ModleHipError with code ERR_TIMEOUT when the launch ran into
+        the deadline (set_wait_timeout / MODLE_HIP_WAIT_TIMEOUT_S) and was aborted"""
+        err = _errbuf()
+        _check(self._L.modle_hip_wait(self._h, err, len(err)), err)
+
+    def set_wait_timeout(self, seconds):
+        if self._L.modle_hip_set_wait_timeout(self._h, float(seconds)) < 0:
+            raise ModleHipError("modle_hip_set_wait_timeout: the deadline must be positive", ERR_ARG)
+
+    def launch_info(self):
+        """layout of the last launch (modle_hip_launch_info) as a dict"""
+        info = LaunchInfo()
+        if self._L.modle_hip_last_launch_info(self._h, C.byref(info)) < 0:
+            raise ModleHipError("modle_hip_last_launch_info failed")
+        return {name: int(getattr(info, name)) for name, _ in LaunchInfo._fields_}
+
+    def enable_state_log(self, max_epochs_per_task):
+        """--log-model-internal-state: needs the diagnostic build (MODLE_HIP_LIB=
+        libmodle_hip_statelog.so); the default build refuses"""
+        err = _errbuf()
+        _check(self._L.modle_hip_enable_state_log(self._h, int(max_epochs_per_task), err, len(err)), err)
+        self._state_log_cap = int(max_epochs_per_task)
+
+    def state_log(self, interval_id, task_index):
+        """records of one task of the last launch: uint64 array (n_epochs, 10), see
+        MODLE_HIP_STATE_LOG_WORDS in include/modle_hip.h"""
+        cap = getattr(self, "_state_log_cap", 0)
+        rec = np.zeros((cap, 10), dtype=np.uint64)
+        n = C.c_size_t(0)
+        err = _errbuf()
+        _check(self._L.modle_hip_get_state_log(self._h, interval_id, task_index, rec.ctypes.data, cap,
+                                               C.byref(n), err, len(err)), err)
+        return rec[:n.value]
+
+    def interval_done(self, interval_id):
+        """True when the launch in flight has finished every task of this interval."""
+        rc = self._L.modle_hip_interval_done(self._h, interval_id)
+        if rc < 0:
+            raise ModleHipError(f"modle_hip_interval_done failed: {rc}")
+        return rc == 1
+
+    def cancel(self):
+        err = _errbuf()
+        _check(self._L.modle_hip_cancel(self._h, err, len(err)), err)
+
+    def kernel_ms(self):
+        ms = C.c_float(0)
+        self._L.modle_hip_last_kernel_ms(self._h, C.byref(ms))
+        return ms.value
+
+    def results(self, interval_id):
+        n = self._n_submitted[interval_id]
+        res = (CellResult * n)()
+        rc = self._L.modle_hip_get_results(self._h, interval_id, res, n)
+        if rc < 0:
+            raise ModleHipError(f"modle_hip_get_results failed: {rc}")
+        return res
+
+    def outputs(self, interval_id):
+        dc, do = C.c_void_p(), C.c_void_p()
+        nr, nc = C.c_uint64(), C.c_uint64()
+        self._L.modle_hip_interval_outputs(self._h, interval_id, C.byref(dc), C.byref(do),
+                                           C.byref(nr), C.byref(nc))
+        return dc.value, do.value, nr.value, nc.value
+
+    def copy_outputs(self, interval_id, want_contacts=True):
+        _, d_occ, nrows, ncols = self.outputs(interval_id)
+        contacts = np.zeros(nrows * ncols + 1, dtype=np.uint32) if want_contacts else None
+        occ = np.zeros(ncols, dtype=np.uint64) if d_occ else None
+        missed = C.c_uint64(0)
+        err = _errbuf()
+        _check(self._L.modle_hip_copy_outputs(
+            self._h, interval_id, contacts.ctypes.data if contacts is not None else None,
+            C.byref(missed), occ.ctypes.data if occ is not None else None, err, len(err)), err)
+        return contacts, missed.value, occ
+
     def simulate_interval(self, start, end, bar_pos, bar_dir, stp_active, stp_inactive, tasks):
         """One-call seam (modle_hip_simulate_interval): returns contacts, missed, occupancy,
         results."""
@@ -726,3 +733,74 @@ class Simulator:
             st.fwd_rank, st.rev_moves, st.fwd_moves, st.rev_coll, st.fwd_coll, len(st.bar_pos),
             st.bar_pos, st.bar_dir, st.bar_active, prng, C.byref(consumed), err, len(err)), err)
         return consumed.value
+
+
+class LoadedBands(BandAnalyses):
+    """Bands that were not simulated: every analysis of BandAnalyses on a band built on the device from a
+    pixel list (a cooler's: cooler.CoolerReader.pixels) or on a band that already lies there.  The ids count
+    from 0 in the order of loading, so that driver.write_outputs takes this object where it takes a
+    Simulator."""
+
+    def __init__(self, device=0):
+        self.device = int(device)
+        self._bands = []  # (tensor, nrows, ncols)
+
+    def load_pixels(self, bin1, bin2, count, nrows, ncols, bin_offset=0):
+        """(id, stats): the band of `nrows` diagonals and `ncols` columns of the host pixels (bin1[t] -
+        bin_offset, bin2[t] - bin_offset) with count[t] contacts, a torch int32 tensor of nrows * ncols + 1
+        words on the device, filled there by the kernel (pixels.band_from_host): only the pixels cross.  The
+        list must be strictly increasing in (bin1, bin2), else pixels.BandListError; the pixels beyond the
+        band and outside the matrix are counted in `stats` (pixels.BandStats) and left out.  The band is then
+        counted by the extraction's own kernel, which must agree with the statistics of the list."""
+        import torch
+
+        from . import pixels
+
+        nrows, ncols = int(nrows), int(ncols)
+        band = torch.empty(nrows * ncols + 1, dtype=torch.int32, device=torch.device("cuda", self.device))
+        ex = pixels.extractor(self.device)
+        stats = ex.band_from_host(bin1, bin2, count, nrows, ncols, bin_offset, band.data_ptr(), band.numel())
+        seen = ex.count(band.data_ptr(), nrows, ncols)
+        if (seen.nnz, seen.sum, seen.max_count) != (stats.nnz_in, stats.sum_in, stats.max_count):
+            raise ModleHipError(f"load_pixels: the band holds {seen.nnz} pixels, {seen.sum} contacts and a maximum of "
+                                f"{seen.max_count}; the list has {stats.nnz_in}, {stats.sum_in} and {stats.max_count}")
+        return self.add_band(band, nrows, ncols), stats
+
+    def add_band(self, tensor, nrows, ncols):
+        """the id of a band that already lies on the device: a contiguous torch int32 tensor of at least
+        nrows * ncols + 1 words in the band's layout (sample_tensors' result, for one)"""
+        import torch
+
+        if tensor.dtype != torch.int32 or tensor.device != torch.device("cuda", self.device) or \
+                not tensor.is_contiguous() or tensor.numel() < int(nrows) * int(ncols) + 1:
+            raise ValueError("add_band: the band must be a contiguous int32 tensor of nrows * ncols + 1 words on "
+                             "this object's device")
+        self._bands.append((tensor, int(nrows), int(ncols)))
+        return len(self._bands) - 1
+
+    def band(self, band_id):
+        return self._bands[band_id][0]
+
+    def release(self, band_id):
+        """lets go of the band; the id is not used again"""
+        self._bands[band_id] = None
+
+    def outputs(self, band_id):
+        tensor, nrows, ncols = self._bands[band_id]
+        return tensor.data_ptr(), None, nrows, ncols
+
+    def copy_outputs(self, band_id, want_contacts=False):
+        """(None, 0, None): a loaded band has no dense host copy, no missed updates and no occupancy"""
+        if want_contacts:
+            raise ModleHipError("copy_outputs: a loaded band is not copied to the host; use pixels()")
+        return None, 0, None
+
+    def close(self):
+        self._bands = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False

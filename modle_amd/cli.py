@@ -18,7 +18,12 @@ the windows around the dots, the barriers or the pairs of a BEDPE file, summed o
 probability, drawn on the GPU (with --subsample-split also `<prefix>_sampled_rest.cool`, the others).  Everything heavy is native: parsing and
 task generation in libmodle_hip.so (host), the simulation on the MI355X (one process per GPU;
 under torch.distributed.run the cells are sharded over the ranks and the matrices are summed
-with RCCL, or with --dist-backend gloo on host copies), the writers in libmodle_cooler.so.  `-t/--threads` is accepted and ignored."""
+with RCCL, or with --dist-backend gloo on host copies), the writers in libmodle_cooler.so.  `-t/--threads` is accepted and ignored.
+
+    python -m modle_amd analyze IN.cool | IN.mcool::/resolutions/R -o out/prefix [-w 3mb] [analysis options]
+
+runs the same analyses on the matrix of a file: its pixels are read by libmodle_cooler.so, scattered into band
+matrices on the GPU (libmodle_pixels.so) and handed to the output stage of `simulate` as they are."""
 import argparse
 import collections
 import decimal
@@ -177,21 +182,9 @@ def sampled_paths(prefix, mcool=False):
     return prefix + "_sampled" + ext, prefix + "_sampled_rest" + ext
 
 
-def build_parser():
-    ap = argparse.ArgumentParser(prog="modle_amd", description=__doc__,
-                                 formatter_class=argparse.RawDescriptionHelpFormatter)
-    sub = ap.add_subparsers(dest="command", required=True)
-    p = sub.add_parser("simulate", aliases=["sim"], help="simulate loop extrusion and write a .cool")
-    io = p.add_argument_group("input / output")
-    io.add_argument("-c", "--chrom-sizes", required=True)
-    io.add_argument("-b", "--extrusion-barrier-file", required=True)
-    io.add_argument("-g", "--genomic-intervals", "--chrom-subranges", default=None)
-    io.add_argument("-f", "--force", action="store_true")
-    io.add_argument("-o", "--output-prefix", required=True)
-    io.add_argument("--assembly-name", default="unknown")
-    io.add_argument("-q", "--quiet", action="store_true")
-    io.add_argument("-v", "--verbose", action="store_true", help="accepted (the log is short anyway)")
-    io.add_argument("--skip-output", action="store_true")
+def add_analysis_arguments(io):
+    """the options of the analyses of a band, which `simulate` and `analyze` share: added to the argument group
+    `io` in the order of simulate's help"""
     io.add_argument("--mcool-resolutions", type=resolution_list, default=None, metavar="LIST",
                     help="write <prefix>.mcool instead of <prefix>.cool: the matrix at the resolution "
                          "(-r), which need not be listed, and at every bin size of the comma-separated "
@@ -280,6 +273,24 @@ def build_parser():
     io.add_argument("--subsample-split", action="store_true",
                     help="with --subsample-frac / --subsample-to: also write <prefix>_sampled_rest.cool, the "
                          "contacts that were not kept: two disjoint pseudo-replicates that add up to the matrix")
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(prog="modle_amd", description=__doc__,
+                                 formatter_class=argparse.RawDescriptionHelpFormatter)
+    sub = ap.add_subparsers(dest="command", required=True)
+    p = sub.add_parser("simulate", aliases=["sim"], help="simulate loop extrusion and write a .cool")
+    io = p.add_argument_group("input / output")
+    io.add_argument("-c", "--chrom-sizes", required=True)
+    io.add_argument("-b", "--extrusion-barrier-file", required=True)
+    io.add_argument("-g", "--genomic-intervals", "--chrom-subranges", default=None)
+    io.add_argument("-f", "--force", action="store_true")
+    io.add_argument("-o", "--output-prefix", required=True)
+    io.add_argument("--assembly-name", default="unknown")
+    io.add_argument("-q", "--quiet", action="store_true")
+    io.add_argument("-v", "--verbose", action="store_true", help="accepted (the log is short anyway)")
+    io.add_argument("--skip-output", action="store_true")
+    add_analysis_arguments(io)
     io.add_argument("--log-model-internal-state", action="store_true",
                     help="write <prefix>_internal_state.log.gz: one line of statistics per task and "
                          "epoch (uses the diagnostic build libmodle_hip_statelog.so)")
@@ -349,6 +360,26 @@ def build_parser():
     e.add_argument("-m", "--metric", choices=["pearson", "spearman", "rmse", "eucl_dist"],
                    default="pearson")
     e.add_argument("--exclude-zero-pixels", action="store_true")
+    n = sub.add_parser("analyze", aliases=["an"],
+                       help="run the analyses of `simulate` on the matrix of a .cool or of one resolution of an "
+                            ".mcool, loaded into band matrices on the GPU")
+    nio = n.add_argument_group("input / output")
+    nio.add_argument("input", metavar="IN.cool | IN.mcool::/resolutions/R",
+                     help="the cooler: the bin size and the chromosomes are the file's; raw counts are read, "
+                          "balancing weights are ignored")
+    nio.add_argument("-o", "--output-prefix", required=True)
+    nio.add_argument("-w", "--diagonal-width", type=genomic_distance, default=None,
+                     help="the width of the band that is loaded (default 3mb, as for simulate); the contacts "
+                          "of the file beyond it are counted and left out")
+    nio.add_argument("--chromosomes", default=None, metavar="LIST",
+                     help="comma-separated names of the chromosomes to analyse (default: all of the file)")
+    nio.add_argument("--device", type=int, default=None, help="HIP device (default: LOCAL_RANK or 0)")
+    nio.add_argument("-f", "--force", action="store_true")
+    nio.add_argument("-q", "--quiet", action="store_true")
+    nio.add_argument("--assembly-name", default="unknown")
+    add_analysis_arguments(nio)
+    # (what preflight and write_outputs look at of simulate's other options)
+    n.set_defaults(skip_output=False, log_model_internal_state=False)
     return ap
 
 
@@ -618,6 +649,12 @@ def plan_run(a, cfg, pre, log):
     log(f"imported {len(chroms)} chromosomes, {len(intervals)} intervals, "
         f"{stats['barriers_imported']} barriers ({stats['barriers_without_strand']} without strand dropped)")
     plan = driver.plan_genome(cfg, intervals, pre.rank, pre.world)
+    return chroms, plan, check_plan(a, cfg, pre, plan, chroms)
+
+
+def check_plan(a, cfg, pre, plan, chroms):
+    """What a plan shows to be bad of the resolutions, the windows and the regions asked for, as a SystemExit
+    before anything is simulated or analysed; returns the dense regions (driver.dense_regions)."""
     if pre.bin_sizes is not None and not a.skip_output:
         hit = driver.mcool_collision(plan, int(cfg.bin_size), pre.bin_sizes)
         if hit is not None:
@@ -645,8 +682,7 @@ def plan_run(a, cfg, pre, log):
             raise SystemExit(f"--pileup-flank: the flank of {bad[2]} ({bad[3]} bins of {pre.pileup.resolution}) does "
                              f"not fit the band of {bad[1]} ({bad[4]} diagonals): the largest flank that fits is "
                              f"{bad[5]} ({bad[5] // pre.pileup.resolution} bins)")
-    regions = driver.dense_regions(plan, int(cfg.bin_size), chroms, a.dense_region) if a.dense_region else []
-    return chroms, plan, regions
+    return driver.dense_regions(plan, int(cfg.bin_size), chroms, a.dense_region) if a.dense_region else []
 
 
 def open_simulator(cfg, pre, backend="nccl"):
@@ -726,6 +762,110 @@ def simulate(a, log=print):
     return 0
 
 
+ANALYSIS_SCRATCH_BANDS = 4  # what the analyses hold at once besides the bands: coarse, dot candidates, kept, rest
+
+
+def analyze_plan(cfg, reader, names):
+    """a plan of driver.plan_genome's shape for the chromosomes `names` of the open cooler `reader`, in the
+    file's order: every chromosome one interval from 0 with the band api.matrix_shape gives it, no barriers
+    and no tasks"""
+    plan = []
+    for name, size in reader.chroms:
+        if name in names:
+            nrows, ncols = api.matrix_shape(cfg, int(size))
+            iv = {"name": name, "size": int(size), "start": 0, "end": int(size), "bar_pos": [], "bar_dir": []}
+            plan.append({"interval": iv, "nrows": nrows, "ncols": ncols, "tasks": None, "skipped": False})
+    return plan
+
+
+def check_band_memory(plan, free_bytes):
+    """SystemExit when the bands of the plan and the scratch of the analyses, ANALYSIS_SCRATCH_BANDS times the
+    largest band, exceed `free_bytes` of device memory"""
+    sizes = [(e["nrows"] * e["ncols"] + 1) * 4 for e in plan]
+    need = sum(sizes) + ANALYSIS_SCRATCH_BANDS * max(sizes, default=0)
+    if need > free_bytes:
+        raise SystemExit(f"analyze: the bands of the {len(plan)} chromosomes ({sum(sizes)} bytes) and the scratch of "
+                         f"the analyses ({ANALYSIS_SCRATCH_BANDS} times the largest band, {max(sizes)} bytes) need "
+                         f"{need} bytes; the device has {int(free_bytes)} free: narrow the band with -w or take fewer "
+                         "chromosomes with --chromosomes")
+
+
+def load_bands(bands, reader, plan, log):
+    """Loads every chromosome of the plan from `reader` into `bands` (an api.LoadedBands); a chromosome without a
+    pixel in its band is marked skipped, as simulate skips one without barriers.  Returns the ids per entry
+    (None: skipped).  SystemExit: a pixel list that is out of order or holds a negative count."""
+    from . import pixels
+
+    ids = []
+    for entry in plan:
+        name = entry["interval"]["name"]
+        bin1, bin2, count, first = reader.pixels(name)
+        try:
+            bid, st = bands.load_pixels(bin1, bin2, count, entry["nrows"], entry["ncols"], first)
+        except pixels.BandListError as e:
+            what = "is not after its predecessor in (bin1, bin2)" if e.code == pixels.ERR_ORDER else \
+                "has a negative count"
+            raise SystemExit(f"{reader.uri}: chromosome {name}: pixel {e.stats.first_bad} of its {len(bin1)} {what}: "
+                             "the file is no valid cooler")
+        log(f"{name}: {st.n_in} pixels in the band ({st.sum_in} contacts), beyond the band {st.n_beyond} pixels "
+            f"({st.sum_beyond} contacts), outside {st.n_outside} pixels ({st.sum_outside} contacts)")
+        if st.n_in == 0:
+            bands.release(bid)
+            entry["skipped"] = True
+            bid = None
+        ids.append(bid)
+    return ids
+
+
+def analyze(a, log=print):
+    """The analyses of simulate on a file: refusals (arguments, file, outputs) -> the plan -> the bands on the
+    device (api.LoadedBands) -> check_plan -> driver.write_outputs, which writes what it writes for simulate"""
+    from . import cooler
+
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("analyze runs on one GPU: WORLD_SIZE is above 1")
+    if a.pileup_at and "barriers" in a.pileup_at:
+        raise SystemExit("--pileup-at barriers: a file has no barriers; give `dots` or a BEDPE file")
+    if a.subsample_seed is None and (a.subsample_frac is not None or a.subsample_to is not None):
+        a.subsample_seed = 0
+    t0 = time.time()
+    try:
+        reader = cooler.CoolerReader(a.input)
+    except cooler.CoolerError as e:
+        raise SystemExit(f"analyze: cannot read {a.input}: {e}")
+    with reader:
+        names = [n for n, _ in reader.chroms] if a.chromosomes is None else \
+            [n for n in a.chromosomes.split(",") if n]
+        for name in names:
+            if name not in dict(reader.chroms):
+                raise SystemExit(f"--chromosomes: {name} is not a chromosome of {a.input} "
+                                 f"({', '.join(n for n, _ in reader.chroms)})")
+        over = {"bin_size": int(reader.bin_size), "track_1d_lef_position": 0}
+        if a.diagonal_width is not None:
+            over["diagonal_width"] = int(a.diagonal_width)
+        cfg = api.make_config(**over)
+        pre = preflight(a, cfg)
+        plan = analyze_plan(cfg, reader, set(names))
+        import torch
+
+        check_band_memory(plan, torch.cuda.mem_get_info(pre.device)[0])
+        bands = api.LoadedBands(pre.device)
+        try:
+            ids = load_bands(bands, reader, plan, log)
+            regions = check_plan(a, cfg, pre, plan, reader.chroms)
+            meta = json.dumps({k: v for k, v in vars(a).items() if v is not None and k != "command"}, sort_keys=True)
+            driver.write_outputs(
+                bands, cfg, plan, ids, None, pre.outputs, pre.bin_sizes, regions, 0, log,
+                coverage_min_diag=a.coverage_ignore_diags or 0, insulation=pre.insulation, dots=pre.dots,
+                pileup=pre.pileup, subsample=subsample_plan(a, cfg), assembly=a.assembly_name,
+                generated_by="modle_amd analyze (MI355X)", metadata_json=meta, force_overwrite=a.force,
+                chroms=reader.chroms)
+        finally:
+            bands.close()
+    log(f"done in {time.time() - t0:.1f} s")
+    return 0
+
+
 def evaluate_cmd(a):
     """prints one JSON object: {chromosome: {vertical: summary, horizontal: summary}}"""
     from . import evaluate as ev
@@ -742,6 +882,8 @@ def main(argv=None):
     a = build_parser().parse_args(argv)
     if a.command in ("evaluate", "eval"):
         return evaluate_cmd(a)
+    if a.command in ("analyze", "an"):
+        return analyze(a, (lambda *x: None) if a.quiet else (lambda *x: print(*x, file=sys.stderr, flush=True)))
     if a.log_model_internal_state and not a.skip_output:
         # the recording code lives in a diagnostic build of the library, chosen at import time
         from . import _lib

@@ -1,7 +1,8 @@
 """ctypes view of the cooler (v3) writer, include/modle_cooler.h.  The product path is the C
 library (modle_amd/libmodle_cooler.so, built by `make -C modle_amd/csrc cooler`); this module
 mirrors how the reference's IO thread uses it (simulation.cpp:117-168, 217-269): create the file
-with every chromosome, append the interval matrices in genome order, close."""
+with every chromosome, append the interval matrices in genome order, close.  CoolerReader is the way
+back (include/modle_cooler_read.h): a chromosome's pixels as they lie in the file."""
 import ctypes
 import os
 
@@ -48,6 +49,24 @@ def lib():
         lb.modle_mcool_resolution.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
         lb.modle_mcool_close.restype = ctypes.c_int
         lb.modle_mcool_close.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+        vpp = ctypes.POINTER(ctypes.c_void_p)  # include/modle_cooler_read.h
+        lb.modle_cool_reader_open.restype = ctypes.c_int
+        lb.modle_cool_reader_open.argtypes = [ctypes.c_char_p, vpp, ctypes.c_char_p, ctypes.c_size_t]
+        lb.modle_cool_reader_info.restype = ctypes.c_int
+        lb.modle_cool_reader_info.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
+                                              ctypes.POINTER(ctypes.c_size_t)]
+        lb.modle_cool_reader_chrom.restype = ctypes.c_int
+        lb.modle_cool_reader_chrom.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_char_p),
+                                               ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int64),
+                                               ctypes.POINTER(ctypes.c_uint64)]
+        lb.modle_cool_reader_indexes.restype = ctypes.c_int
+        lb.modle_cool_reader_indexes.argtypes = [ctypes.c_void_p, vpp, vpp, ctypes.POINTER(ctypes.c_uint64)]
+        lb.modle_cool_reader_pixels.restype = ctypes.c_int
+        lb.modle_cool_reader_pixels.argtypes = [ctypes.c_void_p, ctypes.c_size_t, vpp, vpp, vpp,
+                                                ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int64),
+                                                ctypes.c_char_p, ctypes.c_size_t]
+        lb.modle_cool_reader_close.restype = None
+        lb.modle_cool_reader_close.argtypes = [ctypes.c_void_p]
         _LIB = lb
     return _LIB
 
@@ -186,3 +205,91 @@ class McoolWriter(_Handle):
         for r in self._res.values():
             r.close()  # borrowed handles: gone with the file
         super().close()
+
+
+def _copy_array(ptr, n, ctype, dtype):
+    import numpy as np
+    if n == 0 or not ptr:
+        return np.zeros(0, dtype=dtype)
+    return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctype)), shape=(n,)).copy()
+
+
+class CoolerReader:
+    """A cooler opened for reading (include/modle_cooler_read.h): `uri` is `path`, the cooler at the root of
+    the file, or `path::/resolutions/10000`, that group of an .mcool.  `bin_size`, `chroms` ([(name, size)]) and
+    `chrom_offset` (the first bin of every chromosome and the number of bins) are read on opening; `pixels(chrom)`
+    hands over a chromosome's pixels as they lie in the file.  A bin-type other than "fixed", counts that are no
+    integers and indexes of the wrong length are refused with a CoolerError; balancing weights are ignored."""
+
+    def __init__(self, uri):
+        self.uri = os.fspath(uri)
+        self._h = ctypes.c_void_p()
+        self._err = ctypes.create_string_buffer(1024)
+        rc = lib().modle_cool_reader_open(os.fsencode(self.uri), ctypes.byref(self._h), self._err, len(self._err))
+        if rc != 0:
+            self._h = None
+            raise CoolerError(rc, self._err.value.decode(errors="replace"))
+        bs, n = ctypes.c_uint32(), ctypes.c_size_t()
+        lib().modle_cool_reader_info(self._h, ctypes.byref(bs), ctypes.byref(n))
+        self.bin_size = bs.value
+        self.chroms, self.chrom_offset = [], []
+        for c in range(n.value):
+            name, size, first, bins = ctypes.c_char_p(), ctypes.c_uint64(), ctypes.c_int64(), ctypes.c_uint64()
+            lib().modle_cool_reader_chrom(self._h, c, ctypes.byref(name), ctypes.byref(size), ctypes.byref(first),
+                                          ctypes.byref(bins))
+            self.chroms.append((name.value.decode(), size.value))
+            self.chrom_offset.append(first.value)
+        self.chrom_offset.append(self.chrom_offset[-1] + bins.value if self.chroms else 0)
+        self._index = {name: i for i, (name, _) in enumerate(self.chroms)}
+
+    def _cid(self, chrom):
+        if isinstance(chrom, str):
+            if chrom not in self._index:
+                raise KeyError(f"chromosome {chrom!r} is not in {self.uri}")
+            return self._index[chrom]
+        return int(chrom)
+
+    def n_bins(self, chrom):
+        c = self._cid(chrom)
+        return self.chrom_offset[c + 1] - self.chrom_offset[c]
+
+    def bin1_offset(self):
+        """the file's indexes/bin1_offset, numpy int64 with one entry per bin and one more"""
+        import numpy as np
+        p, n = ctypes.c_void_p(), ctypes.c_uint64()
+        lib().modle_cool_reader_indexes(self._h, None, ctypes.byref(p), ctypes.byref(n))
+        return _copy_array(p.value, n.value + 1, ctypes.c_int64, np.int64)
+
+    def pixels(self, chrom):
+        """(bin1, bin2, count, first_bin) of the pixels whose bin1 lies in `chrom` (a name or an index): numpy
+        int64, int64 and int32 arrays the caller owns, with the file's bin ids, in the file's order, the trans
+        pixels included, and the id of the chromosome's first bin"""
+        import numpy as np
+        p1, p2, pc = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        n, first = ctypes.c_uint64(), ctypes.c_int64()
+        rc = lib().modle_cool_reader_pixels(self._h, self._cid(chrom), ctypes.byref(p1), ctypes.byref(p2),
+                                            ctypes.byref(pc), ctypes.byref(n), ctypes.byref(first), self._err,
+                                            len(self._err))
+        if rc != 0:
+            raise CoolerError(rc, self._err.value.decode(errors="replace"))
+        return (_copy_array(p1.value, n.value, ctypes.c_int64, np.int64),
+                _copy_array(p2.value, n.value, ctypes.c_int64, np.int64),
+                _copy_array(pc.value, n.value, ctypes.c_int32, np.int32), first.value)
+
+    def close(self):
+        if self._h:
+            h, self._h = self._h, None
+            lib().modle_cool_reader_close(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False

@@ -647,3 +647,9 @@ extern "C" int modle_cool_read_band(const char* path, const char* chrom, uint64_
   if (rc == MODLE_COOL_ERR_IO) set_err(err, errlen, std::string("HDF5 error while reading \"") + path + "\"");
   return rc;
 }
+
+// ---------------------------------------------------------------------------------------------
+// The reader that hands over pixels (include/modle_cooler_read.h) shares read_all / read_slice above:
+// it is the rest of this translation unit.
+// ---------------------------------------------------------------------------------------------
+#include "cooler_reader.cpp"

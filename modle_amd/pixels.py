@@ -4,7 +4,8 @@ memory, in cooler order, found on the GPU; the band at a multiple of its bin siz
 of it as dense matrices; its marginals, the sums per diagonal and per bin; its insulation sums
 over sliding diamond windows; its dots, the pixels enriched over their HiCCUPS neighbourhoods;
 its pileups, the windows around anchor pairs summed into one; and its random sampling, every contact
-kept with one probability by a generator keyed by the pixel's coordinates.
+kept with one probability by a generator keyed by the pixel's coordinates; and the way back, sorted pixels
+checked and scattered into a band on the GPU.
 There is no host fallback: without the library or
 without a device the calls fail."""
 import ctypes as C
@@ -15,13 +16,15 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "libmodle_pixels.so")
-ERR_ARG, ERR_DEVICE, ERR_RANGE = -1, -2, -3
+ERR_ARG, ERR_DEVICE, ERR_RANGE, ERR_ORDER = -1, -2, -3, -4
 MAX_WINDOW, MAX_WINDOWS = 1024, 8  # MODLE_PIXELS_MAX_WINDOW, MODLE_PIXELS_MAX_WINDOWS
 MAX_DOT_WINDOW = 20  # MODLE_PIXELS_MAX_DOT_WINDOW
 MAX_PILEUP_FLANK, PILEUP_GROUPS = 32, 256  # MODLE_PIXELS_MAX_PILEUP_FLANK, MODLE_PIXELS_PILEUP_GROUPS
 SAMPLE_TIER1_TRIALS = 64  # MODLE_PIXELS_SAMPLE_TIER1_TRIALS: what a lane draws of its own pixel
 MAX_SAMPLE_TRIALS = 1 << 40  # MODLE_PIXELS_MAX_SAMPLE_TRIALS
 SAMPLE_KEPT, SAMPLE_REST = 0, 1  # MODLE_PIXELS_SAMPLE_KEPT, MODLE_PIXELS_SAMPLE_REST
+BAND_IN, BAND_BEYOND, BAND_OUTSIDE = 0, 1, 2  # MODLE_PIXELS_BAND_IN, _BEYOND, _OUTSIDE
+BAND_TILE_COLS, BAND_TILE_DIAGS = 64, 128  # MODLE_PIXELS_BAND_TILE_COLS, _DIAGS: the tile of a workgroup of the fill
 DOT_FOLDS = (1.75, 1.75, 1.5, 1.5)  # HiCCUPS' thresholds: donut, lower-left, horizontal, vertical
 EXPORTS = ["modle_pixels_create", "modle_pixels_destroy", "modle_pixels_count", "modle_pixels_extract",
            "modle_pixels_to_host", "modle_pixels_coarse_shape", "modle_pixels_coarsen",
@@ -32,13 +35,16 @@ EXPORTS = ["modle_pixels_create", "modle_pixels_destroy", "modle_pixels_count", 
            "modle_pixels_dots_to_host", "modle_pixels_coarse_dots_to_host", "modle_pixels_pileup_accepts",
            "modle_pixels_pileup", "modle_pixels_pileup_to_host",
            "modle_pixels_coarse_pileup_to_host", "modle_pixels_sample_pixels", "modle_pixels_sample",
-           "modle_pixels_sample_to_host"]  # every symbol include/modle_pixels.h declares
+           "modle_pixels_sample_to_host", "modle_pixels_band_classify", "modle_pixels_band_check",
+           "modle_pixels_band_fill", "modle_pixels_band_from_host"]  # every symbol include/modle_pixels.h declares
 
 _LIB = None
 _EXTRACTORS = {}
 
 Stats = namedtuple("Stats", "nnz sum max_count")
 Pixels = namedtuple("Pixels", "bin1 bin2 count bin1_offset stats")  # what extract / coarse_extract return
+# what band_check / band_from_host return (modle_pixels_band_stats)
+BandStats = namedtuple("BandStats", "n_in sum_in nnz_in n_beyond sum_beyond n_outside sum_outside max_count first_bad")
 
 
 class _CStats(C.Structure):  # modle_pixels_stats
@@ -46,10 +52,29 @@ class _CStats(C.Structure):  # modle_pixels_stats
                 ("reserved_", C.c_uint32)]
 
 
+class _CBandStats(C.Structure):  # modle_pixels_band_stats
+    _fields_ = [(name, C.c_uint64) for name in ("n_in", "sum_in", "nnz_in", "n_beyond", "sum_beyond", "n_outside",
+                                                "sum_outside")] + \
+               [("first_bad", C.c_int64), ("max_count", C.c_uint32), ("reserved_", C.c_uint32)]
+
+    def tuple(self):
+        return BandStats(self.n_in, self.sum_in, self.nnz_in, self.n_beyond, self.sum_beyond, self.n_outside,
+                         self.sum_outside, self.max_count, self.first_bad)
+
+
 class PixelsError(RuntimeError):
     def __init__(self, code, message):
         super().__init__(f"modle_pixels error {code}: {message}")
         self.code = code
+
+
+class BandListError(PixelsError):
+    """ERR_ORDER / ERR_RANGE of band_check and band_from_host: `stats` is the BandStats the library filled,
+    stats.first_bad the smallest offending index"""
+
+    def __init__(self, code, message, stats):
+        super().__init__(code, message)
+        self.stats = stats
 
 
 def lib():
@@ -111,6 +136,15 @@ def lib():
                                                   C.c_uint64, u32p]
         lb.modle_pixels_sample.argtypes = shape + draw + [C.POINTER(_CStats), C.c_void_p, C.c_void_p, C.c_void_p] + err
         lb.modle_pixels_sample_to_host.argtypes = shape + draw + [C.c_int] + pix[1:]
+        lb.modle_pixels_band_classify.argtypes = [C.c_uint64, C.c_uint64, C.c_int64, i64p, i64p, C.c_uint64,
+                                                  C.POINTER(C.c_uint8)]
+        # handle, (d_bin1,) d_bin2, d_count, n, nrows, ncols, bin_offset
+        lb.modle_pixels_band_check.argtypes = [C.c_void_p] * 4 + [C.c_uint64] * 3 + [C.c_int64, C.c_void_p,
+                                                                                     C.POINTER(_CBandStats), C.c_void_p] + err
+        lb.modle_pixels_band_fill.argtypes = [C.c_void_p] * 3 + [C.c_uint64] * 3 + [C.c_int64, C.c_void_p, C.c_void_p,
+                                                                                    C.c_uint64, C.c_void_p] + err
+        lb.modle_pixels_band_from_host.argtypes = [C.c_void_p] * 4 + [C.c_uint64] * 3 + \
+            [C.c_int64, C.c_void_p, C.c_uint64, C.POINTER(_CBandStats), C.c_void_p] + err
         for name in EXPORTS:
             getattr(lb, name)  # raises AttributeError if a declared symbol is not exported
         _LIB = lb
@@ -294,6 +328,35 @@ def pileup_accepts(nrows, ncols, flank, bin1, bin2, bin_offset=0):
         raise PixelsError(rc, "pileup_accepts: invalid argument (0 < nrows <= ncols, flank <= 32, "
                               "2 * flank + 1 <= nrows, n < 2^31)")
     return out.astype(bool)
+
+
+def band_classify(nrows, ncols, bin1, bin2, bin_offset=0):
+    """the class of every pixel (bin1[t] - bin_offset, bin2[t] - bin_offset) = (i, j) against a band of `nrows`
+    diagonals and `ncols` columns, a numpy uint8 array: BAND_IN for 0 <= i <= j < ncols and j - i < nrows,
+    BAND_BEYOND for 0 <= i <= j < ncols and j - i >= nrows, BAND_OUTSIDE for everything else, for any int64
+    values (modle_pixels_band_classify; no device is needed)"""
+    if min(int(nrows), int(ncols)) < 0:
+        raise PixelsError(ERR_ARG, "band_classify: negative shape")
+    keep, p1, p2, n = _anchors(bin1, bin2)
+    out = np.zeros(n, dtype=np.uint8)
+    rc = lib().modle_pixels_band_classify(int(nrows), int(ncols), int(bin_offset), p1, p2, n,
+                                          out.ctypes.data_as(C.POINTER(C.c_uint8)))
+    del keep
+    if rc != 0:
+        raise PixelsError(rc, "band_classify: invalid argument (0 < nrows <= ncols, or both 0; n < 2^31)")
+    return out
+
+
+def _band_call(fn, st, *args):
+    """a call of the library that fills the modle_pixels_band_stats `st`: BandStats, or BandListError when the
+    list is out of order or holds a negative count"""
+    err = C.create_string_buffer(512)
+    rc = fn(*args, err, len(err))
+    if rc in (ERR_ORDER, ERR_RANGE):
+        raise BandListError(rc, err.value.decode(errors="replace"), st.tuple())
+    if rc != 0:
+        raise PixelsError(rc, err.value.decode(errors="replace"))
+    return st.tuple()
 
 
 def sample_threshold(frac):
@@ -579,6 +642,40 @@ class Extractor:
                              stream=stream)
 
 
+    def band_check(self, d_bin1, d_bin2, d_count, n, nrows, ncols, bin_offset=0, d_row_start=None, stream=None):
+        """step 1 of pixels to band: one pass over the `n` pixels in the device arrays `d_bin1`, `d_bin2` (int64)
+        and `d_count` (int32) -- class, order, sign and the sums -- and the fill of the device array
+        `d_row_start` (int64[ncols + 1]; None when only the statistics are wanted).  Returns BandStats; a list
+        that is not strictly increasing in (bin1, bin2) or holds a negative count raises BandListError (ERR_ORDER,
+        ERR_RANGE) with the statistics.  Waits for the stream (modle_pixels_band_check)."""
+        st = _CBandStats()
+        return _band_call(self._L.modle_pixels_band_check, st, self._h, d_bin1, d_bin2, d_count, int(n), int(nrows),
+                          int(ncols), int(bin_offset), d_row_start, C.byref(st), _stream_ptr(stream))
+
+    def band_fill_into(self, d_bin2, d_count, n, nrows, ncols, bin_offset, d_row_start, d_out, out_words, stream=None):
+        """step 2: enqueues the fill of the caller-owned device array `d_out` (uint32[nrows * ncols + 1], the
+        band's layout) from the pixels band_check accepted and the row starts it wrote; every word is written,
+        none outside (modle_pixels_band_fill)"""
+        _call(self._L.modle_pixels_band_fill, self._h, d_bin2, d_count, int(n), int(nrows), int(ncols),
+              int(bin_offset), d_row_start, d_out, int(out_words), _stream_ptr(stream))
+
+    def band_from_host(self, bin1, bin2, count, nrows, ncols, bin_offset, d_out, out_words, stream=None):
+        """host pixels (int64 ids, int32 counts) up, checked and scattered into the device array `d_out`
+        (uint32[nrows * ncols + 1]); returns BandStats, raises BandListError with nothing written.  Waits
+        (modle_pixels_band_from_host)."""
+        keep, p1, p2, n = _anchors(bin1, bin2)
+        cnt = np.ascontiguousarray(count, dtype=np.int32).reshape(-1)
+        if len(cnt) != n:
+            raise PixelsError(ERR_ARG, f"band_from_host: {n} pixels and {len(cnt)} counts")
+        st = _CBandStats()
+        i64 = lambda a: a.ctypes.data if n else None
+        out = _band_call(self._L.modle_pixels_band_from_host, st, self._h, i64(keep[0]), i64(keep[1]), i64(cnt), n,
+                         int(nrows), int(ncols), int(bin_offset), d_out, int(out_words), C.byref(st),
+                         _stream_ptr(stream))
+        del keep
+        return out
+
+
 def extractor(device=0):
     """the process-wide context of `device`"""
     ex = _EXTRACTORS.get(int(device))
@@ -700,3 +797,22 @@ def sample(d_band, nrows, ncols, threshold, seed, salt=0, bin_offset=0, rest=Fal
     """The kept contacts (`rest`: the others) of the band at device pointer `d_band` as Pixels, sampled and
     extracted on the device."""
     return extractor(device).sample(d_band, nrows, ncols, threshold, seed, salt, bin_offset, rest, stream)
+
+
+def band_check(d_bin1, d_bin2, d_count, n, nrows, ncols, bin_offset=0, d_row_start=None, stream=None, device=0):
+    """BandStats of the `n` pixels in device arrays against a band of the given shape, and their row starts into
+    the device array `d_row_start`; waits."""
+    return extractor(device).band_check(d_bin1, d_bin2, d_count, n, nrows, ncols, bin_offset, d_row_start, stream)
+
+
+def band_fill_into(d_bin2, d_count, n, nrows, ncols, bin_offset, d_row_start, d_out, out_words, stream=None, device=0):
+    """The band of the checked pixels, scattered into the device array `d_out`; enqueued on `stream`, nothing
+    crosses to the host."""
+    extractor(device).band_fill_into(d_bin2, d_count, n, nrows, ncols, bin_offset, d_row_start, d_out, out_words,
+                                     stream)
+
+
+def band_from_host(bin1, bin2, count, nrows, ncols, bin_offset, d_out, out_words, stream=None, device=0):
+    """The band of host pixels in the device array `d_out`: copied up, checked and scattered on the device;
+    returns BandStats."""
+    return extractor(device).band_from_host(bin1, bin2, count, nrows, ncols, bin_offset, d_out, out_words, stream)

@@ -118,6 +118,11 @@ struct modle_pixels_handle {
   GrowBuf<uint64_t, true> pile_out;
   // modle_pixels_sample_to_host: the kept band and the rest band (modle_sample.hip)
   GrowBuf<uint32_t> sample_kept, sample_rest;
+  // modle_pixels_band_*: the words band_check reduces into, and of modle_pixels_band_from_host the pixels
+  // and their row starts (modle_band.hip)
+  GrowBuf<uint64_t, true> band_words;
+  GrowBuf<int64_t> band_bin1, band_bin2, band_rows;
+  GrowBuf<int32_t> band_count;
 };
 
 #endif
