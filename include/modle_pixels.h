@@ -1,7 +1,7 @@
 /* modle_pixels.h -- C ABI of the sparse-pixel extraction (modle_amd/libmodle_pixels.so), of the
  * coarsening of a band, of its dense regions, of its marginals, of its insulation sums, of its
- * dot candidates, of its pileups and of its random sampling, and of the way back from sorted pixels to
- * a band (further down).
+ * dot candidates, of its pileups and of its random sampling, of the way back from sorted pixels to
+ * a band, and of the comparison of two bands stripe by stripe (further down).
  *
  * The simulation leaves every interval as a dense band matrix in device memory
  * (modle_hip_interval_outputs).  A cooler file is made of the non-zero pixels only, sorted by
@@ -527,6 +527,59 @@ int modle_pixels_band_from_host(modle_pixels_handle* h, const int64_t* bin1, con
                                 const int32_t* count, uint64_t n, uint64_t nrows, uint64_t ncols,
                                 int64_t bin_offset, uint32_t* d_out, uint64_t out_words,
                                 modle_pixels_band_stats* stats, void* stream, char* err, size_t errlen);
+
+/* ---- Stripes: two bands compared stripe by stripe -----------------------------------------------------
+ *
+ * Two bands A (the reference, d_ref) and B (the target, d_tgt) of one shape, each in the layout above; they
+ * may be the same pointer.  With M(i, j) = band[j * nrows + (j - i)] the stripes of bin c, 0 <= c < ncols,
+ * have nrows entries each (evaluate.stripes; the method of `modle_tools evaluate`):
+ *     vertical    v[i] = M(c - i, c) for i <= c,          0 for the i above c
+ *     horizontal  h[i] = M(c, c + i) for c + i < ncols,   0 beyond
+ * and the zero padding counts as entries.  Per direction and bin the call writes the integer sums that
+ * Pearson's and Spearman's correlation, the RMSE and the Euclidean distance of the two stripes are made of;
+ * the scores themselves are one host statement (modle_amd/pixels.py: stripe_scores).  `what` is a mask that
+ * selects three blocks of rows, each row ncols uint64 words, one per bin:
+ *     MODLE_PIXELS_STRIPES_MOMENTS  9 rows  n, Sa, Sb, Saa_lo, Saa_hi, Sbb_lo, Sbb_hi, Sab_lo, Sab_hi
+ *         n == nrows, Sa = sum a, Saa = sum a * a, Sab = sum a * b over the nrows entries; the second
+ *         moments are 128-bit sums in two words, so every shape and every uint32 count is exact: there is
+ *         no range refusal.
+ *     MODLE_PIXELS_STRIPES_MASKED   9 rows  the same sums over the entries with a != 0 and b != 0 (the
+ *         weight-0/1 form of --exclude-zero-pixels); n is their number.
+ *     MODLE_PIXELS_STRIPES_RANKS    3 rows  Raa, Rbb, Rab: the sums of R2(a) * R2(a), R2(b) * R2(b) and
+ *         R2(a) * R2(b) over the nrows entries, R2(x) = 2 * #{y < x} + #{y == x} + 1 counted within x's own
+ *         stripe, padding included: twice the average rank (ties share the mean of their positions).  The
+ *         sum of R2 over a stripe is nrows * (nrows + 1) whatever it holds and is not stored.  Accepted for
+ *         nrows <= MODLE_PIXELS_MAX_STRIPE.
+ * The output is uint64[2][rows][ncols]: direction 0 vertical, 1 horizontal; the blocks in bit order; rows =
+ * modle_pixels_stripes_rows(what).  EVERY output word is written exactly once, with a plain store: the caller
+ * does not pre-zero.  The words of either band that are no pixels are never read, and every address is a
+ * function of nrows and ncols alone.  Nothing here uses floating point.
+ *
+ * There is no coarse form: coarsen either band with modle_pixels_coarsen and pass the result.
+ *
+ * MODLE_PIXELS_ERR_ARG, with nothing written: a null pointer, nrows == 0, nrows > ncols, what == 0 or with
+ * a bit that is not defined, RANKS with nrows > MODLE_PIXELS_MAX_STRIPE, out_words != 2 * rows * ncols, a
+ * d_out that is not 8-byte aligned or overlaps either band. */
+#define MODLE_PIXELS_STRIPES_MOMENTS 1
+#define MODLE_PIXELS_STRIPES_MASKED 2
+#define MODLE_PIXELS_STRIPES_RANKS 4
+#define MODLE_PIXELS_MAX_STRIPE 4096
+
+/* The rows per direction of the mask `what`: 9, 9 and 3 for the three blocks.  Host only: no device is
+ * needed.  what == 0 and a bit that is not defined are MODLE_PIXELS_ERR_ARG. */
+int modle_pixels_stripes_rows(uint64_t what);
+
+/* Enqueues the sums into the device array d_out (uint64[2][rows][ncols], `out_words` == 2 * rows * ncols
+ * words) on `stream`; the call does not wait. */
+int modle_pixels_stripes(modle_pixels_handle* h, const uint32_t* d_ref, const uint32_t* d_tgt, uint64_t nrows,
+                         uint64_t ncols, uint64_t what, uint64_t* d_out, uint64_t out_words, void* stream,
+                         char* err, size_t errlen);
+
+/* The same into a pinned host buffer of the context (grown on demand, freed by modle_pixels_destroy): *rows
+ * (uint64[2][rows][ncols]) stays valid until the next call on the context.  Waits for `stream`. */
+int modle_pixels_stripes_to_host(modle_pixels_handle* h, const uint32_t* d_ref, const uint32_t* d_tgt,
+                                 uint64_t nrows, uint64_t ncols, uint64_t what, const uint64_t** rows,
+                                 void* stream, char* err, size_t errlen);
 
 #ifdef __cplusplus
 }

@@ -560,6 +560,75 @@ class BandAnalyses:
         bands = self.sample_tensors(interval_id, frac, seed, salt, bin_offset, rest=True)
         return tuple(pixels.extract(t.data_ptr(), nrows, ncols, bin_offset, device=self.device) for t in bands)
 
+    def _band_pair(self, interval_id, other, other_id, factor, first_bin, other_factor, other_first_bin, stream):
+        """(d_ref, d_tgt, nrows, ncols, what keeps them alive) for the stripe analyses: the band `other_id` of
+        `other` is the reference and this object's `interval_id` the target, each through _band.  ValueError
+        when the two lie on different devices or differ in shape."""
+        if int(other.device) != int(self.device):
+            raise ValueError(f"stripes: the reference lies on device {other.device}, the band on {self.device}")
+        d_tgt, nrows, ncols, keep = self._band(interval_id, factor, first_bin, stream)
+        d_ref, nr, nc, other_keep = other._band(other_id, other_factor, other_first_bin, stream)
+        if (nr, nc) != (nrows, ncols):
+            raise ValueError(f"stripes: the reference is a band of {nr} diagonals and {nc} bins, the band has "
+                             f"{nrows} and {ncols}")
+        return d_ref, d_tgt, nrows, ncols, (keep, other_keep)
+
+    def stripe_moments(self, interval_id, other, other_id, what=1, factor=1, first_bin=0, other_factor=1,
+                       other_first_bin=0, stream=None):
+        """The interval compared stripe by stripe with band `other_id` of `other` (any owner of bands on the
+        same device, a Simulator or a LoadedBands; this object itself serves): numpy uint64 [2,
+        pixels.stripes_rows(what), ncols], for the vertical and the horizontal stripe of every bin the integer
+        sums pixels.STRIPES_MOMENTS, _MASKED and _RANKS select (include/modle_pixels.h), formed on the device
+        from the two bands where they lie (pixels.stripes).  `other` is the reference (a), the interval the
+        target (b), as in evaluate.compare(ref, tgt).  Either side is first coarsened on the device when its
+        factor is above 1 (`first_bin` as for pixels()); the two shapes must then be equal, else ValueError.
+        Only the sums cross to the host.  Call it after wait()."""
+        from . import pixels
+
+        d_ref, d_tgt, nrows, ncols, keep = self._band_pair(interval_id, other, other_id, factor, first_bin,
+                                                           other_factor, other_first_bin, stream)
+        out = pixels.extractor(self.device).stripes(d_ref, d_tgt, nrows, ncols, what, stream)  # (waits)
+        del keep
+        return out
+
+    def stripe_scores(self, interval_id, other, other_id, metric, exclude_zero_pixels=False, factor=1, first_bin=0,
+                      other_factor=1, other_first_bin=0, stream=None):
+        """(vertical, horizontal): the `metric` (pearson, spearman, rmse, eucl_dist) of every bin's stripes
+        against the reference, two numpy float64 [ncols], what evaluate.compare(ref, tgt, ...) gives for the
+        two directions: pixels.stripe_scores of stripe_moments with the blocks the metric needs.
+        `exclude_zero_pixels`: over the entries that are non-zero in both; there is no such spearman."""
+        from . import pixels
+
+        if metric == "spearman" and exclude_zero_pixels:
+            raise ValueError("stripe_scores: spearman without the zero pixels has ranks that are no integers; "
+                             "evaluate.compare forms it on the host")
+        what = pixels.STRIPES_MASKED if exclude_zero_pixels else pixels.STRIPES_MOMENTS
+        if metric == "spearman":
+            what |= pixels.STRIPES_RANKS
+        rows = self.stripe_moments(interval_id, other, other_id, what, factor, first_bin, other_factor,
+                                   other_first_bin, stream)
+        return tuple(pixels.stripe_scores(rows[d], metric, exclude_zero_pixels) for d in (0, 1))
+
+    def stripe_moments_tensor(self, interval_id, other, other_id, what=1, factor=1, first_bin=0, other_factor=1,
+                              other_first_bin=0, stream=None):
+        """The sums of stripe_moments as one torch int64 tensor [2, rows, ncols] on the device, filled there
+        by the kernels: nothing crosses to the host.  The words hold the uint64 sums bit for bit.  The work is
+        enqueued on `stream` (None: the default stream, on which torch orders its own work); it is waited
+        for only when a side was coarsened into a scratch band, which goes when this returns."""
+        import torch
+
+        from . import pixels
+
+        d_ref, d_tgt, nrows, ncols, keep = self._band_pair(interval_id, other, other_id, factor, first_bin,
+                                                           other_factor, other_first_bin, stream)
+        out = torch.empty((2, pixels.stripes_rows(what), ncols), dtype=torch.int64,
+                          device=torch.device("cuda", self.device))
+        pixels.stripes_into(d_ref, d_tgt, nrows, ncols, what, out.data_ptr(), out.numel(), stream,
+                            device=self.device)
+        if any(k is not None for k in keep):
+            torch.cuda.synchronize(out.device)
+        return out
+
 
 
 # ---------------------------------------------------------------------------------------------

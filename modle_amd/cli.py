@@ -15,7 +15,12 @@ per bin over sliding diamond windows, summed on the GPU; with --dots `<prefix>_d
 enriched over their four HiCCUPS neighbourhoods, found on the GPU; with --pileup-at `<prefix>_pileup.tsv`,
 the windows around the dots, the barriers or the pairs of a BEDPE file, summed on the GPU; with
 --subsample-frac or --subsample-to `<prefix>_sampled.cool`, the matrix with every contact kept with one
-probability, drawn on the GPU (with --subsample-split also `<prefix>_sampled_rest.cool`, the others).  Everything heavy is native: parsing and
+probability, drawn on the GPU (with --subsample-split also `<prefix>_sampled_rest.cool`, the others); with
+--compare-to REF.cool (or REF.mcool::/resolutions/R) `<prefix>_stripes.tsv`, every bin's vertical and
+horizontal stripe scored against the reference file the way `evaluate` scores them, from integer sums formed
+on the GPU: --compare-metrics LIST (pearson, spearman, rmse, eucl_dist; default pearson), --compare-resolution
+R (a multiple of -r, the bin size of REF; default -r) and --compare-exclude-zero-pixels (not with spearman).
+Everything heavy is native: parsing and
 task generation in libmodle_hip.so (host), the simulation on the MI355X (one process per GPU;
 under torch.distributed.run the cells are sharded over the ranks and the matrices are summed
 with RCCL, or with --dist-backend gloo on host copies), the writers in libmodle_cooler.so.  `-t/--threads` is accepted and ignored.
@@ -114,6 +119,18 @@ MAX_PILEUP_FLANK_BINS = 32  # include/modle_pixels.h
 DOT_FOLDS = (1.75, 1.75, 1.5, 1.5)  # HiCCUPS': donut, lower-left, horizontal, vertical
 
 
+COMPARE_METRICS = ("pearson", "spearman", "rmse", "eucl_dist")  # pixels.STRIPE_METRICS, evaluate.METRICS
+
+
+def metric_list(text):
+    """`pearson,rmse`: the comma-separated metrics of --compare-metrics, each once"""
+    items = [t.strip() for t in text.split(",")]
+    if any(t not in COMPARE_METRICS for t in items) or len(set(items)) != len(items):
+        raise argparse.ArgumentTypeError(f"{text!r} is not a comma-separated list of distinct metrics of "
+                                         f"{', '.join(COMPARE_METRICS)}")
+    return items
+
+
 def fold_list(text):
     """`1.75,1.75,1.5,1.5`: the four thresholds of --dots-folds, finite and not negative"""
     try:
@@ -174,6 +191,10 @@ def dots_path(prefix):
 
 def pileup_path(prefix):
     return prefix + "_pileup.tsv"
+
+
+def stripes_path(prefix):
+    return prefix + "_stripes.tsv"
 
 
 def sampled_paths(prefix, mcool=False):
@@ -273,6 +294,14 @@ def add_analysis_arguments(io):
     io.add_argument("--subsample-split", action="store_true",
                     help="with --subsample-frac / --subsample-to: also write <prefix>_sampled_rest.cool, the "
                          "contacts that were not kept: two disjoint pseudo-replicates that add up to the matrix")
+    # The comparison with a reference file (<prefix>_stripes.tsv; the module's text describes the four
+    # options).  They are parsed like the others and kept out of the generated help: the text of
+    # `simulate --help` is held fixed by tests/golden/simulate_help.txt.
+    io.add_argument("--compare-to", default=None, metavar="REF", help=argparse.SUPPRESS)
+    io.add_argument("--compare-metrics", type=metric_list, default=None, metavar="LIST", help=argparse.SUPPRESS)
+    io.add_argument("--compare-resolution", type=genomic_distance, default=None, metavar="R",
+                    help=argparse.SUPPRESS)
+    io.add_argument("--compare-exclude-zero-pixels", action="store_true", default=None, help=argparse.SUPPRESS)
 
 
 def build_parser():
@@ -448,8 +477,13 @@ Pileup = collections.namedtuple("Pileup", "path resolution flank corner sources"
 # with --skip-output, which is refused), the fraction or the target (one of them None), the seed, and
 # whether the second file is written
 Subsample = collections.namedtuple("Subsample", "path rest_path frac target seed split")
+# what --compare-to asks for: the file (None with --skip-output, which is refused), the reference cooler as
+# given, the bin size of the comparison, the metrics in the order given, whether zero pixels are left out,
+# and what preflight read of the reference: its bin size and its chromosomes
+Stripes = collections.namedtuple("Stripes", "path reference resolution metrics exclude_zero ref_bin_size ref_chroms")
 # (`insulation`, `dots` and `pileup` came later: at the end, and None unless asked for; the sampled files
-# are not among the fields: subsample_plan, which preflight calls for its refusals, plans them)
+# and the comparison are not among the fields: subsample_plan and stripes_plan, which preflight calls for
+# their refusals, plan them)
 Preflight = collections.namedtuple("Preflight", "bin_sizes outputs rank world device insulation dots pileup",
                                    defaults=(None, None, None))
 
@@ -570,6 +604,48 @@ def dots_options(a, cfg):
     return Dots(None, res, window, peak, min_count, folds, min_diag, radius)
 
 
+def stripes_options(a, cfg):
+    """The comparison with a reference cooler the arguments ask for, as a Stripes without a path, or None.
+    SystemExit: a --compare-* option without --compare-to, --skip-output (the comparison is a file of the
+    output stage, which checks it against the cooler's sums), spearman together with
+    --compare-exclude-zero-pixels (its weighted ranks are no integers: `evaluate` has it), a resolution that
+    is no multiple of -r, a reference file that is missing or cannot be read as a cooler, or whose bin size is
+    not the resolution of the comparison."""
+    if a.compare_to is None:
+        _needs("--compare-to", (("--compare-metrics", a.compare_metrics),
+                                ("--compare-resolution", a.compare_resolution),
+                                ("--compare-exclude-zero-pixels", a.compare_exclude_zero_pixels)))
+        return None
+    if a.skip_output:
+        raise SystemExit("--compare-to needs the output stage: it excludes --skip-output")
+    metrics = list(a.compare_metrics or ["pearson"])
+    exclude_zero = bool(a.compare_exclude_zero_pixels)
+    if exclude_zero and "spearman" in metrics:
+        raise SystemExit("--compare-exclude-zero-pixels: spearman without the zero pixels has ranks that are no "
+                         "integers; the `evaluate` subcommand forms it on the host")
+    res = _analysis_resolution("--compare-resolution", a.compare_resolution, cfg)
+    path = a.compare_to.split("::", 1)[0]
+    if not os.path.isfile(path):
+        raise SystemExit(f"--compare-to: {path} is no file")
+    from . import cooler
+
+    try:
+        with cooler.CoolerReader(a.compare_to) as reader:
+            ref_bin_size, ref_chroms = int(reader.bin_size), list(reader.chroms)
+    except cooler.CoolerError as e:
+        raise SystemExit(f"--compare-to: cannot read {a.compare_to}: {e}")
+    if ref_bin_size != res:
+        raise SystemExit(f"--compare-to: {a.compare_to} has a bin size of {ref_bin_size}, the comparison runs at "
+                         f"{res} (-r, or --compare-resolution)")
+    return Stripes(None, a.compare_to, res, metrics, exclude_zero, ref_bin_size, ref_chroms)
+
+
+def stripes_plan(a, cfg):
+    """stripes_options with the path of the file, `<prefix>_stripes.tsv`"""
+    plan = stripes_options(a, cfg)
+    return None if plan is None else plan._replace(path=stripes_path(a.output_prefix))
+
+
 def insulation_options(a, cfg):
     """The insulation track the arguments ask for, as an Insulation without a path, or None.
     SystemExit: --insulation-resolution or --insulation-ignore-diags without --insulation-windows, a
@@ -596,9 +672,9 @@ def insulation_options(a, cfg):
 def preflight(a, cfg):
     """What the arguments alone settle and refuse, without a genome or a GPU.  SystemExit: a bad
     --mcool-resolutions list; --coverage-ignore-diags without --coverage, or negative; what
-    insulation_options, dots_options, pileup_options and subsample_options refuse; on rank 0, an output that
-    exists without --force (cooler or .mcool, then bigwig, then .npz, then the expected, the coverage, the
-    insulation, the dots and the pileup file, then the sampled files).  With
+    insulation_options, dots_options, pileup_options, subsample_options and stripes_options refuse; on rank 0,
+    an output that exists without --force (cooler or .mcool, then bigwig, then .npz, then the expected, the
+    coverage, the insulation, the dots and the pileup file, then the sampled files, then the stripes).  With
     --skip-output no file is planned and none is looked at."""
     if a.coverage_ignore_diags is not None:
         if not a.coverage:
@@ -609,6 +685,7 @@ def preflight(a, cfg):
     dots = dots_options(a, cfg)
     pile = pileup_options(a, cfg, dots)
     sub = subsample_plan(a, cfg)
+    cmp_ = stripes_plan(a, cfg)
     # (a bad list ends the run here, before anything is imported or simulated)
     bin_sizes = None if a.mcool_resolutions is None else mcool_bin_sizes(a.mcool_resolutions, cfg.bin_size)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -635,7 +712,7 @@ def preflight(a, cfg):
         for p in (outputs.cooler, outputs.bigwig, outputs.dense, outputs.expected, outputs.coverage,
                   None if ins is None else ins.path, None if dots is None else dots.path,
                   None if pile is None else pile.path, None if sub is None else sub.path,
-                  None if sub is None or not sub.split else sub.rest_path):
+                  None if sub is None or not sub.split else sub.rest_path, None if cmp_ is None else cmp_.path):
             if p and os.path.exists(p) and not a.force:
                 raise SystemExit(f"refusing to overwrite {p}: pass --force to overwrite")
     return Preflight(bin_sizes, outputs, rank, world, device, ins, dots, pile)
@@ -682,6 +759,12 @@ def check_plan(a, cfg, pre, plan, chroms):
             raise SystemExit(f"--pileup-flank: the flank of {bad[2]} ({bad[3]} bins of {pre.pileup.resolution}) does "
                              f"not fit the band of {bad[1]} ({bad[4]} diagonals): the largest flank that fits is "
                              f"{bad[5]} ({bad[5] // pre.pileup.resolution} bins)")
+    cmp_ = stripes_plan(a, cfg)
+    if cmp_ is not None:
+        bad = driver.stripes_misfit(plan, int(cfg.bin_size), cmp_.resolution, cmp_.metrics, cmp_.ref_bin_size,
+                                    cmp_.ref_chroms, chroms)
+        if bad is not None:
+            raise SystemExit(f"--compare-to {cmp_.reference}: {bad}")
     return driver.dense_regions(plan, int(cfg.bin_size), chroms, a.dense_region) if a.dense_region else []
 
 
@@ -745,7 +828,7 @@ def simulate(a, log=print):
         occupancies = driver.write_outputs(
             sim, cfg, plan, ids, tensors, pre.outputs, pre.bin_sizes, regions, pre.rank, log, a.dist_backend,
             coverage_min_diag=a.coverage_ignore_diags or 0, insulation=pre.insulation, dots=pre.dots, pileup=pre.pileup,
-            subsample=subsample_plan(a, cfg),
+            subsample=subsample_plan(a, cfg), stripes=stripes_plan(a, cfg),
             assembly=a.assembly_name,
             generated_by="modle_amd (MI355X)", metadata_json=meta,
             force_overwrite=a.force, chroms=chroms)
@@ -857,7 +940,7 @@ def analyze(a, log=print):
             driver.write_outputs(
                 bands, cfg, plan, ids, None, pre.outputs, pre.bin_sizes, regions, 0, log,
                 coverage_min_diag=a.coverage_ignore_diags or 0, insulation=pre.insulation, dots=pre.dots,
-                pileup=pre.pileup, subsample=subsample_plan(a, cfg), assembly=a.assembly_name,
+                pileup=pre.pileup, subsample=subsample_plan(a, cfg), stripes=stripes_plan(a, cfg), assembly=a.assembly_name,
                 generated_by="modle_amd analyze (MI355X)", metadata_json=meta, force_overwrite=a.force,
                 chroms=reader.chroms)
         finally:

@@ -910,6 +910,122 @@ def _interval_pileup(sim, plan, ids, marginals, cache, flank, name, k, factor, f
     return pile, n_used, api.pileup_expected_terms(dist_hist, diag_sum, nc, flank)
 
 
+def stripes_what(metrics, exclude_zero):
+    """the mask of pixels.stripes for the `metrics` of --compare-metrics: the moments always (check_stripes
+    reads them), the masked moments with --compare-exclude-zero-pixels, the rank sums for spearman"""
+    from . import pixels
+
+    return pixels.STRIPES_MOMENTS | (pixels.STRIPES_MASKED if exclude_zero else 0) | \
+        (pixels.STRIPES_RANKS if "spearman" in metrics else 0)
+
+
+def stripes_misfit(plan, base, resolution, metrics, ref_bin_size, ref_chroms, chroms=None):
+    """What keeps the run from being compared with a reference cooler of `ref_bin_size` and the chromosomes
+    `ref_chroms` ([(name, size)]) at `resolution`, as a sentence, or None: another bin size; a chromosome of an
+    entry of the plan that has a matrix which the file lacks or holds with another length (`chroms`: the
+    run's [(name, size)]; None: the sizes the plan carries); spearman on a band deeper than
+    pixels.MAX_STRIPE diagonals at `resolution`."""
+    from . import pixels
+
+    if int(ref_bin_size) != int(resolution):
+        return f"the file has a bin size of {int(ref_bin_size)}, the comparison runs at {int(resolution)}"
+    have, sizes = dict(ref_chroms), dict(chroms if chroms is not None else _chroms_of_plan(plan))
+    for _, entry, _, _, (nr, _) in plan_bands(plan, base, resolution):
+        name = entry["interval"]["name"]
+        if name not in have:
+            return f"the file has no chromosome {name}"
+        if int(have[name]) != int(sizes[name]):
+            return f"chromosome {name} has {int(have[name])} bp in the file and {int(sizes[name])} in the run"
+        if "spearman" in metrics and nr > pixels.MAX_STRIPE:
+            return (f"spearman ranks stripes of at most {pixels.MAX_STRIPE} entries, the band of "
+                    f"{interval_name(entry['interval'])} has {nr} diagonals at {int(resolution)}")
+    return None
+
+
+def check_stripes(name, rows, nrows, ref_sum, run_sum):
+    """What ties the sums of the stripes (api.BandAnalyses.stripe_moments with pixels.STRIPES_MOMENTS among
+    the blocks, which then come first) to the two bands, in exact integers, before a row is written: every
+    pixel lies in one vertical and in one horizontal stripe, so in either direction the Sa of the bins add up
+    to the contacts of the reference band, `ref_sum`, and the Sb to those of the run's, `run_sum`; and every n
+    is the depth of the band, `nrows`.  RuntimeError, naming the interval and what fails."""
+    for d, direction in enumerate(("vertical", "horizontal")):
+        n, sa, sb = ([int(x) for x in rows[d][k]] for k in range(3))
+        if any(x != int(nrows) for x in n):
+            raise RuntimeError(f"{name}: a {direction} stripe counts {next(x for x in n if x != int(nrows))} entries, "
+                               f"the band has {int(nrows)} diagonals")
+        for what, got, want in (("reference", sum(sa), int(ref_sum)), ("run", sum(sb), int(run_sum))):
+            if got != want:
+                raise RuntimeError(f"{name}: the {direction} stripes of the {what} add up to {got} contacts, "
+                                   f"its band holds {want}")
+
+
+def stripes_header(reference, resolution, exclude_zero, metrics):
+    """the two header lines of <prefix>_stripes.tsv: what was compared, then the columns"""
+    return (f"# reference={reference} resolution={int(resolution)} "
+            f"exclude_zero_pixels={'yes' if exclude_zero else 'no'}\n"
+            "chrom\tstart\tend" + "".join(f"\t{m}_vertical\t{m}_horizontal" for m in metrics) + "\n")
+
+
+def stripes_lines(iv, base, factor, scores):
+    """the rows of <prefix>_stripes.tsv for one interval, one per bin of `factor` * `base` base pairs: chrom,
+    start, end (clipped to the interval like insulation_lines), then per metric the repr of the score of
+    the vertical and of the horizontal stripe, NaN as `nan`.  `scores`: per metric the (vertical, horizontal)
+    pair of api.BandAnalyses.stripe_scores, in the order of the columns."""
+    start, end, base, k = int(iv["start"]), int(iv["end"]), int(base), int(factor)
+    p = (start // base) % k
+    out = []
+    for c in range(len(scores[0][0]) if scores else 0):
+        lo, hi = start + max(0, c * k - p) * base, min(end, start + ((c + 1) * k - p) * base)
+        out.append(f"{iv['name']}\t{lo}\t{hi}" + "".join(f"\t{float(v[c])!r}\t{float(h[c])!r}" for v, h in scores)
+                   + "\n")
+    return out
+
+
+def write_stripes(path, plan, base, reference, resolution, exclude_zero, metrics, stripes):
+    """<prefix>_stripes.tsv: the header, then the scores of every bin of every entry of the plan that is not
+    skipped, in plan order, at the bin size `resolution` (a multiple of `base`).  `stripes(k, factor,
+    first_bin)` returns the scores of plan entry k per metric -- what stripes_lines takes -- or None for an
+    entry without a matrix."""
+    with open(path, "w") as fh:
+        fh.write(stripes_header(reference, resolution, exclude_zero, metrics))
+        for k, entry, first_bin, factor, _ in plan_bands(plan, base, resolution):
+            got = stripes(k, factor, first_bin)
+            if got is not None:
+                fh.writelines(stripes_lines(entry["interval"], base, factor, got))
+
+
+@_needs_matrix
+def _interval_stripes(sim, plan, ids, reader, metrics, exclude_zero, sums, k, factor, first_bin):
+    """write_stripes' callback.  The reference's pixels of the interval's chromosome are scattered into a band
+    of the interval's own shape at the comparison's bin size on the device (api.LoadedBands.load_pixels at the
+    interval's first bin in the file), the run's band is coarsened there where `factor` is above 1, the sums of
+    the stripes are formed from the two where they lie and checked (check_stripes) against the contacts the
+    reference band was loaded with and those of the run's band -- `sums[k]` of the cooler at the base bin size,
+    else counted on the coarse band --, and the reference band is let go."""
+    from . import pixels
+
+    entry = plan[k]
+    iv = entry["interval"]
+    nr, nc = insulation_shape(entry["nrows"], entry["ncols"], first_bin, factor)
+    bin1, bin2, count, chrom_first = reader.pixels(iv["name"])
+    ref = api.LoadedBands(sim.device)
+    try:
+        rid, st = ref.load_pixels(bin1, bin2, count, nr, nc, chrom_first + coarse_bin_range(first_bin, entry["ncols"],
+                                                                                            factor)[0])
+        del bin1, bin2, count
+        rows = sim.stripe_moments(ids[k], ref, rid, stripes_what(metrics, exclude_zero), factor, first_bin)
+        if factor == 1 and k in sums:
+            run_sum = sums[k]
+        else:
+            d_band, nrows, ncols, keep = sim._band(ids[k], factor, first_bin, None)
+            run_sum = pixels.extractor(sim.device).count(d_band, nrows, ncols).sum  # (waits)
+            del keep
+        check_stripes(interval_name(iv), rows, nr, st.sum_in, run_sum)
+    finally:
+        ref.close()
+    return [tuple(pixels.stripe_scores(rows[d], m, exclude_zero) for d in (0, 1)) for m in metrics]
+
+
 def sample_matrices(sim, cfg, plan, ids, total, subsample, bin_sizes, log, **attrs):
     """Writes `subsample.path`, the cooler (or .mcool) of the kept contacts, and with `subsample.split`
     `subsample.rest_path`, that of the others.  The threshold is that of `subsample.frac`, or with
@@ -965,7 +1081,8 @@ def reduce_missed(missed, backend, rank, device=None):
 
 
 def write_outputs(sim, cfg, plan, ids, tensors, outputs, bin_sizes=None, regions=(), rank=0, log=print,
-                  backend="nccl", coverage_min_diag=0, insulation=None, dots=None, pileup=None, subsample=None, **attrs):
+                  backend="nccl", coverage_min_diag=0, insulation=None, dots=None, pileup=None, subsample=None,
+                  stripes=None, **attrs):
     """What a finished launch writes while the simulator is open: the state log (every rank its
     own), then on rank 0 the cooler or .mcool with the missing-interactions warnings, the dense
     `regions` (of dense_regions), the distance-decay curves (at every bin size of the file) and the
@@ -974,7 +1091,9 @@ def write_outputs(sim, cfg, plan, ids, tensors, outputs, bin_sizes=None, regions
     written), and the dots `dots` (a cli.Dots; None or without a path: not written),
     and the pileups `pileup` (a cli.Pileup; likewise; its source `dots` piles the dots just written),
     and the sampled matrix `subsample` (a cli.Subsample; likewise): the same file as the cooler from the kept
-    half of a binomial thinning of every interval (sample_matrices), and with its `split` the other half.  `outputs.state_log`, `.cooler`, `.dense`,
+    half of a binomial thinning of every interval (sample_matrices), and with its `split` the other half,
+    and the comparison `stripes` (a cli.Stripes; likewise): the scores of every bin's stripes against the
+    reference cooler it names (write_stripes).  `outputs.state_log`, `.cooler`, `.dense`,
     `.expected`, `.coverage`: the paths, None for a file that is not written; without a cooler
     (--skip-output) the matrices are only summed, for the warnings.  `tensors`: with several ranks the (contacts, occupancy) torch tensors per plan entry;
     they are reduced in place onto rank 0 (reduce_to_rank0 with `backend`), which extracts from the
@@ -1067,6 +1186,15 @@ def write_outputs(sim, cfg, plan, ids, tensors, outputs, bin_sizes=None, regions
                      functools.partial(_interval_pileup, sim, plan, ids, marginals, {}, int(pileup.flank) // res),
                      unplaced)
         log(f"written {pileup.path}")
+    if stripes is not None and stripes.path is not None:
+        from . import cooler
+
+        with cooler.CoolerReader(stripes.reference) as reader:
+            write_stripes(stripes.path, plan, int(cfg.bin_size), stripes.reference, stripes.resolution,
+                          stripes.exclude_zero, stripes.metrics,
+                          functools.partial(_interval_stripes, sim, plan, ids, reader, list(stripes.metrics),
+                                            bool(stripes.exclude_zero), sums))
+        log(f"written {stripes.path}")
     return occupancies
 
 

@@ -4,11 +4,13 @@ memory, in cooler order, found on the GPU; the band at a multiple of its bin siz
 of it as dense matrices; its marginals, the sums per diagonal and per bin; its insulation sums
 over sliding diamond windows; its dots, the pixels enriched over their HiCCUPS neighbourhoods;
 its pileups, the windows around anchor pairs summed into one; and its random sampling, every contact
-kept with one probability by a generator keyed by the pixel's coordinates; and the way back, sorted pixels
-checked and scattered into a band on the GPU.
+kept with one probability by a generator keyed by the pixel's coordinates; the way back, sorted pixels
+checked and scattered into a band on the GPU; and two bands compared stripe by stripe, the integer sums of
+every bin's vertical and horizontal stripe formed on the GPU and turned into scores by stripe_scores.
 There is no host fallback: without the library or
 without a device the calls fail."""
 import ctypes as C
+import math
 import os
 from collections import namedtuple
 
@@ -25,6 +27,9 @@ MAX_SAMPLE_TRIALS = 1 << 40  # MODLE_PIXELS_MAX_SAMPLE_TRIALS
 SAMPLE_KEPT, SAMPLE_REST = 0, 1  # MODLE_PIXELS_SAMPLE_KEPT, MODLE_PIXELS_SAMPLE_REST
 BAND_IN, BAND_BEYOND, BAND_OUTSIDE = 0, 1, 2  # MODLE_PIXELS_BAND_IN, _BEYOND, _OUTSIDE
 BAND_TILE_COLS, BAND_TILE_DIAGS = 64, 128  # MODLE_PIXELS_BAND_TILE_COLS, _DIAGS: the tile of a workgroup of the fill
+STRIPES_MOMENTS, STRIPES_MASKED, STRIPES_RANKS = 1, 2, 4  # MODLE_PIXELS_STRIPES_MOMENTS, _MASKED, _RANKS
+MAX_STRIPE = 4096  # MODLE_PIXELS_MAX_STRIPE: the deepest band the rank sums are formed of
+STRIPE_METRICS = ("pearson", "spearman", "rmse", "eucl_dist")  # what stripe_scores forms (evaluate.METRICS)
 DOT_FOLDS = (1.75, 1.75, 1.5, 1.5)  # HiCCUPS' thresholds: donut, lower-left, horizontal, vertical
 EXPORTS = ["modle_pixels_create", "modle_pixels_destroy", "modle_pixels_count", "modle_pixels_extract",
            "modle_pixels_to_host", "modle_pixels_coarse_shape", "modle_pixels_coarsen",
@@ -36,7 +41,8 @@ EXPORTS = ["modle_pixels_create", "modle_pixels_destroy", "modle_pixels_count", 
            "modle_pixels_pileup", "modle_pixels_pileup_to_host",
            "modle_pixels_coarse_pileup_to_host", "modle_pixels_sample_pixels", "modle_pixels_sample",
            "modle_pixels_sample_to_host", "modle_pixels_band_classify", "modle_pixels_band_check",
-           "modle_pixels_band_fill", "modle_pixels_band_from_host"]  # every symbol include/modle_pixels.h declares
+           "modle_pixels_band_fill", "modle_pixels_band_from_host", "modle_pixels_stripes_rows",
+           "modle_pixels_stripes", "modle_pixels_stripes_to_host"]  # every symbol include/modle_pixels.h declares
 
 _LIB = None
 _EXTRACTORS = {}
@@ -145,6 +151,10 @@ def lib():
                                                                                     C.c_uint64, C.c_void_p] + err
         lb.modle_pixels_band_from_host.argtypes = [C.c_void_p] * 4 + [C.c_uint64] * 3 + \
             [C.c_int64, C.c_void_p, C.c_uint64, C.POINTER(_CBandStats), C.c_void_p] + err
+        pair = [C.c_void_p] * 3 + [C.c_uint64] * 3  # handle, d_ref, d_tgt, nrows, ncols, what
+        lb.modle_pixels_stripes_rows.argtypes = [C.c_uint64]
+        lb.modle_pixels_stripes.argtypes = pair + [C.c_void_p, C.c_uint64, C.c_void_p] + err
+        lb.modle_pixels_stripes_to_host.argtypes = pair + [C.POINTER(C.c_void_p), C.c_void_p] + err
         for name in EXPORTS:
             getattr(lb, name)  # raises AttributeError if a declared symbol is not exported
         _LIB = lb
@@ -400,6 +410,91 @@ def sample_pixels(bin1, bin2, count, threshold, seed, salt=0, bin_offset=0):
     del keep
     if rc != 0:
         raise PixelsError(rc, "sample_pixels: invalid argument (threshold <= 2^32, ids in [0, 2^32))")
+    return out
+
+
+def _what(what):
+    """the mask of a stripes call, refused outside uint64 (ctypes would wrap it silently)"""
+    what = int(what)
+    if not 0 <= what < 1 << 64:
+        raise PixelsError(ERR_ARG, f"stripes: the mask {what} is no uint64")
+    return what
+
+
+def stripes_rows(what):
+    """the rows per direction of the mask `what` of STRIPES_MOMENTS (9), STRIPES_MASKED (9) and STRIPES_RANKS (3)
+    (modle_pixels_stripes_rows; no device is needed)"""
+    rc = lib().modle_pixels_stripes_rows(_what(what))
+    if rc < 0:
+        raise PixelsError(rc, "stripes_rows: invalid argument (a non-empty mask of MOMENTS 1, MASKED 2, RANKS 4)")
+    return rc
+
+
+def _pearson(n, sa, sb, saa, sbb, sab):
+    """(n Sab - Sa Sb) / sqrt((n Saa - Sa^2)(n Sbb - Sb^2)) of Python ints, clipped to [-1, 1]; NaN when the
+    product under the root is 0.  Exact up to one division and one root."""
+    num = n * sab - sa * sb
+    den = (n * saa - sa * sa) * (n * sbb - sb * sb)
+    if den == 0:
+        return math.nan
+    # as the root of num^2 / den, the quotient of two ints, which Python rounds correctly: a stripe against
+    # itself (num^2 == den) scores 1.0 exactly, whatever the size of the sums
+    return max(-1.0, min(1.0, math.copysign(math.sqrt(num * num / den), num)))
+
+
+def stripe_scores(rows, metric, masked=False):
+    """The scores of the stripes from the integer sums `rows` of one direction, uint64 [rows(what), ncols]
+    with the blocks of `what` in bit order (Extractor.stripes(...)[direction], or the sums restated on the
+    host): a numpy float64 [ncols].  The one statement of what a score is; every metric is formed in Python
+    integers, exactly, up to one final float / math.sqrt / division:
+        pearson    (n Sab - Sa Sb) / sqrt((n Saa - Sa^2)(n Sbb - Sb^2)), clipped to [-1, 1]; NaN when the
+                   product under the root is 0
+        rmse       sqrt((Saa - 2 Sab + Sbb) / n); NaN when n is 0
+        eucl_dist  sqrt(Saa - 2 Sab + Sbb)
+        spearman   the Pearson formula on (nrows, nrows (nrows + 1), nrows (nrows + 1), Raa, Rbb, Rab), the
+                   sums of the doubled average ranks; 1.0 where Sa == 0 or Sb == 0 (a stripe of zeros), as
+                   evaluate.compare has it
+    `masked`: from the block over the entries where both stripes are non-zero (--exclude-zero-pixels); there
+    is no masked spearman (its weighted ranks are not integers: evaluate.compare has it).  Which blocks
+    `rows` holds follows from its number of rows: 3 RANKS, 18 MOMENTS | MASKED, 21 all three, and of the two
+    masks that 9 and 12 rows leave open the one with MASKED when `masked` is asked for, else the one with
+    MOMENTS.  ValueError when the block a metric needs is missing: pearson and the distances need MOMENTS
+    (`masked`: MASKED), spearman MOMENTS and RANKS.  No sum can leave the doubles: the largest, the product
+    under Pearson's root, is below 2^224."""
+    if metric not in STRIPE_METRICS:
+        raise ValueError(f"stripe_scores: the metric must be one of {STRIPE_METRICS}")
+    rows = np.asarray(rows)
+    if rows.ndim != 2 or rows.dtype != np.uint64 or rows.shape[0] not in (3, 9, 12, 18, 21):
+        raise ValueError(f"stripe_scores: rows of shape {rows.shape} and type {rows.dtype} are no uint64 "
+                         "[rows(what), ncols]")
+    if metric == "spearman" and masked:
+        raise ValueError("stripe_scores: there is no masked spearman (evaluate.compare forms it on the host)")
+    nr = rows.shape[0]
+    side = STRIPES_MASKED if masked else STRIPES_MOMENTS
+    what = {3: STRIPES_RANKS, 9: side, 12: side | STRIPES_RANKS, 18: 3, 21: 7}[nr]
+    need = side | (STRIPES_RANKS if metric == "spearman" else 0)
+    if what & need != need:
+        raise ValueError(f"stripe_scores: {metric}{' (masked)' if masked else ''} needs the blocks {need} of the "
+                         f"mask, the {nr} rows hold {what}")
+    at = 9 if masked and what & STRIPES_MOMENTS else 0
+    mom = [[int(x) for x in rows[at + k]] for k in range(9)]
+    ranks = [[int(x) for x in rows[nr - 3 + k]] for k in range(3)] if metric == "spearman" else None
+    out = np.empty(rows.shape[1], dtype=np.float64)
+    for c in range(rows.shape[1]):
+        n, sa, sb = mom[0][c], mom[1][c], mom[2][c]
+        saa, sbb, sab = (mom[k][c] | (mom[k + 1][c] << 64) for k in (3, 5, 7))
+        if metric == "pearson":
+            out[c] = _pearson(n, sa, sb, saa, sbb, sab)
+        elif metric == "spearman":
+            # (unmasked moments: n is the depth of the band, and the sum of the doubled ranks n (n + 1))
+            out[c] = 1.0 if sa == 0 or sb == 0 else \
+                _pearson(n, n * (n + 1), n * (n + 1), ranks[0][c], ranks[1][c], ranks[2][c])
+        else:
+            ss = saa - 2 * sab + sbb  # the sum of (a - b)^2: never negative
+            if metric == "eucl_dist":
+                out[c] = math.sqrt(ss)
+            else:
+                out[c] = math.sqrt(ss / n) if n else math.nan  # (the quotient of two ints is correctly rounded)
     return out
 
 
@@ -675,6 +770,24 @@ class Extractor:
         del keep
         return out
 
+    def stripes_into(self, d_ref, d_tgt, nrows, ncols, what, d_out, out_words, stream=None):
+        """enqueues the comparison of the bands at `d_ref` and `d_tgt` (one shape; they may be the same) stripe
+        by stripe into the caller-owned device array `d_out` (uint64[2][stripes_rows(what)][ncols], 8-byte
+        aligned, `out_words` == 2 * rows * ncols): per direction (vertical, horizontal) and bin the moments
+        (STRIPES_MOMENTS), the moments over the entries where both are non-zero (STRIPES_MASKED) and the
+        rank sums (STRIPES_RANKS; nrows <= MAX_STRIPE); every word is written (modle_pixels_stripes)"""
+        _call(self._L.modle_pixels_stripes, self._h, d_ref, d_tgt, int(nrows), int(ncols), _what(what), d_out,
+              int(out_words), _stream_ptr(stream))
+
+    def stripes(self, d_ref, d_tgt, nrows, ncols, what=STRIPES_MOMENTS, stream=None):
+        """the sums of stripes_into as a numpy uint64[2, stripes_rows(what), ncols] the caller owns, formed on
+        the device (modle_pixels_stripes_to_host); stripe_scores turns a direction of it into scores"""
+        ptr = C.c_void_p()
+        _call(self._L.modle_pixels_stripes_to_host, self._h, d_ref, d_tgt, int(nrows), int(ncols), _what(what),
+              C.byref(ptr), _stream_ptr(stream))
+        rows = stripes_rows(what)
+        return _host_array(ptr.value, 2 * rows * int(ncols), np.uint64).reshape(2, rows, int(ncols))
+
 
 def extractor(device=0):
     """the process-wide context of `device`"""
@@ -816,3 +929,15 @@ def band_from_host(bin1, bin2, count, nrows, ncols, bin_offset, d_out, out_words
     """The band of host pixels in the device array `d_out`: copied up, checked and scattered on the device;
     returns BandStats."""
     return extractor(device).band_from_host(bin1, bin2, count, nrows, ncols, bin_offset, d_out, out_words, stream)
+
+
+def stripes_into(d_ref, d_tgt, nrows, ncols, what, d_out, out_words, stream=None, device=0):
+    """The sums of the stripes of the bands at device pointers `d_ref` and `d_tgt`, into the device array `d_out`
+    (uint64[2][stripes_rows(what)][ncols]); enqueued on `stream`, nothing crosses to the host."""
+    extractor(device).stripes_into(d_ref, d_tgt, nrows, ncols, what, d_out, out_words, stream)
+
+
+def stripes(d_ref, d_tgt, nrows, ncols, what=STRIPES_MOMENTS, stream=None, device=0):
+    """The sums of the stripes of the bands at device pointers `d_ref` and `d_tgt`: numpy uint64[2,
+    stripes_rows(what), ncols], formed on the device."""
+    return extractor(device).stripes(d_ref, d_tgt, nrows, ncols, what, stream)

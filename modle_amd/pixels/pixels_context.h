@@ -123,6 +123,8 @@ struct modle_pixels_handle {
   GrowBuf<uint64_t, true> band_words;
   GrowBuf<int64_t> band_bin1, band_bin2, band_rows;
   GrowBuf<int32_t> band_count;
+  // modle_pixels_stripes_to_host: two directions of rows(what) rows of ncols words (modle_stripes.hip)
+  GrowBuf<uint64_t, true> stripes;
 };
 
 #endif
