@@ -386,6 +386,14 @@ class BandAnalyses:
                                                    nr * nc + 1, stream)
         return scratch.data_ptr(), nr, nc, scratch
 
+    def contact_sum(self, interval_id, factor=1, first_bin=0):
+        """The sum of the contacts of the interval's band at `factor` times the bin size, counted on the device
+        (pixels.Stats.sum of pixels.count; `first_bin` as for pixels()).  Call it after wait()."""
+        from . import pixels
+
+        d_band, nrows, ncols, _keep = self._band(interval_id, factor, first_bin, None)
+        return pixels.extractor(self.device).count(d_band, nrows, ncols).sum  # (waits: a scratch may go)
+
     def dot_table(self, interval_id, w, p, folds=None, min_diag=2, factor=1, first_bin=0, stream=None):
         """(scale, expected) of the interval for dots(): the table pixels.dot_scales builds from the
         diagonal sums of the marginals pass (float64 [4, nrows]) and the expected count per diagonal,

@@ -37,7 +37,7 @@ import os
 import sys
 import time
 
-from . import api, driver, genome
+from . import api, driver, genome, pixels
 from .params import CS_LOOP, CS_NOISIFY, CS_TAD
 
 STRATEGIES = {  # cli.hpp:63-72
@@ -101,7 +101,10 @@ def resolution_list(text):
     return [genomic_distance(t) for t in items]
 
 
-MAX_INSULATION_WINDOWS, MAX_INSULATION_WINDOW_BINS = 8, 1024  # include/modle_pixels.h
+# the limits and defaults of the library, under the names the front end uses (importing pixels loads nothing)
+MAX_INSULATION_WINDOWS, MAX_INSULATION_WINDOW_BINS = pixels.MAX_WINDOWS, pixels.MAX_WINDOW
+MAX_DOT_WINDOW_BINS, MAX_PILEUP_FLANK_BINS = pixels.MAX_DOT_WINDOW, pixels.MAX_PILEUP_FLANK
+DOT_FOLDS, COMPARE_METRICS = pixels.DOT_FOLDS, pixels.STRIPE_METRICS
 
 
 def window_list(text):
@@ -112,14 +115,6 @@ def window_list(text):
     if len(items) > MAX_INSULATION_WINDOWS:
         raise argparse.ArgumentTypeError(f"{text!r} lists {len(items)} windows: at most {MAX_INSULATION_WINDOWS}")
     return [genomic_distance(t) for t in items]
-
-
-MAX_DOT_WINDOW_BINS = 20  # include/modle_pixels.h
-MAX_PILEUP_FLANK_BINS = 32  # include/modle_pixels.h
-DOT_FOLDS = (1.75, 1.75, 1.5, 1.5)  # HiCCUPS': donut, lower-left, horizontal, vertical
-
-
-COMPARE_METRICS = ("pearson", "spearman", "rmse", "eucl_dist")  # pixels.STRIPE_METRICS, evaluate.METRICS
 
 
 def metric_list(text):
@@ -456,17 +451,17 @@ def output_paths(prefix, mcool=False):
     return prefix + (".mcool" if mcool else ".cool"), prefix + "_lef_1d_occupancy.bw"
 
 
-def state_log_path(prefix):
-    return prefix + "_internal_state.log.gz"  # cli.cpp:871-875
+def _file(a, path_of, wanted=True):
+    """this run's file by the `*_path` function `path_of`, or None: not `wanted`, or --skip-output"""
+    return path_of(a.output_prefix) if wanted and not a.skip_output else None
 
 
-# what preflight settles; a path is None for a file the run does not write, `state_log` is this rank's
-# (`expected` and `coverage` came later: at the end, and None unless asked for)
+# The files without options of their own; a path is None for a file the run does not write, `state_log` is
+# this rank's.  (The first four fields are also made positionally: `expected` and `coverage` default to None.)
 Outputs = collections.namedtuple("Outputs", "cooler bigwig dense state_log expected coverage", defaults=(None, None))
 # what --insulation-windows asks for: the file (None with --skip-output), the bin size of the track, the
 # windows in base pairs as given and the diagonals left out
 Insulation = collections.namedtuple("Insulation", "path resolution windows min_diag")
-# (`insulation` came later: at the end, and None unless asked for)
 # what --dots asks for: the file (None with --skip-output), the bin size, window, peak and cluster radius
 # in base pairs, the smallest count, the four folds and the diagonals no window may reach below
 Dots = collections.namedtuple("Dots", "path resolution window peak min_count folds min_diag radius")
@@ -481,18 +476,19 @@ Subsample = collections.namedtuple("Subsample", "path rest_path frac target seed
 # given, the bin size of the comparison, the metrics in the order given, whether zero pixels are left out,
 # and what preflight read of the reference: its bin size and its chromosomes
 Stripes = collections.namedtuple("Stripes", "path reference resolution metrics exclude_zero ref_bin_size ref_chroms")
-# (`insulation`, `dots` and `pileup` came later: at the end, and None unless asked for; the sampled files
-# and the comparison are not among the fields: subsample_plan and stripes_plan, which preflight calls for
-# their refusals, plan them)
-Preflight = collections.namedtuple("Preflight", "bin_sizes outputs rank world device insulation dots pileup",
-                                   defaults=(None, None, None))
+# The whole plan of a run, which preflight makes once: the bin sizes of the .mcool (None: a .cool), the
+# Outputs, this rank among the ranks and its device, the five records above (None: not asked for) and the
+# diagonals --coverage leaves out.  (The first five fields are also made positionally: the others default.)
+Preflight = collections.namedtuple(
+    "Preflight", "bin_sizes outputs rank world device insulation dots pileup subsample stripes coverage_min_diag",
+    defaults=(None, None, None, None, None, 0))
 
 
 def subsample_options(a, cfg):
-    """The sampled matrix the arguments ask for, as a Subsample without paths, or None.  SystemExit:
-    --subsample-seed or --subsample-split without a depth, both depths (the parser refuses that already),
-    a fraction outside (0, 1] or NaN, a negative target, a seed that is no uint64, --skip-output (both
-    depths need the cooler: its sums set the target, and the sampled file is a cooler)."""
+    """The sampled matrix the arguments ask for, as a Subsample with the files of sampled_paths, or None.
+    SystemExit: --subsample-seed or --subsample-split without a depth, both depths (the parser refuses that
+    already), a fraction outside (0, 1] or NaN, a negative target, a seed that is no uint64, --skip-output
+    (both depths need the cooler: its sums set the target, and the sampled file is a cooler)."""
     frac, target = a.subsample_frac, a.subsample_to
     if frac is None and target is None:
         if a.subsample_seed is not None:
@@ -511,17 +507,8 @@ def subsample_options(a, cfg):
         raise SystemExit(f"--subsample-seed: {seed} is no unsigned 64-bit number")
     if a.skip_output:
         raise SystemExit(f"--subsample-{'frac' if target is None else 'to'} needs the cooler: it excludes --skip-output")
-    return Subsample(None, None, frac, target, seed, bool(a.subsample_split))
-
-
-def subsample_plan(a, cfg):
-    """subsample_options with the paths of the files: `<prefix>_sampled.cool` and `<prefix>_sampled_rest.cool`,
-    .mcool with --mcool-resolutions"""
-    sub = subsample_options(a, cfg)
-    if sub is None:
-        return None
     kept_path, rest_path = sampled_paths(a.output_prefix, mcool=a.mcool_resolutions is not None)
-    return sub._replace(path=kept_path, rest_path=rest_path)
+    return Subsample(kept_path, rest_path, frac, target, seed, bool(a.subsample_split))
 
 
 def _needs(option, given):
@@ -542,7 +529,7 @@ def _analysis_resolution(name, value, cfg):
 
 
 def pileup_options(a, cfg, dots):
-    """The pileups the arguments ask for, as a Pileup without a path, or None.  `dots`: what dots_options
+    """The pileups the arguments ask for, as a Pileup, or None.  `dots`: what dots_options
     returned.  SystemExit: a --pileup-* option without --pileup-at, a resolution that is no multiple of
     -r, a flank or corner that is no positive multiple of the pileup resolution, a flank above 32 bins, a
     corner above the flank, the source `dots` without --dots or at another resolution than the dots'."""
@@ -567,11 +554,11 @@ def pileup_options(a, cfg, dots):
         if int(dots.resolution) != res:
             raise SystemExit(f"--pileup-at dots: the pileup resolution ({res}) is not the dots resolution "
                              f"({int(dots.resolution)})")
-    return Pileup(None, res, flank, corner, list(a.pileup_at))
+    return Pileup(_file(a, pileup_path), res, flank, corner, list(a.pileup_at))
 
 
 def dots_options(a, cfg):
-    """The dot calling the arguments ask for, as a Dots without a path, or None.  SystemExit: a
+    """The dot calling the arguments ask for, as a Dots, or None.  SystemExit: a
     --dots-* option without --dots, a negative number of diagonals, a count below 1, a resolution that is
     no multiple of -r, a window, peak or radius that is no multiple of the dots resolution, a peak that
     is not below the window, a window above 20 bins."""
@@ -601,11 +588,11 @@ def dots_options(a, cfg):
     if window // res > MAX_DOT_WINDOW_BINS:
         raise SystemExit(f"--dots-window: {window} is {window // res} bins of {res}: at most {MAX_DOT_WINDOW_BINS}")
     folds = list(DOT_FOLDS if a.dots_folds is None else a.dots_folds)
-    return Dots(None, res, window, peak, min_count, folds, min_diag, radius)
+    return Dots(_file(a, dots_path), res, window, peak, min_count, folds, min_diag, radius)
 
 
 def stripes_options(a, cfg):
-    """The comparison with a reference cooler the arguments ask for, as a Stripes without a path, or None.
+    """The comparison with a reference cooler the arguments ask for, as a Stripes, or None.
     SystemExit: a --compare-* option without --compare-to, --skip-output (the comparison is a file of the
     output stage, which checks it against the cooler's sums), spearman together with
     --compare-exclude-zero-pixels (its weighted ranks are no integers: `evaluate` has it), a resolution that
@@ -637,17 +624,11 @@ def stripes_options(a, cfg):
     if ref_bin_size != res:
         raise SystemExit(f"--compare-to: {a.compare_to} has a bin size of {ref_bin_size}, the comparison runs at "
                          f"{res} (-r, or --compare-resolution)")
-    return Stripes(None, a.compare_to, res, metrics, exclude_zero, ref_bin_size, ref_chroms)
-
-
-def stripes_plan(a, cfg):
-    """stripes_options with the path of the file, `<prefix>_stripes.tsv`"""
-    plan = stripes_options(a, cfg)
-    return None if plan is None else plan._replace(path=stripes_path(a.output_prefix))
+    return Stripes(_file(a, stripes_path), a.compare_to, res, metrics, exclude_zero, ref_bin_size, ref_chroms)
 
 
 def insulation_options(a, cfg):
-    """The insulation track the arguments ask for, as an Insulation without a path, or None.
+    """The insulation track the arguments ask for, as an Insulation, or None.
     SystemExit: --insulation-resolution or --insulation-ignore-diags without --insulation-windows, a
     negative number of diagonals, a resolution that is no multiple of -r, a window that is no positive
     multiple of the insulation resolution or has more than 1024 bins."""
@@ -666,15 +647,17 @@ def insulation_options(a, cfg):
         if w // res > MAX_INSULATION_WINDOW_BINS:
             raise SystemExit(f"--insulation-windows: {w} is {w // res} bins of {res}: at most "
                              f"{MAX_INSULATION_WINDOW_BINS}")
-    return Insulation(None, res, list(a.insulation_windows), min_diag)
+    return Insulation(_file(a, insulation_path), res, list(a.insulation_windows), min_diag)
 
 
 def preflight(a, cfg):
-    """What the arguments alone settle and refuse, without a genome or a GPU.  SystemExit: a bad
-    --mcool-resolutions list; --coverage-ignore-diags without --coverage, or negative; what
-    insulation_options, dots_options, pileup_options, subsample_options and stripes_options refuse; on rank 0,
-    an output that exists without --force (cooler or .mcool, then bigwig, then .npz, then the expected, the
-    coverage, the insulation, the dots and the pileup file, then the sampled files, then the stripes).  With
+    """The whole plan of the run, a Preflight: what the arguments alone settle and refuse, without a genome or
+    a GPU.  Nothing after it derives an analysis from the arguments again.  SystemExit:
+    --coverage-ignore-diags without --coverage, or negative; what insulation_options, dots_options,
+    pileup_options, subsample_options and stripes_options refuse, in that order (the last opens the reference
+    cooler, the one time it is opened before the launch); a bad --mcool-resolutions list; on rank 0, an output
+    that exists without --force (cooler or .mcool, then bigwig, then .npz, then the expected, the coverage,
+    the insulation, the dots and the pileup file, then the sampled files, then the stripes).  With
     --skip-output no file is planned and none is looked at."""
     if a.coverage_ignore_diags is not None:
         if not a.coverage:
@@ -684,38 +667,32 @@ def preflight(a, cfg):
     ins = insulation_options(a, cfg)
     dots = dots_options(a, cfg)
     pile = pileup_options(a, cfg, dots)
-    sub = subsample_plan(a, cfg)
-    cmp_ = stripes_plan(a, cfg)
+    sub = subsample_options(a, cfg)
+    cmp_ = stripes_options(a, cfg)
     # (a bad list ends the run here, before anything is imported or simulated)
     bin_sizes = None if a.mcool_resolutions is None else mcool_bin_sizes(a.mcool_resolutions, cfg.bin_size)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     device = a.device if a.device is not None else int(os.environ.get("LOCAL_RANK", "0"))
+    analyses = (ins, dots, pile, sub, cmp_, a.coverage_ignore_diags or 0)
     if a.skip_output:
-        return Preflight(bin_sizes, Outputs(None, None, None, None), rank, world, device, ins, dots, pile)
+        return Preflight(bin_sizes, Outputs(None, None, None, None), rank, world, device, *analyses)
     cool_path, bw_path = output_paths(a.output_prefix, mcool=bin_sizes is not None)
-    log_path = state_log_path(a.output_prefix) if world == 1 else \
-        f"{a.output_prefix}_internal_state.rank{rank}.log.gz"
-    outputs = Outputs(cool_path, bw_path if cfg.track_1d_lef_position else None,
-                      dense_path(a.output_prefix) if a.dense_region else None,
-                      log_path if a.log_model_internal_state else None,
-                      expected_path(a.output_prefix) if a.expected else None,
-                      coverage_path(a.output_prefix) if a.coverage else None)
-    if ins is not None:
-        ins = ins._replace(path=insulation_path(a.output_prefix))
-    if dots is not None:
-        dots = dots._replace(path=dots_path(a.output_prefix))
-    if pile is not None:
-        pile = pile._replace(path=pileup_path(a.output_prefix))
+    # (cli.cpp:871-875; with several ranks every rank writes its own)
+    log_path = a.output_prefix + ("_internal_state.log.gz" if world == 1 else f"_internal_state.rank{rank}.log.gz")
+    outputs = Outputs(cool_path, bw_path if cfg.track_1d_lef_position else None, _file(a, dense_path, a.dense_region),
+                      log_path if a.log_model_internal_state else None, _file(a, expected_path, a.expected),
+                      _file(a, coverage_path, a.coverage))
     if rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(cool_path)), exist_ok=True)
-        for p in (outputs.cooler, outputs.bigwig, outputs.dense, outputs.expected, outputs.coverage,
-                  None if ins is None else ins.path, None if dots is None else dots.path,
-                  None if pile is None else pile.path, None if sub is None else sub.path,
-                  None if sub is None or not sub.split else sub.rest_path, None if cmp_ is None else cmp_.path):
+        planned = [outputs.cooler, outputs.bigwig, outputs.dense, outputs.expected, outputs.coverage]
+        planned += [r.path for r in (ins, dots, pile, sub) if r is not None]
+        planned += [sub.rest_path] if sub is not None and sub.split else []
+        planned += [cmp_.path] if cmp_ is not None else []
+        for p in planned:
             if p and os.path.exists(p) and not a.force:
                 raise SystemExit(f"refusing to overwrite {p}: pass --force to overwrite")
-    return Preflight(bin_sizes, outputs, rank, world, device, ins, dots, pile)
+    return Preflight(bin_sizes, outputs, rank, world, device, *analyses)
 
 
 def plan_run(a, cfg, pre, log):
@@ -759,7 +736,7 @@ def check_plan(a, cfg, pre, plan, chroms):
             raise SystemExit(f"--pileup-flank: the flank of {bad[2]} ({bad[3]} bins of {pre.pileup.resolution}) does "
                              f"not fit the band of {bad[1]} ({bad[4]} diagonals): the largest flank that fits is "
                              f"{bad[5]} ({bad[5] // pre.pileup.resolution} bins)")
-    cmp_ = stripes_plan(a, cfg)
+    cmp_ = pre.stripes
     if cmp_ is not None:
         bad = driver.stripes_misfit(plan, int(cfg.bin_size), cmp_.resolution, cmp_.metrics, cmp_.ref_bin_size,
                                     cmp_.ref_chroms, chroms)
@@ -811,8 +788,16 @@ def run_plan(sim, a, cfg, plan, pre, log):
     return ids, tensors
 
 
+def output_stage(sim, a, cfg, plan, ids, tensors, pre, regions, chroms, log, generated_by, backend="nccl"):
+    """driver.write_outputs for the plan `pre`, with the attributes every cooler of the run carries: the
+    arguments that were given as the metadata, --assembly-name, --force and the chromosomes of the genome"""
+    meta = json.dumps({k: v for k, v in vars(a).items() if v is not None and k != "command"}, sort_keys=True)
+    return driver.write_outputs(sim, cfg, plan, ids, tensors, pre, regions, log, backend, assembly=a.assembly_name,
+                                generated_by=generated_by, metadata_json=meta, force_overwrite=a.force, chroms=chroms)
+
+
 def simulate(a, log=print):
-    """preflight (arguments only) -> plan_run -> open_simulator -> run_plan -> driver.write_outputs,
+    """preflight (arguments only) -> plan_run -> open_simulator -> run_plan -> output_stage,
     and the bigwig once the simulator is closed"""
     cfg = config_from_args(a)
     pre = preflight(a, cfg)
@@ -823,15 +808,8 @@ def simulate(a, log=print):
         ids, tensors = run_plan(sim, a, cfg, plan, pre, log)
         # The contact matrices stay on the device: the cooler is written from their non-zero
         # pixels, extracted there (libmodle_pixels.so), and the warning uses the extraction's sum.
-        meta = json.dumps({k: v for k, v in vars(a).items() if v is not None and k != "command"},
-                          sort_keys=True)
-        occupancies = driver.write_outputs(
-            sim, cfg, plan, ids, tensors, pre.outputs, pre.bin_sizes, regions, pre.rank, log, a.dist_backend,
-            coverage_min_diag=a.coverage_ignore_diags or 0, insulation=pre.insulation, dots=pre.dots, pileup=pre.pileup,
-            subsample=subsample_plan(a, cfg), stripes=stripes_plan(a, cfg),
-            assembly=a.assembly_name,
-            generated_by="modle_amd (MI355X)", metadata_json=meta,
-            force_overwrite=a.force, chroms=chroms)
+        occupancies = output_stage(sim, a, cfg, plan, ids, tensors, pre, regions, chroms, log, "modle_amd (MI355X)",
+                                   a.dist_backend)
     finally:
         sim.close()
     if pre.rank == 0 and pre.outputs.bigwig is not None:
@@ -902,7 +880,7 @@ def load_bands(bands, reader, plan, log):
 
 def analyze(a, log=print):
     """The analyses of simulate on a file: refusals (arguments, file, outputs) -> the plan -> the bands on the
-    device (api.LoadedBands) -> check_plan -> driver.write_outputs, which writes what it writes for simulate"""
+    device (api.LoadedBands) -> check_plan -> output_stage, which writes what it writes for simulate"""
     from . import cooler
 
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -936,13 +914,7 @@ def analyze(a, log=print):
         try:
             ids = load_bands(bands, reader, plan, log)
             regions = check_plan(a, cfg, pre, plan, reader.chroms)
-            meta = json.dumps({k: v for k, v in vars(a).items() if v is not None and k != "command"}, sort_keys=True)
-            driver.write_outputs(
-                bands, cfg, plan, ids, None, pre.outputs, pre.bin_sizes, regions, 0, log,
-                coverage_min_diag=a.coverage_ignore_diags or 0, insulation=pre.insulation, dots=pre.dots,
-                pileup=pre.pileup, subsample=subsample_plan(a, cfg), stripes=stripes_plan(a, cfg), assembly=a.assembly_name,
-                generated_by="modle_amd analyze (MI355X)", metadata_json=meta, force_overwrite=a.force,
-                chroms=reader.chroms)
+            output_stage(bands, a, cfg, plan, ids, None, pre, regions, reader.chroms, log, "modle_amd analyze (MI355X)")
         finally:
             bands.close()
     log(f"done in {time.time() - t0:.1f} s")

@@ -449,6 +449,15 @@ def interval_name(iv):
     return f"{iv['name']}:{iv['start']}-{iv['end']}"
 
 
+def bin_span(iv, base, factor, c):
+    """[lo, hi) in base pairs of bin `c` of the interval's band at `factor` times the bin size `base`.  Fine bins
+    count from the interval's start and coarse bins are anchored at the chromosome's, so the first and the last
+    bin are clipped to the interval."""
+    start, base, k = int(iv["start"]), int(base), int(factor)
+    p = (start // base) % k
+    return start + max(0, c * k - p) * base, min(int(iv["end"]), start + ((c + 1) * k - p) * base)
+
+
 def check_marginals(name, total, diag_sum, coverage, min_diag=0):
     """What ties the marginals of a band (api.Simulator.marginals) to the sum of its pixels, `total`
     (pixels.Stats.sum), in exact integers: the diagonals add up to the total, and the coverage counts
@@ -475,10 +484,9 @@ def expected_lines(iv, bin_size, diag_sum, n_valid):
 
 def coverage_lines(iv, bin_size, coverage):
     """the lines of <prefix>_coverage.bedgraph for one interval: chrom, start, end, value per bin;
-    bin i starts i bins after the interval's start and the last one ends with the interval"""
-    start, end, b = int(iv["start"]), int(iv["end"]), int(bin_size)
-    return [f"{iv['name']}\t{start + i * b}\t{min(start + (i + 1) * b, end)}\t{int(c)}\n"
-            for i, c in enumerate(coverage)]
+    bin i starts i bins after the interval's start and the last one ends with the interval (bin_span)"""
+    spans = (bin_span(iv, bin_size, 1, i) for i in range(len(coverage)))
+    return [f"{iv['name']}\t{lo}\t{hi}\t{int(c)}\n" for (lo, hi), c in zip(spans, coverage)]
 
 
 def write_expected(path, plan, base, bin_sizes, marginals):
@@ -585,13 +593,10 @@ def insulation_header(windows):
 def insulation_lines(iv, base, factor, ins_sum, n_valid, score):
     """the rows of <prefix>_insulation.tsv for one interval, one per bin of `factor` * `base` base pairs:
     chrom, start, end, then per window (the rows of the three arrays) the sum, the number of pixels and
-    the repr of the score.  Fine bins count from the interval's start and coarse bins are anchored at the
-    chromosome's, so the first and the last bin are clipped to the interval."""
-    start, end, base, k = int(iv["start"]), int(iv["end"]), int(base), int(factor)
-    p = (start // base) % k
+    the repr of the score.  The bins are bin_span's."""
     out = []
     for c in range(len(ins_sum[0]) if len(ins_sum) else 0):
-        lo, hi = start + max(0, c * k - p) * base, min(end, start + ((c + 1) * k - p) * base)
+        lo, hi = bin_span(iv, base, factor, c)
         out.append(f"{iv['name']}\t{lo}\t{hi}" + "".join(
             f"\t{int(s[c])}\t{int(n[c])}\t{float(x[c])!r}" for s, n, x in zip(ins_sum, n_valid, score)) + "\n")
     return out
@@ -662,18 +667,10 @@ def dots_header():
 def dots_lines(iv, base, factor, bin1, bin2, count, expected):
     """the rows of <prefix>_dots.bedpe for one interval, one per dot, in the order given: chrom, start
     and end of bin1, the same of bin2, the count, the repr of the expected count at that distance and
-    the repr of their quotient.  The bins are of `factor` * `base` base pairs: fine bins count from the
-    interval's start and coarse bins are anchored at the chromosome's, so the first and the last bin are
-    clipped to the interval (like insulation_lines)."""
-    start, end, base, k = int(iv["start"]), int(iv["end"]), int(base), int(factor)
-    p = (start // base) % k
-
-    def span(c):
-        return start + max(0, c * k - p) * base, min(end, start + ((c + 1) * k - p) * base)
-
+    the repr of their quotient.  The bins are of `factor` * `base` base pairs, with bin_span's ends."""
     out = []
     for b1, b2, c, e in zip(map(int, bin1), map(int, bin2), map(int, count), map(float, expected)):
-        (lo1, hi1), (lo2, hi2) = span(b1), span(b2)
+        (lo1, hi1), (lo2, hi2) = bin_span(iv, base, factor, b1), bin_span(iv, base, factor, b2)
         ratio = c / e if e > 0 else float("inf")
         out.append(f"{iv['name']}\t{lo1}\t{hi1}\t{iv['name']}\t{lo2}\t{hi2}\t{c}\t{e!r}\t{ratio!r}\n")
     return out
@@ -968,14 +965,12 @@ def stripes_header(reference, resolution, exclude_zero, metrics):
 
 def stripes_lines(iv, base, factor, scores):
     """the rows of <prefix>_stripes.tsv for one interval, one per bin of `factor` * `base` base pairs: chrom,
-    start, end (clipped to the interval like insulation_lines), then per metric the repr of the score of
+    start, end (bin_span's), then per metric the repr of the score of
     the vertical and of the horizontal stripe, NaN as `nan`.  `scores`: per metric the (vertical, horizontal)
     pair of api.BandAnalyses.stripe_scores, in the order of the columns."""
-    start, end, base, k = int(iv["start"]), int(iv["end"]), int(base), int(factor)
-    p = (start // base) % k
     out = []
     for c in range(len(scores[0][0]) if scores else 0):
-        lo, hi = start + max(0, c * k - p) * base, min(end, start + ((c + 1) * k - p) * base)
+        lo, hi = bin_span(iv, base, factor, c)
         out.append(f"{iv['name']}\t{lo}\t{hi}" + "".join(f"\t{float(v[c])!r}\t{float(h[c])!r}" for v, h in scores)
                    + "\n")
     return out
@@ -1014,12 +1009,7 @@ def _interval_stripes(sim, plan, ids, reader, metrics, exclude_zero, sums, k, fa
                                                                                             factor)[0])
         del bin1, bin2, count
         rows = sim.stripe_moments(ids[k], ref, rid, stripes_what(metrics, exclude_zero), factor, first_bin)
-        if factor == 1 and k in sums:
-            run_sum = sums[k]
-        else:
-            d_band, nrows, ncols, keep = sim._band(ids[k], factor, first_bin, None)
-            run_sum = pixels.extractor(sim.device).count(d_band, nrows, ncols).sum  # (waits)
-            del keep
+        run_sum = sums[k] if factor == 1 and k in sums else sim.contact_sum(ids[k], factor, first_bin)
         check_stripes(interval_name(iv), rows, nr, st.sum_in, run_sum)
     finally:
         ref.close()
@@ -1080,35 +1070,15 @@ def reduce_missed(missed, backend, rank, device=None):
     return [int(m) for m in t.tolist()]
 
 
-def write_outputs(sim, cfg, plan, ids, tensors, outputs, bin_sizes=None, regions=(), rank=0, log=print,
-                  backend="nccl", coverage_min_diag=0, insulation=None, dots=None, pileup=None, subsample=None,
-                  stripes=None, **attrs):
-    """What a finished launch writes while the simulator is open: the state log (every rank its
-    own), then on rank 0 the cooler or .mcool with the missing-interactions warnings, the dense
-    `regions` (of dense_regions), the distance-decay curves (at every bin size of the file) and the
-    coverage without the diagonals below `coverage_min_diag`, and the insulation track `insulation` (a
-    cli.Insulation: path, resolution, windows in base pairs, min_diag; None or without a path: not
-    written), and the dots `dots` (a cli.Dots; None or without a path: not written),
-    and the pileups `pileup` (a cli.Pileup; likewise; its source `dots` piles the dots just written),
-    and the sampled matrix `subsample` (a cli.Subsample; likewise): the same file as the cooler from the kept
-    half of a binomial thinning of every interval (sample_matrices), and with its `split` the other half,
-    and the comparison `stripes` (a cli.Stripes; likewise): the scores of every bin's stripes against the
-    reference cooler it names (write_stripes).  `outputs.state_log`, `.cooler`, `.dense`,
-    `.expected`, `.coverage`: the paths, None for a file that is not written; without a cooler
-    (--skip-output) the matrices are only summed, for the warnings.  `tensors`: with several ranks the (contacts, occupancy) torch tensors per plan entry;
-    they are reduced in place onto rank 0 (reduce_to_rank0 with `backend`), which extracts from the
-    reduced tensor without a host copy; the missed-update counts are summed over the ranks as well, so
-    that the warnings weigh the whole job's missed updates against the whole job's matrix.
-    `attrs`: write_pixels' keywords.  Returns the occupancies per plan entry, for write_bigwig."""
-    from . import pixels
-
+def collect_outputs(sim, plan, ids, tensors, outputs, rank, log, backend):
+    """What every rank does after a launch: its state log `outputs.state_log`, then per registered interval
+    the occupancy and the missed-update count, and with several ranks (`tensors`) the reduces onto rank 0
+    (reduce_to_rank0 with `backend`: contacts, then occupancy, per interval; then reduce_missed).  Every rank
+    issues the same collectives in the same order; an entry that is skipped costs none.  Returns (the
+    occupancies per plan entry, the missed updates per plan entry: on rank 0 the whole job's)."""
     if outputs.state_log is not None:
         write_state_log(outputs.state_log, sim, plan, ids)
         log(f"written {outputs.state_log}")
-    if tensors is not None:
-        import torch
-
-        dev = torch.device("cuda", sim.device)
     occupancies, missed = [], []
     for k, iid in enumerate(ids):
         if iid is None:
@@ -1124,77 +1094,125 @@ def write_outputs(sim, cfg, plan, ids, tensors, outputs, bin_sizes=None, regions
         occupancies.append(occ)
         missed.append(n_missed)
     if tensors is not None:
-        # (every rank issues the same collectives in the same order: two per registered interval,
-        # then this one; an entry that is skipped costs none)
+        import torch
+
+        dev = torch.device("cuda", sim.device)
         missed = reduce_missed(missed, backend, rank, dev)
         torch.cuda.synchronize(dev)
-    if rank != 0:
-        return occupancies
-    if outputs.cooler is None:
-        for k, iid in enumerate(ids):
-            if iid is not None:
-                d_contacts, _, nrows, ncols = sim.outputs(iid)
-                stats = pixels.extractor(sim.device).count(d_contacts, nrows, ncols)
-                warn_missing(plan[k]["interval"]["name"], stats.sum, missed[k], log)
-        return occupancies
+    return occupancies, missed
+
+
+def warn_without_files(sim, plan, ids, missed, log):
+    """--skip-output: the matrices are only summed where they lie, for the missing-interactions warnings"""
+    from . import pixels
+
+    for k, iid in enumerate(ids):
+        if iid is not None:
+            d_contacts, _, nrows, ncols = sim.outputs(iid)
+            stats = pixels.extractor(sim.device).count(d_contacts, nrows, ncols)
+            warn_missing(plan[k]["interval"]["name"], stats.sum, missed[k], log)
+
+
+def insulation_file(sim, cfg, plan, ids, sums, marginals, log, insulation):
+    """<prefix>_insulation.tsv of the cli.Insulation `insulation`"""
+    bins = [int(w) // int(insulation.resolution) for w in insulation.windows]
+    write_insulation(insulation.path, plan, int(cfg.bin_size), insulation.resolution, insulation.windows,
+                     functools.partial(_interval_insulation, sim, plan, ids, bins, int(insulation.min_diag), marginals))
+    log(f"written {insulation.path}")
+
+
+def dots_file(sim, cfg, plan, ids, sums, marginals, log, dots):
+    """<prefix>_dots.bedpe of the cli.Dots `dots`; returns write_dots' callback, which keeps the dots per entry:
+    a pileup at the dots reads them again"""
+    res = int(dots.resolution)
+    interval_dots = functools.lru_cache(maxsize=None)(
+        functools.partial(_interval_dots, sim, plan, ids, int(dots.window) // res, int(dots.peak) // res,
+                          int(dots.min_count), list(dots.folds), int(dots.min_diag), int(dots.radius) // res))
+    write_dots(dots.path, plan, int(cfg.bin_size), res, interval_dots)
+    log(f"written {dots.path}")
+    return interval_dots
+
+
+def pileup_file(sim, cfg, plan, ids, sums, marginals, log, pileup, interval_dots):
+    """<prefix>_pileup.tsv of the cli.Pileup `pileup`; its source `dots` piles the dots just written
+    (`interval_dots`: what dots_file returned)"""
+    base, res = int(cfg.bin_size), int(pileup.resolution)
+    placed, unplaced = {}, {}
+    for what in pileup.sources:
+        if what not in ("dots", "barriers") and what not in placed:
+            placed[what], trans, outside = place_pairs(plan, base, res, read_bedpe(what))
+            unplaced[what] = trans + outside
+            if trans + outside:
+                log(f"--pileup-at {what}: {trans + outside} pairs are not placed ({trans} between two "
+                    f"chromosomes, {outside} in no simulated interval)")
+    write_pileup(pileup.path, plan, base, res, pileup.flank, pileup.corner, pileup.sources,
+                 functools.partial(_interval_anchors, plan, ids, base, res, interval_dots, placed),
+                 functools.partial(_interval_pileup, sim, plan, ids, marginals, {}, int(pileup.flank) // res),
+                 unplaced)
+    log(f"written {pileup.path}")
+
+
+def stripes_file(sim, cfg, plan, ids, sums, marginals, log, stripes):
+    """<prefix>_stripes.tsv of the cli.Stripes `stripes`: the reference cooler is opened here, the one time after
+    the launch, for its pixels"""
+    from . import cooler
+
+    with cooler.CoolerReader(stripes.reference) as reader:
+        write_stripes(stripes.path, plan, int(cfg.bin_size), stripes.reference, stripes.resolution,
+                      stripes.exclude_zero, stripes.metrics,
+                      functools.partial(_interval_stripes, sim, plan, ids, reader, list(stripes.metrics),
+                                        bool(stripes.exclude_zero), sums))
+    log(f"written {stripes.path}")
+
+
+def write_files(sim, cfg, plan, ids, missed, pre, regions, log, **attrs):
+    """Rank 0's files of the plan `pre`, in this order: the cooler or .mcool with the missing-interactions
+    warnings (`missed`: of collect_outputs), the sampled matrices (sample_matrices), the dense `regions`, the
+    distance-decay curves at every bin size of the file, the coverage without the diagonals below
+    `pre.coverage_min_diag`, then insulation_file, dots_file, pileup_file and stripes_file.  All of them read
+    the matrices where they lie (with several ranks: the reduced tensors), after the cooler's INT32 range check
+    has passed.  `attrs`: write_pixels' keywords."""
+    outputs, bin_sizes = pre.outputs, pre.bin_sizes
     sums = {}  # the sum of the pixels per plan entry, at the base bin size
     write_pixels(outputs.cooler, cfg, plan,
                  functools.partial(_interval_pixels, sim, plan, ids, missed, log, sums=sums), bin_sizes, **attrs)
     log(f"written {outputs.cooler}")
-    if subsample is not None and subsample.path is not None:
-        sample_matrices(sim, cfg, plan, ids, sum(sums.values()), subsample, bin_sizes, log, **attrs)
+    if pre.subsample is not None:
+        sample_matrices(sim, cfg, plan, ids, sum(sums.values()), pre.subsample, bin_sizes, log, **attrs)
     if outputs.dense is not None:
-        # (the cooler's INT32 range check has passed: the uint32 words are int32 counts; with
-        # several ranks the region is unpacked from the reduced tensor, like the pixels)
+        # (the uint32 words are int32 counts: the range check)
         np.savez(outputs.dense, **{key: sim.dense(ids[k], lo, hi).view(np.int32) for k, lo, hi, key in regions})
         log(f"written {outputs.dense}")
-    # (likewise after the range check, and with several ranks from the reduced tensor)
-    marginals = functools.partial(_interval_marginals, sim, plan, ids, sums, int(coverage_min_diag), {})
+    marginals = functools.partial(_interval_marginals, sim, plan, ids, sums, int(pre.coverage_min_diag), {})
     if outputs.expected is not None:
         write_expected(outputs.expected, plan, int(cfg.bin_size), bin_sizes, marginals)
         log(f"written {outputs.expected}")
     if outputs.coverage is not None:
         write_coverage(outputs.coverage, plan, int(cfg.bin_size), marginals)
         log(f"written {outputs.coverage}")
-    if insulation is not None and insulation.path is not None:
-        bins = [int(w) // int(insulation.resolution) for w in insulation.windows]
-        write_insulation(insulation.path, plan, int(cfg.bin_size), insulation.resolution, insulation.windows,
-                         functools.partial(_interval_insulation, sim, plan, ids, bins, int(insulation.min_diag),
-                                           marginals))
-        log(f"written {insulation.path}")
-    interval_dots = None
-    if dots is not None and dots.path is not None:
-        res = int(dots.resolution)
-        # (kept per entry: a pileup at the dots reads them again)
-        interval_dots = functools.lru_cache(maxsize=None)(
-            functools.partial(_interval_dots, sim, plan, ids, int(dots.window) // res, int(dots.peak) // res,
-                              int(dots.min_count), list(dots.folds), int(dots.min_diag), int(dots.radius) // res))
-        write_dots(dots.path, plan, int(cfg.bin_size), res, interval_dots)
-        log(f"written {dots.path}")
-    if pileup is not None and pileup.path is not None:
-        base, res = int(cfg.bin_size), int(pileup.resolution)
-        placed, unplaced = {}, {}
-        for what in pileup.sources:
-            if what not in ("dots", "barriers") and what not in placed:
-                placed[what], trans, outside = place_pairs(plan, base, res, read_bedpe(what))
-                unplaced[what] = trans + outside
-                if trans + outside:
-                    log(f"--pileup-at {what}: {trans + outside} pairs are not placed ({trans} between two "
-                        f"chromosomes, {outside} in no simulated interval)")
-        write_pileup(pileup.path, plan, base, res, pileup.flank, pileup.corner, pileup.sources,
-                     functools.partial(_interval_anchors, plan, ids, base, res, interval_dots, placed),
-                     functools.partial(_interval_pileup, sim, plan, ids, marginals, {}, int(pileup.flank) // res),
-                     unplaced)
-        log(f"written {pileup.path}")
-    if stripes is not None and stripes.path is not None:
-        from . import cooler
+    shared = (sim, cfg, plan, ids, sums, marginals, log)
+    if pre.insulation is not None:
+        insulation_file(*shared, pre.insulation)
+    interval_dots = dots_file(*shared, pre.dots) if pre.dots is not None else None
+    if pre.pileup is not None:
+        pileup_file(*shared, pre.pileup, interval_dots)
+    if pre.stripes is not None:
+        stripes_file(*shared, pre.stripes)
 
-        with cooler.CoolerReader(stripes.reference) as reader:
-            write_stripes(stripes.path, plan, int(cfg.bin_size), stripes.reference, stripes.resolution,
-                          stripes.exclude_zero, stripes.metrics,
-                          functools.partial(_interval_stripes, sim, plan, ids, reader, list(stripes.metrics),
-                                            bool(stripes.exclude_zero), sums))
-        log(f"written {stripes.path}")
+
+def write_outputs(sim, cfg, plan, ids, tensors, pre, regions=(), log=print, backend="nccl", **attrs):
+    """The output stage of a finished launch, while the simulator is open, for the plan `pre` (a
+    cli.Preflight): collect_outputs on every rank; then on rank 0 write_files, or without a cooler
+    (--skip-output, under which no record of `pre` has a path) warn_without_files.  `tensors`: with several
+    ranks the (contacts, occupancy) torch tensors per plan entry, which are reduced in place onto rank 0;
+    the missed-update counts are summed over the ranks as well, so that the warnings weigh the whole job's
+    missed updates against the whole job's matrix.  `regions`: of dense_regions.  `attrs`: write_pixels'
+    keywords.  Returns the occupancies per plan entry, for write_bigwig."""
+    occupancies, missed = collect_outputs(sim, plan, ids, tensors, pre.outputs, pre.rank, log, backend)
+    if pre.rank == 0 and pre.outputs.cooler is not None:
+        write_files(sim, cfg, plan, ids, missed, pre, regions, log, **attrs)
+    elif pre.rank == 0:
+        warn_without_files(sim, plan, ids, missed, log)
     return occupancies
 
 

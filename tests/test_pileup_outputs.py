@@ -417,7 +417,7 @@ def test_the_options_parse_and_preflight_plans_the_file(prefix):
     assert pre.outputs == cli.Outputs(prefix + ".cool", None, None, None)  # as before
     assert cli.Preflight([5000], pre.outputs, 0, 1, 0).pileup is None  # the fields of before still make one
     assert cli.Preflight([5000], pre.outputs, 0, 1, 0, None, None).pileup is None
-    assert cli.Preflight._fields[-1] == "pileup"
+    assert cli.Preflight._fields[:8] == ("bin_sizes", "outputs", "rank", "world", "device", "insulation", "dots", "pileup")
     pre = run_preflight(prefix, "--pileup-at", "barriers")
     assert pre.pileup == cli.Pileup(prefix + "_pileup.tsv", 5000, 50_000, 15_000, ["barriers"])
     assert cli.pileup_path(prefix) == prefix + "_pileup.tsv"

@@ -193,20 +193,19 @@ def test_the_options_parse_and_the_files_are_planned(prefix):
 
     a, cfg = parse(prefix)
     before = cli.preflight(a, cfg)
-    assert cli.subsample_plan(a, cfg) is None
+    assert before.subsample is None
     a, cfg = parse(prefix, "--subsample-frac", "0.25", "--seed", "77")
-    assert cli.preflight(a, cfg) == before  # what preflight returns does not change
-    assert cli.subsample_plan(a, cfg) == cli.Subsample(prefix + "_sampled.cool", prefix + "_sampled_rest.cool", 0.25, None,
-                                                       77, False)
+    assert cli.preflight(a, cfg)._replace(subsample=None) == before  # that field changes and nothing else
+    assert cli.preflight(a, cfg).subsample == cli.Subsample(prefix + "_sampled.cool", prefix + "_sampled_rest.cool", 0.25,
+                                                            None, 77, False)
     a, cfg = parse(prefix, "--subsample-to", "1000000", "--subsample-seed", str(2**64 - 1), "--subsample-split",
                    "--mcool-resolutions", "10kb,50kb")
-    cli.preflight(a, cfg)
-    assert cli.subsample_plan(a, cfg) == cli.Subsample(prefix + "_sampled.mcool", prefix + "_sampled_rest.mcool", None,
-                                                       1_000_000, 2**64 - 1, True)
+    assert cli.preflight(a, cfg).subsample == cli.Subsample(prefix + "_sampled.mcool", prefix + "_sampled_rest.mcool", None,
+                                                            1_000_000, 2**64 - 1, True)
     assert cli.sampled_paths("x/y") == ("x/y_sampled.cool", "x/y_sampled_rest.cool")
     assert cli.sampled_paths("x/y", mcool=True) == ("x/y_sampled.mcool", "x/y_sampled_rest.mcool")
-    assert cli.subsample_plan(*parse(prefix, "--subsample-frac", "1")).frac == 1.0
-    assert cli.subsample_plan(*parse(prefix, "--subsample-to", "0")).target == 0
+    assert cli.preflight(*parse(prefix, "--subsample-frac", "1")).subsample.frac == 1.0
+    assert cli.preflight(*parse(prefix, "--subsample-to", "0")).subsample.target == 0
 
 
 SUBSAMPLE_REFUSED = [

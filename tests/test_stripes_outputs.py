@@ -430,11 +430,11 @@ def run_preflight(prefix, *extra):
 
 
 def run_plan(prefix, *extra):
-    """what the output stage is handed: cli.stripes_plan, after preflight has accepted the arguments"""
+    """what the output stage is handed: the `stripes` of the plan, after preflight has accepted the arguments"""
     a = parse(prefix, *extra)
-    cfg = cli.config_from_args(a)
-    assert cli.preflight(a, cfg).outputs.cooler == prefix + ".cool"
-    return cli.stripes_plan(a, cfg)
+    pre = cli.preflight(a, cli.config_from_args(a))
+    assert pre.outputs.cooler == prefix + ".cool"
+    return pre.stripes
 
 
 def test_the_options_parse_and_preflight_plans_the_file(prefix, refs):
