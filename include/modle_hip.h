@@ -348,6 +348,27 @@ int modle_hip_test_phases(modle_hip_handle* h, uint32_t phase_mask, uint64_t sta
  *                     Philox4x32-10 as two 64-bit values, then two zeros -- the round function of the
  *                     PHILOX generator policy, for the Random123 known-answer vectors */
 #define MODLE_HIP_UNIT_PHILOX 6u
+/*   DRAWS             the distributions of the path on their own, drawn by one wave in sequence with the
+ *                     device's `*_exact` routines from a generator seeded like modle_hip_prng_seed(seed).
+ *                     in (n >= 3 pairs) = kind, seed, p0, p1, p2, m; the rest is not read.  out[0] = engine
+ *                     outputs consumed, out[1 .. m] = the m draws (m + 1 <= 2 n), doubles as bit images;
+ *                     what follows stays zero.  Kinds and their parameters (doubles as bit images):
+ *                       1 canonical    -                    5 poisson      p0 = mean
+ *                       2 bernoulli    p0 = p               6 binomial     p0 = t (int64), p1 = p
+ *                       3 uniform_int  p0 = lo, p1 = hi     7 genextreme   p0 = mu, p1 = sigma, p2 = xi
+ *                       4 normal       p0 = mean, p1 = sigma
+ *   DRAW_FORMS        the pure forms of the same file, one element per lane.  in = the head pair (form, 0),
+ *                     then two pairs (a, b, c, d) per element; out = (0, 0), then four words per element:
+ *                       1 canonical_raw(raw = a)                      -> bit image
+ *                       2 bernoulli_raw(raw = a, p = b)               -> 0 / 1
+ *                       3 uniform_int_bucket(range = a), and raw = b divided by that bucket with
+ *                         udiv_by_uniform(raw, bucket, 1.0 / bucket)  -> bucket, quotient (range 2^64 - 1: zeros)
+ *                       4 genextreme_from_canonical(u = a, mu = b, sigma = c, xi = d) -> bit image
+ *                       5 binom_fc(k = a)                             -> bit image
+ *                       6 udiv_by_uniform(raw = a, d = b, 1.0 / d)    -> quotient (d = 0: zero)
+ *                     the words of an element that a form does not name are zero */
+#define MODLE_HIP_UNIT_DRAWS 7u
+#define MODLE_HIP_UNIT_DRAW_FORMS 8u
 int modle_hip_test_units(modle_hip_handle* h, uint32_t what, const uint64_t* in, size_t n,
                          uint64_t nrows, uint64_t ncols, uint32_t* contacts,
                          uint64_t* missed_updates, uint64_t* out, char* err, size_t errlen);

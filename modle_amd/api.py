@@ -787,11 +787,15 @@ class Simulator(BandAnalyses):
             contacts, nrows, ncols, C.byref(missed), occ.ctypes.data, res, err, len(err)), err)
         return contacts, missed.value, occ, res
 
-    def test_units(self, what, pairs, nrows=0, ncols=0, contacts=None, missed=0):
-        """Unit-level entry point (modle_hip_test_units); returns (out words, contacts, missed)."""
+    def test_units(self, what, pairs, nrows=0, ncols=0, contacts=None, missed=0, out=None):
+        """Unit-level entry point (modle_hip_test_units); returns (out words, contacts, missed).
+        `out`: a contiguous uint64 array of 2 n words of the caller's (a window of a larger, guarded one)."""
         pairs = np.ascontiguousarray(pairs, dtype=np.uint64).reshape(-1)
         n = len(pairs) // 2
-        out = np.zeros(2 * n, dtype=np.uint64)
+        if out is None:
+            out = np.zeros(2 * n, dtype=np.uint64)
+        if out.dtype != np.uint64 or out.shape != (2 * n,) or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous uint64 array of 2 n words")
         m = C.c_uint64(missed)
         err = _errbuf()
         _check(self._L.modle_hip_test_units(

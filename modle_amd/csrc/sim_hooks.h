@@ -181,7 +181,13 @@ MODLE_DEV u32 run_test_phases(const Params& p, const Interval& iv, const Workspa
 // test/units/simulation_cpu/collision_encoding_test.cpp), run by the device code itself.
 // =============================================================================================
 constexpr u32 UNIT_LOOP_STATS = 1, UNIT_MATRIX_INCREMENT = 2, UNIT_COLLISION_WORDS = 3,
-              UNIT_MATH_LOG_EXP = 4, UNIT_MATH_POW_SQRT = 5, UNIT_PHILOX = 6;
+              UNIT_MATH_LOG_EXP = 4, UNIT_MATH_POW_SQRT = 5, UNIT_PHILOX = 6, UNIT_DRAWS = 7,
+              UNIT_DRAW_FORMS = 8;
+// kinds of UNIT_DRAWS and forms of UNIT_DRAW_FORMS (layouts: include/modle_hip.h)
+constexpr u32 DRAW_CANONICAL = 1, DRAW_BERNOULLI = 2, DRAW_UNIFORM_INT = 3, DRAW_NORMAL = 4,
+              DRAW_POISSON = 5, DRAW_BINOMIAL = 6, DRAW_GENEXTREME = 7;
+constexpr u32 FORM_CANONICAL = 1, FORM_BERNOULLI = 2, FORM_BUCKET_UDIV = 3, FORM_GENEXTREME = 4,
+              FORM_BINOM_FC = 5, FORM_UDIV = 6;
 
 // predicates of one collision word, packed: bit 0 collision_occurred(), bit 1 collision_avoided(),
 // bits 2..5 collision_occurred(CHROM_BOUNDARY / LEF_BAR / LEF_LEF_PRIMARY / LEF_LEF_SECONDARY),
@@ -195,6 +201,42 @@ MODLE_DEV u32 cw_predicates(u32 w) {
     f |= cw_avoided_as(w, kinds[k]) ? (64u << k) : 0u;
   }
   return f;
+}
+
+// random.hpp:28-29: SplitMix64(seed).generateSeedSequence<4>(), as modle_hip_prng_seed does on the host
+MODLE_DEV void unit_seed_state(u64 seed, u64 s[4]) {
+  for (int i = 0; i < 4; ++i) {
+    u64 z = (seed += 0x9e3779b97f4a7c15ull);
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    s[i] = z ^ (z >> 31);
+  }
+}
+
+// one draw of UNIT_DRAWS as the path makes it: the `*_exact` routine of the kind, executed by the whole wave
+// (`bucket`: uniform_int_bucket of the range, computed once per call like the path's callers do); uniform
+MODLE_DEV u64 unit_draw(Cell& c, u32 kind, u64 p0, u64 p1, u64 p2, u64 bucket) {
+  const f64 a = __builtin_bit_cast(f64, p0), b = __builtin_bit_cast(f64, p1), d = __builtin_bit_cast(f64, p2);
+  switch (kind) {
+    case DRAW_CANONICAL:
+      return __builtin_bit_cast(u64, canonical_raw(rng_next(c.g)));
+    case DRAW_BERNOULLI:  // (bernoulli_distribution draws nothing at p == 0: the path's callers skip the trial)
+      return a == 0.0 ? 0u : (bernoulli_raw(rng_next(c.g), a) ? 1u : 0u);
+    case DRAW_UNIFORM_INT: {  // {lo, hi} = (p0, p1)
+      const u64 range = p1 - p0;
+      if (range == 0) return p0;
+      if (range == ~u64(0)) return rng_next(c.g) + p0;
+      return uniform_int_exact(c.g, range, bucket) + p0;
+    }
+    case DRAW_NORMAL:  // {mean, sigma} = (a, b): a fresh distribution object per draw, no cached variate
+      return __builtin_bit_cast(u64, unit_normal_exact(c.g, c.lds) * b + a);
+    case DRAW_POISSON:
+      return poisson_exact(c.g, a);
+    case DRAW_BINOMIAL:  // {t, p} = (p0 as a signed integer, b)
+      return static_cast<u64>(binomial_exact(c.g, static_cast<i64>(p0), b));
+    default:  // DRAW_GENEXTREME {mu, sigma, xi} = (a, b, d)
+      return __builtin_bit_cast(u64, genextreme_from_canonical(canonical_raw(rng_next(c.g)), a, b, d));
+  }
 }
 
 // `in`: n pairs of 64-bit values; `out`: what the unit produces (see the cases); uniform
@@ -270,6 +312,65 @@ MODLE_DEV u32 run_test_units(const Params& p, const Interval& iv, const Workspac
         out[4 * v + 1] = (static_cast<u64>(x[3]) << 32) | x[2];
         out[4 * v + 2] = 0;
         out[4 * v + 3] = 0;
+      }
+    }
+  } else if (what == UNIT_DRAWS) {
+    // head (three pairs): kind, seed, three parameters as bit images, number of draws m (m + 1 <= 2 n);
+    // out = (engine outputs consumed, the m draws).  The count is fixed by the call: the only loops that are
+    // not are the rejection loops of the routines themselves, which end with probability one
+    if (n < 3) return ERR_INTERNAL;
+    const u32 kind = wave::uniform(static_cast<u32>(in[0]));
+    const u64 seed = wave::uniform(in[1]);
+    const u64 p0 = wave::uniform(in[2]), p1 = wave::uniform(in[3]), p2 = wave::uniform(in[4]);
+    const u64 m = wave::uniform(in[5]);
+    if (kind < DRAW_CANONICAL || kind > DRAW_GENEXTREME || m >= 2 * static_cast<u64>(n)) return ERR_INTERNAL;
+    u64 st[4];
+    unit_seed_state(seed, st);
+    rng_init(c.g, st);
+    const u64 range = p1 - p0;
+    const u64 bucket = (kind == DRAW_UNIFORM_INT && range != 0 && range != ~u64(0)) ? uniform_int_bucket(range) : 1;
+    for (u64 i = 0; i < m; ++i) {
+      const u64 v = unit_draw(c, kind, p0, p1, p2, bucket);
+      if (lane == 0) out[1 + i] = v;
+    }
+    if (lane == 0) out[0] = c.g.pos;
+  } else if (what == UNIT_DRAW_FORMS) {
+    // head pair: (form, unused); then two pairs (a, b, c, d) per element, one element per lane; out = up to
+    // four words per element at the element's own place, the rest zero
+    if (n < 1) return ERR_INTERNAL;
+    const u32 form = wave::uniform(static_cast<u32>(in[0]));
+    if (form < FORM_CANONICAL || form > FORM_UDIV) return ERR_INTERNAL;
+    const u32 count = (n - 1) / 2;
+    for (u32 base = 0; base < count; base += 64) {
+      const u32 v = base + lane;
+      if (v < count) {
+        const u64* e = in + 2 + 4 * static_cast<u64>(v);
+        u64* o = out + 2 + 4 * static_cast<u64>(v);
+        const u64 a = e[0], b = e[1];
+        u64 r0 = 0, r1 = 0;
+        if (form == FORM_CANONICAL) {
+          r0 = __builtin_bit_cast(u64, canonical_raw(a));
+        } else if (form == FORM_BERNOULLI) {  // (raw, p)
+          r0 = bernoulli_raw(a, __builtin_bit_cast(f64, b)) ? 1u : 0u;
+        } else if (form == FORM_BUCKET_UDIV) {  // (range, raw): the bucket, and raw / bucket as the position draws take it
+          if (a != ~u64(0)) {                   // (the full range has no bucket: zeros)
+            const u64 bucket = uniform_int_bucket(a);
+            r0 = bucket;
+            r1 = udiv_by_uniform(b, bucket, 1.0 / static_cast<f64>(bucket));
+          }
+        } else if (form == FORM_GENEXTREME) {  // (u, mu, sigma, xi)
+          r0 = __builtin_bit_cast(u64, genextreme_from_canonical(__builtin_bit_cast(f64, a), __builtin_bit_cast(f64, b),
+                                                               __builtin_bit_cast(f64, e[2]),
+                                                               __builtin_bit_cast(f64, e[3])));
+        } else if (form == FORM_BINOM_FC) {  // (k)
+          r0 = __builtin_bit_cast(u64, binom_fc(static_cast<i64>(a)));
+        } else if (b != 0) {  // FORM_UDIV (raw, d): any divisor, inside the stated bound of udiv_by_uniform or not
+          r0 = udiv_by_uniform(a, b, 1.0 / static_cast<f64>(b));
+        }
+        o[0] = r0;
+        o[1] = r1;
+        o[2] = 0;
+        o[3] = 0;
       }
     }
   } else {

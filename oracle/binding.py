@@ -64,6 +64,16 @@ def lib():
     L.mo_binomial.restype = C.c_int64
     L.mo_genextreme.argtypes = [P(Prng), C.c_double, C.c_double, C.c_double]
     L.mo_genextreme.restype = C.c_double
+    L.mo_draw_many.argtypes = [C.c_uint32, u64p, C.c_uint64, C.c_size_t, u64p, P(C.c_uint64)]
+    L.mo_draw_many.restype = C.c_int
+    L.mo_draw_forms.argtypes = [C.c_uint32, u64p, C.c_size_t, u64p]
+    L.mo_draw_forms.restype = C.c_int
+    L.mo_binom_fc.argtypes = [C.c_int64]
+    L.mo_binom_fc.restype = C.c_double
+    L.mo_uniform_int_bucket.argtypes = [C.c_uint64]
+    L.mo_uniform_int_bucket.restype = C.c_uint64
+    L.mo_udiv_by_uniform.argtypes = [C.c_uint64, C.c_uint64, C.c_double]
+    L.mo_udiv_by_uniform.restype = C.c_uint64
     L.mo_xxh3_64.argtypes = [C.c_char_p, C.c_size_t, C.c_uint64]
     L.mo_xxh3_64.restype = C.c_uint64
     L.mo_interval_hash.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]
@@ -126,6 +136,27 @@ def prng_from_state(state):
         g.s[i] = int(state[i])
     g.count = 0
     return g
+
+
+def draw_many(kind, params, seed, n):
+    """n draws of one kind (kinds and parameter words: MODLE_HIP_UNIT_DRAWS, include/modle_hip.h) from a
+    generator seeded with `seed`; returns (the draws as 64-bit words, engine outputs consumed)."""
+    words = np.zeros(3, dtype=np.uint64)
+    words[:len(params)] = np.asarray(params, dtype=np.uint64)
+    out = np.zeros(n, dtype=np.uint64)
+    consumed = C.c_uint64(0)
+    if lib().mo_draw_many(kind, words, seed, n, out, C.byref(consumed)) != 0:
+        raise ValueError(f"unknown kind of draw {kind}")
+    return out, consumed.value
+
+
+def draw_forms(form, elements):
+    """the pure forms of MODLE_HIP_UNIT_DRAW_FORMS on elements of four words; four words out per element"""
+    elements = np.ascontiguousarray(elements, dtype=np.uint64).reshape(-1, 4)
+    out = np.zeros_like(elements)
+    if lib().mo_draw_forms(form, elements.reshape(-1), len(elements), out.reshape(-1)) != 0:
+        raise ValueError(f"unknown form {form}")
+    return out
 
 
 def make_tasks(cfg, name, chrom_size, start, end, first_id=0):

@@ -144,18 +144,20 @@ static const double TWO_M56 = 1.387778780781445675529539585113525390625e-17; /* 
 
 /* boost::random::bernoulli_distribution<double>: p == 0 draws nothing;
  * otherwise double(raw) <= p * double(max - min) with max - min = 2^64 - 1 -> 2^64 */
+static inline int bernoulli_of_raw(uint64_t raw, double p) { return (double)raw <= p * TWO64; }
 int mo_bernoulli(mo_prng_t* g, double p) {
   if (p == 0.0) return 0;
-  return (double)mo_prng_next(g) <= p * TWO64;
+  return bernoulli_of_raw(mo_prng_next(g), p);
 }
 
 /* boost::random::generate_canonical<double, 53>: one 64-bit draw, divided by 2^64; a result
  * of exactly 1 is nudged down by epsilon/2 */
-double mo_canonical(mo_prng_t* g) {
-  double r = (double)mo_prng_next(g) / TWO64;
+static inline double canonical_of_raw(uint64_t raw) {
+  double r = (double)raw / TWO64;
   if (r == 1.0) r -= 2.220446049250313e-16 / 2;
   return r;
 }
+double mo_canonical(mo_prng_t* g) { return canonical_of_raw(mo_prng_next(g)); }
 
 /* boost::random::uniform_01<double>: raw * 2^-64, redrawn while the product rounds to 1 */
 double mo_uniform_01(mo_prng_t* g) {
@@ -166,12 +168,16 @@ double mo_uniform_01(mo_prng_t* g) {
 }
 
 /* boost::random::uniform_int_distribution<uint64_t>{lo, hi}: bucket rejection */
+uint64_t mo_uniform_int_bucket(uint64_t range) { /* range != 2^64 - 1 */
+  uint64_t bucket = UINT64_MAX / (range + 1);
+  if (UINT64_MAX % (range + 1) == range) ++bucket;
+  return bucket;
+}
 uint64_t mo_uniform_int(mo_prng_t* g, uint64_t lo, uint64_t hi) {
   const uint64_t range = hi - lo;
   if (range == 0) return lo;
   if (range == UINT64_MAX) return mo_prng_next(g) + lo;
-  uint64_t bucket = UINT64_MAX / (range + 1);
-  if (UINT64_MAX % (range + 1) == range) ++bucket;
+  const uint64_t bucket = mo_uniform_int_bucket(range);
   for (;;) {
     const uint64_t r = mo_prng_next(g) / bucket;
     if (r <= range) return r + lo;
@@ -409,9 +415,93 @@ int64_t mo_binomial(mo_prng_t* g, int64_t t, double p_) {
 }
 
 /* genextreme_value_distribution<double> (genextreme_value_distribution.hpp:87-105) */
+static double genextreme_of_canonical(double u, double mu, double sigma, double xi) {
+  if (xi == 0.0) return (mu - sigma) * mm_log(-mm_log(u));
+  return mu + (sigma * (1.0 - mm_pow(-mm_log(u), xi))) / xi;
+}
 double mo_genextreme(mo_prng_t* g, double mu, double sigma, double xi) {
-  if (xi == 0.0) return (mu - sigma) * mm_log(-mm_log(mo_canonical(g)));
-  return mu + (sigma * (1.0 - mm_pow(-mm_log(mo_canonical(g)), xi))) / xi;
+  return genextreme_of_canonical(mo_canonical(g), mu, sigma, xi);
+}
+
+/* ---- test-only entries: the draws in bulk, and the pure forms on given inputs ------------------
+ * (the counterparts of MODLE_HIP_UNIT_DRAWS / MODLE_HIP_UNIT_DRAW_FORMS, include/modle_hip.h: same
+ * kinds, same parameter words, same forms) */
+static inline double f64_of(uint64_t bits) {
+  double x;
+  memcpy(&x, &bits, 8);
+  return x;
+}
+static inline uint64_t bits_of(double x) {
+  uint64_t b;
+  memcpy(&b, &x, 8);
+  return b;
+}
+
+int mo_draw_many(uint32_t kind, const uint64_t params[3], uint64_t seed, size_t n, uint64_t* out,
+                 uint64_t* consumed) {
+  mo_prng_t g;
+  mo_prng_seed(&g, seed);
+  const double a = f64_of(params[0]), b = f64_of(params[1]), c = f64_of(params[2]);
+  if (kind < 1 || kind > 7) return -1;
+  for (size_t i = 0; i < n; ++i) {
+    switch (kind) {
+      case 1: out[i] = bits_of(mo_canonical(&g)); break;
+      case 2: out[i] = (uint64_t)mo_bernoulli(&g, a); break;
+      case 3: out[i] = mo_uniform_int(&g, params[0], params[1]); break;
+      case 4: out[i] = bits_of(mo_normal(&g, a, b)); break;
+      case 5: out[i] = mo_poisson(&g, a); break;
+      case 6: out[i] = (uint64_t)mo_binomial(&g, (int64_t)params[0], b); break;
+      default: out[i] = bits_of(mo_genextreme(&g, a, b, c)); break;
+    }
+  }
+  if (consumed != NULL) *consumed = g.count;
+  return 0;
+}
+
+double mo_binom_fc(int64_t k) { return k < 0 ? 0.0 : binom_fc(k); }
+
+/* the device's division of a raw output by a wave-uniform divisor (sim_rng.h: udiv_by_uniform): a
+ * double-precision product gives the quotient to within one, the remainder tells which way.  The
+ * oracle itself divides exactly (mo_uniform_int); this restatement exists to hold the device's form
+ * on inputs beyond the bound it states, where the plain quotient is not the expectation */
+uint64_t mo_udiv_by_uniform(uint64_t raw, uint64_t d, double inv) {
+  uint64_t q = (uint64_t)((double)raw * inv);
+  const uint64_t rem = raw - q * d;
+  if ((int64_t)rem < 0) {
+    --q;
+  } else if (rem >= d) {
+    ++q;
+  }
+  return q;
+}
+
+int mo_draw_forms(uint32_t form, const uint64_t* in, size_t count, uint64_t* out) {
+  if (form < 1 || form > 6) return -1;
+  for (size_t v = 0; v < count; ++v) {
+    const uint64_t* e = in + 4 * v;
+    uint64_t r0 = 0, r1 = 0;
+    if (form == 1) {
+      r0 = bits_of(canonical_of_raw(e[0]));
+    } else if (form == 2) {
+      r0 = (uint64_t)bernoulli_of_raw(e[0], f64_of(e[1]));
+    } else if (form == 3) {
+      if (e[0] != UINT64_MAX) {
+        r0 = mo_uniform_int_bucket(e[0]);
+        r1 = mo_udiv_by_uniform(e[1], r0, 1.0 / (double)r0);
+      }
+    } else if (form == 4) {
+      r0 = bits_of(genextreme_of_canonical(f64_of(e[0]), f64_of(e[1]), f64_of(e[2]), f64_of(e[3])));
+    } else if (form == 5) {
+      r0 = bits_of(mo_binom_fc((int64_t)e[0]));
+    } else if (e[1] != 0) {
+      r0 = mo_udiv_by_uniform(e[0], e[1], 1.0 / (double)e[1]);
+    }
+    out[4 * v] = r0;
+    out[4 * v + 1] = r1;
+    out[4 * v + 2] = 0;
+    out[4 * v + 3] = 0;
+  }
+  return 0;
 }
 
 /* ============================================================================================

@@ -140,6 +140,16 @@ double mo_normal(mo_prng_t* g, double mean, double sigma);
 uint64_t mo_poisson(mo_prng_t* g, double mean);
 int64_t mo_binomial(mo_prng_t* g, int64_t t, double p);
 double mo_genextreme(mo_prng_t* g, double mu, double sigma, double xi);
+/* test-only: n draws of one kind from a generator seeded with `seed` (kinds and the three parameter
+ * words as MODLE_HIP_UNIT_DRAWS, include/modle_hip.h; doubles come back as bit images), the engine
+ * outputs they consumed, and the pure forms of MODLE_HIP_UNIT_DRAW_FORMS on `count` elements of
+ * four words each (four words out per element).  Both return 0, or -1 for an unknown kind / form */
+int mo_draw_many(uint32_t kind, const uint64_t params[3], uint64_t seed, size_t n, uint64_t* out,
+                 uint64_t* consumed);
+int mo_draw_forms(uint32_t form, const uint64_t* in, size_t count, uint64_t* out);
+double mo_binom_fc(int64_t k);
+uint64_t mo_uniform_int_bucket(uint64_t range);
+uint64_t mo_udiv_by_uniform(uint64_t raw, uint64_t d, double inv);
 
 /* ---- hashing / task derivation ------------------------------------------------------------- */
 uint64_t mo_xxh3_64(const void* data, size_t len, uint64_t seed);

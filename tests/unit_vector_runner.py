@@ -14,6 +14,7 @@ from modle_amd.params import Config
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
                       "reference_unit_vectors.json")
 UNIT_LOOP_STATS, UNIT_MATRIX_INCREMENT, UNIT_COLLISION_WORDS = 1, 2, 3
+UNIT_DRAWS, UNIT_DRAW_FORMS = 7, 8  # (the regimes and the checks of these two: tests/draw_cases.py)
 PH_BIND, PH_GEN_MOVES = 0x1000, 0x2000
 EV_COLLISION = 0x10
 KINDS = [0x08, 0x04, 0x02, 0x01]  # predicate bit order: CHROM_BOUNDARY, LEF_BAR, PRIMARY, SECONDARY
@@ -81,6 +82,12 @@ class OracleUnits:
         w = self.L.mo_collision_word(idx, ev)
         return w, self.L.mo_collision_predicates(w)
 
+    def draws(self, kind, words, seed, m):
+        return self.b.draw_many(kind, words, seed, m)
+
+    def draw_forms(self, form, elements):
+        return self.b.draw_forms(form, elements)
+
     def make_prng(self, seed):
         return self.b.prng_from_seed(seed)
 
@@ -127,6 +134,20 @@ class DeviceUnits:
         out, _ = self._units(base_config(), UNIT_COLLISION_WORDS,
                              np.array([[idx, ev]], dtype=np.uint64), 0, 0, None, 0)
         return int(out[0]), int(out[1])
+
+    def draws(self, kind, words, seed, m):
+        """m draws of one kind by the device's `*_exact` routines: (the draws, engine outputs consumed)"""
+        call = np.zeros(2 * max(3, (m + 2) // 2), dtype=np.uint64)
+        call[:6] = np.array([kind, seed] + list(words) + [m], dtype=np.uint64)
+        out, _ = self._units(base_config(), UNIT_DRAWS, call, 0, 0, None, 0)
+        return out[1:m + 1], int(out[0])
+
+    def draw_forms(self, form, elements):
+        """the pure forms on elements of four words: four words out per element"""
+        el = np.ascontiguousarray(elements, dtype=np.uint64).reshape(-1)
+        call = np.concatenate([np.array([form, 0], dtype=np.uint64), el])
+        out, _ = self._units(base_config(), UNIT_DRAW_FORMS, call, 0, 0, None, 0)
+        return out[2:].reshape(-1, 4)
 
     def make_prng(self, seed):
         from phase_backend import splitmix_seed
