@@ -581,6 +581,12 @@ int modle_pixels_stripes_to_host(modle_pixels_handle* h, const uint32_t* d_ref, 
                                  uint64_t nrows, uint64_t ncols, uint64_t what, const uint64_t** rows,
                                  void* stream, char* err, size_t errlen);
 
+/* The launch caps this build of the library was compiled with, for the tests that lower them: caps[0] the
+ * workgroups of a stripes launch at most (2^20), caps[1] the grid's y of the band fill at most (65535),
+ * caps[2] the workgroups of the band check at most (1024), caps[3] the threads of the bin1_offset scan
+ * (1024).  No result depends on any of them.  Host only: no device is needed. */
+void modle_pixels_build_caps(uint64_t caps[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,7 +17,8 @@ from collections import namedtuple
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-SO_PATH = os.path.join(_HERE, "libmodle_pixels.so")
+# (MODLE_PIXELS_LIB: another build of the library, e.g. libmodle_pixels_smallgrid.so of `make smallgrid`)
+SO_PATH = os.path.join(_HERE, os.environ.get("MODLE_PIXELS_LIB", "libmodle_pixels.so"))
 ERR_ARG, ERR_DEVICE, ERR_RANGE, ERR_ORDER = -1, -2, -3, -4
 MAX_WINDOW, MAX_WINDOWS = 1024, 8  # MODLE_PIXELS_MAX_WINDOW, MODLE_PIXELS_MAX_WINDOWS
 MAX_DOT_WINDOW = 20  # MODLE_PIXELS_MAX_DOT_WINDOW
@@ -42,7 +43,12 @@ EXPORTS = ["modle_pixels_create", "modle_pixels_destroy", "modle_pixels_count", 
            "modle_pixels_coarse_pileup_to_host", "modle_pixels_sample_pixels", "modle_pixels_sample",
            "modle_pixels_sample_to_host", "modle_pixels_band_classify", "modle_pixels_band_check",
            "modle_pixels_band_fill", "modle_pixels_band_from_host", "modle_pixels_stripes_rows",
-           "modle_pixels_stripes", "modle_pixels_stripes_to_host"]  # every symbol include/modle_pixels.h declares
+           "modle_pixels_stripes", "modle_pixels_stripes_to_host",
+           "modle_pixels_build_caps"]  # every symbol include/modle_pixels.h declares
+# what modle_pixels_build_caps reports of the default build: the workgroups of a stripes launch, the grid's y of
+# the band fill, the workgroups of the band check, the threads of the bin1_offset scan
+BuildCaps = namedtuple("BuildCaps", "stripes_grid fill_grid_y check_groups scan_threads")
+DEFAULT_BUILD_CAPS = BuildCaps(1 << 20, 65535, 1024, 1024)
 
 _LIB = None
 _EXTRACTORS = {}
@@ -155,6 +161,8 @@ def lib():
         lb.modle_pixels_stripes_rows.argtypes = [C.c_uint64]
         lb.modle_pixels_stripes.argtypes = pair + [C.c_void_p, C.c_uint64, C.c_void_p] + err
         lb.modle_pixels_stripes_to_host.argtypes = pair + [C.POINTER(C.c_void_p), C.c_void_p] + err
+        lb.modle_pixels_build_caps.argtypes = [u64p]
+        lb.modle_pixels_build_caps.restype = None
         for name in EXPORTS:
             getattr(lb, name)  # raises AttributeError if a declared symbol is not exported
         _LIB = lb
@@ -181,6 +189,14 @@ def _call(fn, *args):
     rc = fn(*args, err, len(err))
     if rc != 0:
         raise PixelsError(rc, err.value.decode(errors="replace"))
+
+
+def build_caps():
+    """the launch caps the loaded library was compiled with, BuildCaps (modle_pixels_build_caps; no device is
+    needed): DEFAULT_BUILD_CAPS unless MODLE_PIXELS_LIB names a test build"""
+    caps = (C.c_uint64 * 4)()
+    lib().modle_pixels_build_caps(caps)
+    return BuildCaps(*(int(c) for c in caps))
 
 
 def coarse_shape(nrows, ncols, factor, first_bin=0):

@@ -37,7 +37,8 @@ constexpr unsigned kBandDiags = MODLE_PIXELS_BAND_TILE_DIAGS;  // diagonals of a
 constexpr unsigned kBandRows = kBandCols + kBandDiags - 1;     // matrix rows that cross a tile
 constexpr unsigned kFillThreads = 256;
 constexpr unsigned kCheckThreads = 256;
-constexpr unsigned kCheckGroups = 1024;  // workgroups of band_check at most
+constexpr unsigned kCheckGroups = MODLE_BAND_CHECK_GROUPS;  // workgroups of band_check at most: 1024 (pixels_context.h)
+constexpr unsigned kFillMaxY = MODLE_BAND_FILL_MAX_Y;       // gridDim.y of band_fill at most: 65535
 static_assert(kBandCols % 64 == 0 && kBandDiags % 64 == 0, "a wave stores within one column of a full tile");
 static_assert(kBandCols * kBandDiags * 4 <= 32 * 1024, "several workgroups per CU");
 static_assert(kBandCols == 64, "a wave reads a row's entries inside the tile in one step");
@@ -142,7 +143,7 @@ __global__ __launch_bounds__(kFillThreads) void band_fill(const int64_t* __restr
   const unsigned tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const uint64_t j0 = static_cast<uint64_t>(blockIdx.x) * kBandCols;
   const unsigned cn = static_cast<unsigned>(min(static_cast<uint64_t>(kBandCols), ncols - j0));
-  // (the grid's y is capped at 65535: a workgroup takes every gridDim.y-th tile of its columns)
+  // (the grid's y is capped at kFillMaxY: a workgroup takes every gridDim.y-th tile of its columns)
   for (uint64_t d0 = static_cast<uint64_t>(blockIdx.y) * kBandDiags; d0 < nrows;
        d0 += static_cast<uint64_t>(gridDim.y) * kBandDiags) {
   const unsigned dn = static_cast<unsigned>(min(static_cast<uint64_t>(kBandDiags), nrows - d0));
@@ -281,7 +282,7 @@ int fill_impl(modle_pixels_handle* h, const int64_t* d_bin2, const int32_t* d_co
     return MODLE_PIXELS_OK;
   }
   const dim3 grid(static_cast<unsigned>((ncols + kBandCols - 1) / kBandCols),
-                  static_cast<unsigned>(std::min<uint64_t>(65535, (nrows + kBandDiags - 1) / kBandDiags)));
+                  static_cast<unsigned>(std::min<uint64_t>(kFillMaxY, (nrows + kBandDiags - 1) / kBandDiags)));
   hipLaunchKernelGGL(band_fill, grid, dim3(kFillThreads), 0, stream, d_bin2, d_count, n, nrows, ncols, bin_offset,
                      d_row_start, d_out);
   PIX_TRY(hipGetLastError());

@@ -30,7 +30,7 @@ namespace {
 constexpr unsigned kCountCols = 64;     // columns of one pixels_count tile
 constexpr unsigned kCountDepth = 256;  // band words (d) of one pixels_count tile
 constexpr unsigned kCountThreads = 256;
-constexpr unsigned kScanThreads = 1024;
+constexpr unsigned kScanThreads = MODLE_PIXELS_SCAN_THREADS;  // 1024 (pixels_context.h)
 constexpr unsigned kExtractThreads = 256;  // 4 waves
 constexpr unsigned kRowsPerWave = 16;
 constexpr unsigned kRowsPerBlock = kRowsPerWave * (kExtractThreads / 64);
@@ -230,6 +230,14 @@ int extract_impl(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
 }
 
 }  // namespace
+
+extern "C" void modle_pixels_build_caps(uint64_t caps[4]) {
+  if (caps == nullptr) return;
+  caps[0] = MODLE_STRIPES_MAX_GRID;
+  caps[1] = MODLE_BAND_FILL_MAX_Y;
+  caps[2] = MODLE_BAND_CHECK_GROUPS;
+  caps[3] = kScanThreads;
+}
 
 extern "C" int modle_pixels_create(int device, modle_pixels_handle** out, char* err, size_t errlen) {
   if (out == nullptr || device < 0) {

@@ -43,7 +43,8 @@ constexpr unsigned kWaves = 4;      // waves of a workgroup
 constexpr unsigned kUnroll = 4;     // loads in flight per lane
 constexpr unsigned kMomRows = 9;    // n, Sa, Sb, Saa, Sbb, Sab (the last three in two words)
 constexpr unsigned kRankRows = 3;   // Raa, Rbb, Rab
-constexpr unsigned kMaxGrid = 1u << 20;  // workgroups of a launch; the kernels stride over what is beyond
+// workgroups of a launch, 2^20 (pixels_context.h); the kernels stride over what is beyond
+constexpr unsigned kMaxGrid = MODLE_STRIPES_MAX_GRID;
 constexpr uint64_t kAll = MODLE_PIXELS_STRIPES_MOMENTS | MODLE_PIXELS_STRIPES_MASKED | MODLE_PIXELS_STRIPES_RANKS;
 
 // the nine words of a stripe pair, in the order of the output rows

@@ -9,6 +9,26 @@
 
 #include "modle_pixels.h"
 
+// The launch geometry whose caps a test build lowers (`make smallgrid`), so that the loops behind them take
+// a second trip on small shapes; modle_pixels_build_caps reports the compiled values in this order.
+#ifndef MODLE_STRIPES_MAX_GRID  // workgroups of a launch of modle_stripes.hip at most
+#define MODLE_STRIPES_MAX_GRID (1u << 20)
+#endif
+#ifndef MODLE_BAND_FILL_MAX_Y  // gridDim.y of band_fill at most (modle_band.hip)
+#define MODLE_BAND_FILL_MAX_Y 65535u
+#endif
+#ifndef MODLE_BAND_CHECK_GROUPS  // workgroups of band_check at most (modle_band.hip)
+#define MODLE_BAND_CHECK_GROUPS 1024u
+#endif
+#ifndef MODLE_PIXELS_SCAN_THREADS  // threads of the one workgroup of pixels_scan (modle_pixels.hip)
+#define MODLE_PIXELS_SCAN_THREADS 1024u
+#endif
+static_assert(MODLE_STRIPES_MAX_GRID >= 1 && MODLE_STRIPES_MAX_GRID <= (1u << 20), "a grid's x");
+static_assert(MODLE_BAND_FILL_MAX_Y >= 1 && MODLE_BAND_FILL_MAX_Y <= 65535u, "a grid's y");
+static_assert(MODLE_BAND_CHECK_GROUPS >= 1 && MODLE_BAND_CHECK_GROUPS <= 1024u, "workgroups of band_check");
+static_assert(MODLE_PIXELS_SCAN_THREADS % 64 == 0 && MODLE_PIXELS_SCAN_THREADS >= 64 &&
+                  MODLE_PIXELS_SCAN_THREADS <= 1024u, "whole waves of one workgroup");
+
 struct DeviceStats {
   unsigned long long nnz;
   unsigned long long sum;

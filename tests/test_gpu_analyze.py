@@ -46,7 +46,7 @@ def analysis_options(bedpe):
 def analyze(args, expect_ok=True):
     if ranks._failed:
         pytest.fail(f"not started: the run {ranks._failed[0]} failed before")
-    env = {k: v for k, v in os.environ.items() if k != "MODLE_HIP_LIB"}
+    env = {k: v for k, v in os.environ.items() if k not in ("MODLE_HIP_LIB", "MODLE_PIXELS_LIB")}
     try:
         p = subprocess.run([sys.executable, "-m", "modle_amd", "analyze", *args], cwd=ROOT, env=env,
                            capture_output=True, text=True, timeout=300)

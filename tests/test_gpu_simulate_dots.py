@@ -92,7 +92,7 @@ def test_a_window_that_does_not_fit_ends_the_run_before_the_launch(workdir):
     options = BASIC + ["--dots", "--dots-window", "50kb"]  # 4 * 10 + 1 + 2 > 40
     p = subprocess.run([sys.executable, "-m", "modle_amd", "simulate", "-c", sizes, "-b", bed, "-o", prefix,
                         *ranks.COMMON, *options], cwd=ranks.ROOT, capture_output=True, text=True, timeout=120,
-                       env={k: v for k, v in os.environ.items() if k != "MODLE_HIP_LIB"})
+                       env={k: v for k, v in os.environ.items() if k not in ("MODLE_HIP_LIB", "MODLE_PIXELS_LIB")})
     assert p.returncode != 0
     last = p.stderr.strip().splitlines()[-1]
     assert last.startswith("--dots-window: the window of 50000 (10 bins of 5000) with 2 diagonals ignored does not fit "

@@ -71,7 +71,7 @@ def simulate(d, name, world, port, options):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
                "--master-addr", "127.0.0.1", "--master-port", str(port), *args,
                "--dist-backend", "gloo", "--device", "0"]
-    env = {k: v for k, v in os.environ.items() if k != "MODLE_HIP_LIB"}
+    env = {k: v for k, v in os.environ.items() if k not in ("MODLE_HIP_LIB", "MODLE_PIXELS_LIB")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     try:
         p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)

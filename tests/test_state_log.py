@@ -93,7 +93,7 @@ def test_cli_writes_the_state_log(tmp_path):
     (tmp_path / "g.chrom.sizes").write_text(sizes)
     (tmp_path / "b.bed").write_text(bed)
     prefix = str(tmp_path / "run")
-    env = {k: v for k, v in os.environ.items() if k != "MODLE_HIP_LIB"}
+    env = {k: v for k, v in os.environ.items() if k not in ("MODLE_HIP_LIB", "MODLE_PIXELS_LIB")}
     p = subprocess.run([sys.executable, "-m", "modle_amd", "simulate", "-c", str(tmp_path / "g.chrom.sizes"),
                         "-b", str(tmp_path / "b.bed"), "-o", prefix, "--ncells", "3", "-w", "500000",
                         "--target-contact-density", "0.5", "--log-model-internal-state", "-q"],
