@@ -1,7 +1,7 @@
 /* modle_pixels.h -- C ABI of the sparse-pixel extraction (modle_amd/libmodle_pixels.so), of the
  * coarsening of a band, of its dense regions, of its marginals, of its insulation sums, of its
  * dot candidates, of its pileups and of its random sampling, of the way back from sorted pixels to
- * a band, and of the comparison of two bands stripe by stripe (further down).
+ * a band, and of the comparison of two bands stripe by stripe and diagonal by diagonal (further down).
  *
  * The simulation leaves every interval as a dense band matrix in device memory
  * (modle_hip_interval_outputs).  A cooler file is made of the non-zero pixels only, sorted by
@@ -580,6 +580,57 @@ int modle_pixels_stripes(modle_pixels_handle* h, const uint32_t* d_ref, const ui
 int modle_pixels_stripes_to_host(modle_pixels_handle* h, const uint32_t* d_ref, const uint32_t* d_tgt,
                                  uint64_t nrows, uint64_t ncols, uint64_t what, const uint64_t** rows,
                                  void* stream, char* err, size_t errlen);
+
+/* ---- SCC: two bands compared diagonal by diagonal -----------------------------------------------------
+ *
+ * The sums the stratum-adjusted correlation coefficient of HiCRep (Yang et al., Genome Research 2017) is made
+ * of.  Two bands A (the reference, d_ref) and B (the target, d_tgt) of one shape, each in the layout above;
+ * they may be the same pointer.  M(x, y) is the symmetric matrix of a band: M(x, y) = band[max(x, y) * nrows +
+ * |x - y|] for 0 <= x, y < ncols, and 0 outside the matrix.  For the smoothing half-width `smooth` = h, 0 <= h
+ * <= MODLE_PIXELS_MAX_SCC_SMOOTH, the smoothed value of a pixel is the box SUM
+ *     X(i, j) = sum over |di| <= h, |dj| <= h of M(i + di, j + dj):
+ * the box crosses the main diagonal through the symmetry and the cells outside the chromosome count 0 (HiCRep's
+ * zero-padded mean filter; Pearson's correlation does not see the division by (2h + 1)^2 a mean would add, so
+ * nothing on the device is a float).  The strata are the diagonals d, min_diag <= d <= max_diag; the call
+ * requires max_diag + 2 h <= nrows - 1, so no box of a stratum reaches a diagonal the band does not hold and the
+ * result is that of the full matrix.  Stratum d has the ncols - d entries a_i = X_A(i, i + d) and b_i =
+ * X_B(i, i + d), 0 <= i < ncols - d, and per stratum the call writes MODLE_PIXELS_SCC_ROWS words:
+ *     n, Sa_lo, Sa_hi, Sb_lo, Sb_hi, Saa_lo, Saa_hi, Sbb_lo, Sbb_hi, Sab_lo, Sab_hi
+ *   n = #{ i : a_i != 0 or b_i != 0 }; an entry that is zero in both adds nothing to any other sum, so the
+ *       caller has both of HiCRep's sample conventions from one output: n, or ncols - d;
+ *   Sa = sum a, Saa = sum a * a, Sab = sum a * b: 128-bit sums in two words each.  a < 1681 * 2^32 < 2^43, so Sa
+ *       can pass 2^64 and Saa stays below 2^118: every shape and every uint32 count is exact and there is no
+ *       range refusal.
+ * The scores are one host statement (modle_amd/pixels.py: scc_scores).  The output is uint64[11][nrows],
+ * row-major, column d; the columns outside [min_diag, max_diag] hold 0.  EVERY output word is written exactly
+ * once, with a plain store: the caller does not pre-zero.  The words of either band that are no pixels are never
+ * read, every address is a function of nrows, ncols, h and the strata alone, and no result depends on the launch
+ * geometry: a strip of 64 strata is walked by at most modle_pixels_scc_groups() workgroups, whose partial sums
+ * meet in scratch of the context (grown on demand).
+ *
+ * There is no coarse form: coarsen either band with modle_pixels_coarsen and pass the result.
+ *
+ * MODLE_PIXELS_ERR_ARG, with nothing written: a null pointer, nrows == 0, nrows > ncols, smooth > 20, min_diag >
+ * max_diag, max_diag + 2 * smooth > nrows - 1, out_words != 11 * nrows, a d_out that is not 8-byte aligned or
+ * overlaps either band. */
+#define MODLE_PIXELS_SCC_ROWS 11
+#define MODLE_PIXELS_MAX_SCC_SMOOTH 20
+
+/* The workgroups per strip of 64 strata at most that this build of the library was compiled with (128; a test
+ * build lowers it).  No result depends on it.  Host only: no device is needed. */
+uint64_t modle_pixels_scc_groups(void);
+
+/* Enqueues the sums into the device array d_out (uint64[11][nrows], `out_words` == 11 * nrows words) on
+ * `stream`; the call does not wait. */
+int modle_pixels_scc(modle_pixels_handle* h, const uint32_t* d_ref, const uint32_t* d_tgt, uint64_t nrows,
+                     uint64_t ncols, uint64_t smooth, uint64_t min_diag, uint64_t max_diag, uint64_t* d_out,
+                     uint64_t out_words, void* stream, char* err, size_t errlen);
+
+/* The same into a pinned host buffer of the context (grown on demand, freed by modle_pixels_destroy): *rows
+ * (uint64[11][nrows]) stays valid until the next call on the context.  Waits for `stream`. */
+int modle_pixels_scc_to_host(modle_pixels_handle* h, const uint32_t* d_ref, const uint32_t* d_tgt, uint64_t nrows,
+                             uint64_t ncols, uint64_t smooth, uint64_t min_diag, uint64_t max_diag,
+                             const uint64_t** rows, void* stream, char* err, size_t errlen);
 
 /* The launch caps this build of the library was compiled with, for the tests that lower them: caps[0] the
  * workgroups of a stripes launch at most (2^20), caps[1] the grid's y of the band fill at most (65535),

@@ -637,6 +637,60 @@ class BandAnalyses:
             torch.cuda.synchronize(out.device)
         return out
 
+    def scc_moments(self, interval_id, other, other_id, smooth=0, min_diag=1, max_diag=None, factor=1, first_bin=0,
+                    other_factor=1, other_first_bin=0, stream=None):
+        """The interval compared diagonal by diagonal with band `other_id` of `other` (the reference, as in
+        stripe_moments): numpy uint64 [pixels.SCC_ROWS, nrows], per stratum min_diag <= d <= max_diag of the two
+        matrices smoothed by a box of half-width `smooth` bins the number of entries that are non-zero in
+        either and the 128-bit sums of a, b, a * a, b * b and a * b (include/modle_pixels.h), formed on the
+        device from the two bands where they lie (pixels.scc); the other columns hold 0.  `max_diag` None:
+        the widest the band allows, nrows - 1 - 2 * smooth.  Either side is first coarsened on the device when
+        its factor is above 1; the two shapes must then be equal, else ValueError.  HiCRep compares at equal
+        depth: sample the deeper band first (sample_tensors).  Only the sums cross to the host.  Call it after
+        wait()."""
+        from . import pixels
+
+        d_ref, d_tgt, nrows, ncols, keep = self._band_pair(interval_id, other, other_id, factor, first_bin,
+                                                           other_factor, other_first_bin, stream)
+        out = pixels.extractor(self.device).scc(d_ref, d_tgt, nrows, ncols, smooth, min_diag, max_diag,
+                                                stream)  # (waits)
+        del keep
+        return out
+
+    def scc(self, interval_id, other, other_id, smooth=0, min_diag=1, max_diag=None, include_zeros=False, factor=1,
+            first_bin=0, other_factor=1, other_first_bin=0, stream=None):
+        """(scc, rho, weight): HiCRep's stratum-adjusted correlation coefficient of the interval against the
+        reference, the correlation of every stratum and its weight: pixels.scc_scores of scc_moments.
+        `include_zeros`: a stratum counts all its entries, not only those that are non-zero in either matrix."""
+        from . import pixels
+
+        rows = self.scc_moments(interval_id, other, other_id, smooth, min_diag, max_diag, factor, first_bin,
+                                other_factor, other_first_bin, stream)
+        _, _, nrows, ncols = self.outputs(interval_id)
+        nrows, ncols = pixels.band_shape(nrows, ncols, factor, first_bin)
+        hi = nrows - 1 - 2 * int(smooth) if max_diag is None else int(max_diag)
+        return pixels.scc_scores(rows, ncols, min_diag, hi, include_zeros)
+
+    def scc_moments_tensor(self, interval_id, other, other_id, smooth=0, min_diag=1, max_diag=None, factor=1,
+                           first_bin=0, other_factor=1, other_first_bin=0, stream=None):
+        """The sums of scc_moments as one torch int64 tensor [pixels.SCC_ROWS, nrows] on the device, filled there
+        by the kernels: nothing crosses to the host.  The words hold the uint64 sums bit for bit.  The work is
+        enqueued on `stream` (None: the default stream, on which torch orders its own work); it is waited
+        for only when a side was coarsened into a scratch band, which goes when this returns."""
+        import torch
+
+        from . import pixels
+
+        d_ref, d_tgt, nrows, ncols, keep = self._band_pair(interval_id, other, other_id, factor, first_bin,
+                                                           other_factor, other_first_bin, stream)
+        if max_diag is None:
+            max_diag = nrows - 1 - 2 * int(smooth)
+        out = torch.empty((pixels.SCC_ROWS, nrows), dtype=torch.int64, device=torch.device("cuda", self.device))
+        pixels.scc_into(d_ref, d_tgt, nrows, ncols, smooth, min_diag, max_diag, out.data_ptr(), out.numel(), stream,
+                        device=self.device)
+        if any(k is not None for k in keep):
+            torch.cuda.synchronize(out.device)
+        return out
 
 
 # ---------------------------------------------------------------------------------------------

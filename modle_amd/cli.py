@@ -19,7 +19,15 @@ probability, drawn on the GPU (with --subsample-split also `<prefix>_sampled_res
 --compare-to REF.cool (or REF.mcool::/resolutions/R) `<prefix>_stripes.tsv`, every bin's vertical and
 horizontal stripe scored against the reference file the way `evaluate` scores them, from integer sums formed
 on the GPU: --compare-metrics LIST (pearson, spearman, rmse, eucl_dist; default pearson), --compare-resolution
-R (a multiple of -r, the bin size of REF; default -r) and --compare-exclude-zero-pixels (not with spearman).
+R (a multiple of -r, the bin size of REF; default -r) and --compare-exclude-zero-pixels (not with spearman);
+with --compare-to REF --scc also `<prefix>_scc.tsv`, per interval the stratum-adjusted correlation coefficient
+of HiCRep against the reference and the correlation of every diagonal, from integer sums formed on the GPU, at
+the bin size of the comparison: --scc-smooth D (the half-width of the smoothing box, a whole number of bins, at
+most 20; default 0), --scc-max-distance D (the last diagonal, a whole number of bins; default and at most the
+widest the band allows with that smoothing), --scc-ignore-diags N (the first diagonal; default 1, HiCRep's
+excluded main diagonal) and --scc-include-zeros (a diagonal counts all its pixels, not only those that are
+non-zero in either matrix).  HiCRep compares at equal depth: sample the deeper matrix first (--subsample-to).
+The score is the one pixels.scc_scores states, modelled on the Python package `hicrep`, not a run of it.
 Everything heavy is native: parsing and
 task generation in libmodle_hip.so (host), the simulation on the MI355X (one process per GPU;
 under torch.distributed.run the cells are sharded over the ranks and the matrices are summed
@@ -104,6 +112,7 @@ def resolution_list(text):
 # the limits and defaults of the library, under the names the front end uses (importing pixels loads nothing)
 MAX_INSULATION_WINDOWS, MAX_INSULATION_WINDOW_BINS = pixels.MAX_WINDOWS, pixels.MAX_WINDOW
 MAX_DOT_WINDOW_BINS, MAX_PILEUP_FLANK_BINS = pixels.MAX_DOT_WINDOW, pixels.MAX_PILEUP_FLANK
+MAX_SCC_SMOOTH_BINS = pixels.MAX_SCC_SMOOTH
 DOT_FOLDS, COMPARE_METRICS = pixels.DOT_FOLDS, pixels.STRIPE_METRICS
 
 
@@ -190,6 +199,10 @@ def pileup_path(prefix):
 
 def stripes_path(prefix):
     return prefix + "_stripes.tsv"
+
+
+def scc_path(prefix):
+    return prefix + "_scc.tsv"
 
 
 def sampled_paths(prefix, mcool=False):
@@ -297,6 +310,12 @@ def add_analysis_arguments(io):
     io.add_argument("--compare-resolution", type=genomic_distance, default=None, metavar="R",
                     help=argparse.SUPPRESS)
     io.add_argument("--compare-exclude-zero-pixels", action="store_true", default=None, help=argparse.SUPPRESS)
+    # HiCRep's SCC against the same reference (<prefix>_scc.tsv), kept out of the generated help likewise
+    io.add_argument("--scc", action="store_true", default=None, help=argparse.SUPPRESS)
+    io.add_argument("--scc-smooth", type=genomic_distance, default=None, metavar="D", help=argparse.SUPPRESS)
+    io.add_argument("--scc-max-distance", type=genomic_distance, default=None, metavar="D", help=argparse.SUPPRESS)
+    io.add_argument("--scc-ignore-diags", type=int, default=None, metavar="N", help=argparse.SUPPRESS)
+    io.add_argument("--scc-include-zeros", action="store_true", default=None, help=argparse.SUPPRESS)
 
 
 def build_parser():
@@ -476,12 +495,17 @@ Subsample = collections.namedtuple("Subsample", "path rest_path frac target seed
 # given, the bin size of the comparison, the metrics in the order given, whether zero pixels are left out,
 # and what preflight read of the reference: its bin size and its chromosomes
 Stripes = collections.namedtuple("Stripes", "path reference resolution metrics exclude_zero ref_bin_size ref_chroms")
+# what --scc asks for: the file (None with --skip-output, which --compare-to refuses), the half-width of the
+# smoothing box and the last diagonal in base pairs (None: the widest the band allows), the first diagonal, and
+# whether a diagonal counts the pixels that are zero in both matrices; the bin size is Stripes.resolution
+Scc = collections.namedtuple("Scc", "path smooth max_distance min_diag include_zeros")
 # The whole plan of a run, which preflight makes once: the bin sizes of the .mcool (None: a .cool), the
-# Outputs, this rank among the ranks and its device, the five records above (None: not asked for) and the
-# diagonals --coverage leaves out.  (The first five fields are also made positionally: the others default.)
+# Outputs, this rank among the ranks and its device, the five records above (None: not asked for), the
+# diagonals --coverage leaves out, and the Scc.  (The first five fields are also made positionally: the others
+# default.)
 Preflight = collections.namedtuple(
-    "Preflight", "bin_sizes outputs rank world device insulation dots pileup subsample stripes coverage_min_diag",
-    defaults=(None, None, None, None, None, 0))
+    "Preflight", "bin_sizes outputs rank world device insulation dots pileup subsample stripes coverage_min_diag scc",
+    defaults=(None, None, None, None, None, 0, None))
 
 
 def subsample_options(a, cfg):
@@ -627,6 +651,32 @@ def stripes_options(a, cfg):
     return Stripes(_file(a, stripes_path), a.compare_to, res, metrics, exclude_zero, ref_bin_size, ref_chroms)
 
 
+def scc_options(a, cfg, stripes):
+    """The stratum-adjusted correlation the arguments ask for, as an Scc, or None.  `stripes`: what
+    stripes_options returned; the comparison's bin size is its resolution.  SystemExit: a --scc-* option without
+    --scc, --scc without --compare-to, a negative number of diagonals, a smoothing or a largest distance that is
+    no whole number of bins, a smoothing above 20 bins."""
+    if not a.scc:
+        _needs("--scc", (("--scc-smooth", a.scc_smooth), ("--scc-max-distance", a.scc_max_distance),
+                         ("--scc-ignore-diags", a.scc_ignore_diags), ("--scc-include-zeros", a.scc_include_zeros)))
+        return None
+    if stripes is None:
+        raise SystemExit("--scc needs --compare-to")
+    res = int(stripes.resolution)
+    min_diag = 1 if a.scc_ignore_diags is None else a.scc_ignore_diags
+    if min_diag < 0:
+        raise SystemExit(f"--scc-ignore-diags: {min_diag} is negative")
+    smooth = 0 if a.scc_smooth is None else int(a.scc_smooth)
+    if smooth % res != 0:
+        raise SystemExit(f"--scc-smooth: {smooth} is not a multiple of the resolution of the comparison ({res})")
+    if smooth // res > MAX_SCC_SMOOTH_BINS:
+        raise SystemExit(f"--scc-smooth: {smooth} is {smooth // res} bins of {res}: at most {MAX_SCC_SMOOTH_BINS}")
+    far = None if a.scc_max_distance is None else int(a.scc_max_distance)
+    if far is not None and far % res != 0:
+        raise SystemExit(f"--scc-max-distance: {far} is not a multiple of the resolution of the comparison ({res})")
+    return Scc(_file(a, scc_path), smooth, far, min_diag, bool(a.scc_include_zeros))
+
+
 def insulation_options(a, cfg):
     """The insulation track the arguments ask for, as an Insulation, or None.
     SystemExit: --insulation-resolution or --insulation-ignore-diags without --insulation-windows, a
@@ -654,10 +704,11 @@ def preflight(a, cfg):
     """The whole plan of the run, a Preflight: what the arguments alone settle and refuse, without a genome or
     a GPU.  Nothing after it derives an analysis from the arguments again.  SystemExit:
     --coverage-ignore-diags without --coverage, or negative; what insulation_options, dots_options,
-    pileup_options, subsample_options and stripes_options refuse, in that order (the last opens the reference
-    cooler, the one time it is opened before the launch); a bad --mcool-resolutions list; on rank 0, an output
-    that exists without --force (cooler or .mcool, then bigwig, then .npz, then the expected, the coverage,
-    the insulation, the dots and the pileup file, then the sampled files, then the stripes).  With
+    pileup_options, subsample_options, stripes_options and scc_options refuse, in that order (stripes_options
+    opens the reference cooler, the one time it is opened before the launch); a bad --mcool-resolutions list; on
+    rank 0, an output that exists without --force (cooler or .mcool, then bigwig, then .npz, then the expected,
+    the coverage, the insulation, the dots and the pileup file, then the sampled files, then the stripes, then
+    the SCC).  With
     --skip-output no file is planned and none is looked at."""
     if a.coverage_ignore_diags is not None:
         if not a.coverage:
@@ -669,12 +720,13 @@ def preflight(a, cfg):
     pile = pileup_options(a, cfg, dots)
     sub = subsample_options(a, cfg)
     cmp_ = stripes_options(a, cfg)
+    scc = scc_options(a, cfg, cmp_)
     # (a bad list ends the run here, before anything is imported or simulated)
     bin_sizes = None if a.mcool_resolutions is None else mcool_bin_sizes(a.mcool_resolutions, cfg.bin_size)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     device = a.device if a.device is not None else int(os.environ.get("LOCAL_RANK", "0"))
-    analyses = (ins, dots, pile, sub, cmp_, a.coverage_ignore_diags or 0)
+    analyses = (ins, dots, pile, sub, cmp_, a.coverage_ignore_diags or 0, scc)
     if a.skip_output:
         return Preflight(bin_sizes, Outputs(None, None, None, None), rank, world, device, *analyses)
     cool_path, bw_path = output_paths(a.output_prefix, mcool=bin_sizes is not None)
@@ -689,6 +741,7 @@ def preflight(a, cfg):
         planned += [r.path for r in (ins, dots, pile, sub) if r is not None]
         planned += [sub.rest_path] if sub is not None and sub.split else []
         planned += [cmp_.path] if cmp_ is not None else []
+        planned += [scc.path] if scc is not None else []
         for p in planned:
             if p and os.path.exists(p) and not a.force:
                 raise SystemExit(f"refusing to overwrite {p}: pass --force to overwrite")
@@ -742,6 +795,11 @@ def check_plan(a, cfg, pre, plan, chroms):
                                     cmp_.ref_chroms, chroms)
         if bad is not None:
             raise SystemExit(f"--compare-to {cmp_.reference}: {bad}")
+    if pre.scc is not None:
+        bad = driver.scc_misfit(plan, int(cfg.bin_size), cmp_.resolution, pre.scc.smooth, pre.scc.max_distance,
+                                pre.scc.min_diag)
+        if bad is not None:
+            raise SystemExit(f"--scc: {bad}")
     return driver.dense_regions(plan, int(cfg.bin_size), chroms, a.dense_region) if a.dense_region else []
 
 

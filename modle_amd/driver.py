@@ -989,14 +989,113 @@ def write_stripes(path, plan, base, reference, resolution, exclude_zero, metrics
                 fh.writelines(stripes_lines(entry["interval"], base, factor, got))
 
 
+def scc_strata(nrows, resolution, smooth, max_distance, min_diag):
+    """(h, lo, hi): the half-width of the smoothing box in bins and the strata of a band of `nrows` diagonals
+    at `resolution` for the `smooth`, `max_distance` (bp; None: the widest the band allows) and `min_diag` of
+    a cli.Scc: hi = min(nrows - 1 - 2 h, max_distance // resolution), so that no box leaves the band.  lo > hi:
+    no stratum is left."""
+    h = int(smooth) // int(resolution)
+    hi = int(nrows) - 1 - 2 * h
+    if max_distance is not None:
+        hi = min(hi, int(max_distance) // int(resolution))
+    return h, int(min_diag), hi
+
+
+def scc_misfit(plan, base, resolution, smooth, max_distance, min_diag):
+    """What keeps the SCC from being formed at `resolution`, as a sentence that names the interval, or None: an
+    entry of the plan that has a matrix in whose band scc_strata leaves no stratum."""
+    for _, entry, _, _, (nr, _) in plan_bands(plan, base, resolution):
+        h, lo, hi = scc_strata(nr, resolution, smooth, max_distance, min_diag)
+        if lo > hi:
+            return (f"no diagonal is left in the band of {interval_name(entry['interval'])} ({nr} diagonals at "
+                    f"{int(resolution)}): with a smoothing of {h} bins the last one is {hi}, the first one {lo}")
+    return None
+
+
+def check_scc(name, rows, ncols, h, lo, hi, ref_diag, run_diag):
+    """What ties the sums of the strata (api.BandAnalyses.scc_moments) to the two bands, in exact integers,
+    before a row is written.  For every stratum lo <= d <= hi: n is at most its ncols - d entries; Sab^2 <=
+    Saa * Sbb (Cauchy-Schwarz); and, as the (2h + 1 - |k|) cells of a box on the diagonal d + k run over
+    different pixels of that diagonal while the box moves along the stratum,
+        Sa(d) <= sum over |k| <= 2h of (2h + 1 - |k|) * diag_sum_A(|d + k|)
+    against the sums per diagonal of the reference band, `ref_diag`, with equality at h == 0; the same for Sb
+    and the run's, `run_diag` (the marginals).  RuntimeError, naming the interval, the stratum and what fails."""
+    h = int(h)
+    for d in range(int(lo), int(hi) + 1):
+        w = [int(rows[k][d]) for k in range(11)]
+        n = w[0]
+        sa, sb, saa, sbb, sab = (w[k] | (w[k + 1] << 64) for k in (1, 3, 5, 7, 9))
+        if n > int(ncols) - d:
+            raise RuntimeError(f"{name}: diagonal {d} counts {n} entries, it has {int(ncols) - d} pixels")
+        if sab * sab > saa * sbb:
+            raise RuntimeError(f"{name}: diagonal {d} has Sab^2 = {sab * sab} above Saa * Sbb = {saa * sbb}")
+        for what, got, diag in (("reference", sa, ref_diag), ("run", sb, run_diag)):
+            most = sum((2 * h + 1 - abs(k)) * int(diag[abs(d + k)]) for k in range(-2 * h, 2 * h + 1))
+            if got > most or (h == 0 and got != most):
+                raise RuntimeError(f"{name}: diagonal {d} of the {what} adds up to {got} contacts, the diagonals "
+                                   f"its boxes reach allow {'exactly' if h == 0 else 'at most'} {most}")
+
+
+def _g17(x):
+    return "nan" if x != x else "%.17g" % x
+
+
+def scc_header(reference, resolution, smooth, include_zeros):
+    """the two header lines of <prefix>_scc.tsv: what was compared, then the columns"""
+    return (f"# reference={reference} resolution={int(resolution)} smooth={int(smooth)} "
+            f"include_zeros={'yes' if include_zeros else 'no'}\n"
+            "distance\tn\trho\tweight\n")
+
+
+def scc_lines(iv, base, factor, ncols, h, lo, hi, rows, include_zeros):
+    """the rows of <prefix>_scc.tsv for one interval: a `#` line with the chromosome, start, end, the bin size,
+    the half-width of the box in bins, the strata and the SCC, then per stratum its distance in base pairs, the
+    number of samples, its correlation and its weight (pixels.scc_scores of `rows`), floats as %.17g, NaN as
+    `nan`"""
+    from . import pixels
+
+    scc, rho, weight = pixels.scc_scores(rows, ncols, lo, hi, include_zeros)
+    res = int(base) * int(factor)
+    out = [f"# chrom={iv['name']} start={int(iv['start'])} end={int(iv['end'])} bin_size={res} smooth_bins={int(h)} "
+           f"min_diag={int(lo)} max_diag={int(hi)} scc={_g17(scc)}\n"]
+    for d in range(int(lo), int(hi) + 1):
+        n = int(ncols) - d if include_zeros else int(rows[0][d])
+        out.append(f"{d * res}\t{n}\t{_g17(float(rho[d - lo]))}\t{_g17(float(weight[d - lo]))}\n")
+    return out
+
+
+def write_scc(path, plan, base, reference, resolution, smooth, include_zeros, taken):
+    """<prefix>_scc.tsv: the header, then scc_lines of every entry of the plan that is not skipped, in plan
+    order.  `taken(k)` returns (ncols, h, lo, hi, rows) of plan entry k -- the strata and the sums
+    _interval_scc formed -- or None for an entry without a matrix."""
+    with open(path, "w") as fh:
+        fh.write(scc_header(reference, resolution, smooth, include_zeros))
+        for k, entry, _, factor, _ in plan_bands(plan, base, resolution):
+            got = taken(k)
+            if got is not None:
+                fh.writelines(scc_lines(entry["interval"], base, factor, *got, include_zeros))
+
+
+def _interval_scc(sim, plan, ids, marginals, scc, resolution, taken, k, ref, rid, nr, nc, factor, first_bin):
+    """What _interval_stripes does for --scc while the reference band `rid` of `ref` lies on the device: the sums
+    of the strata (scc_strata of the cli.Scc `scc` at the comparison's `resolution`) of the two bands are formed
+    where they lie, checked (check_scc) against the diagonal sums of both, and kept in `taken[k]` for write_scc."""
+    h, lo, hi = scc_strata(nr, resolution, scc.smooth, scc.max_distance, scc.min_diag)
+    rows = sim.scc_moments(ids[k], ref, rid, h, lo, hi, factor, first_bin)
+    check_scc(interval_name(plan[k]["interval"]), rows, nc, h, lo, hi, ref.marginals(rid)[0],
+              marginals(k, factor, first_bin)[0])
+    taken[k] = (nc, h, lo, hi, rows)
+
+
 @_needs_matrix
-def _interval_stripes(sim, plan, ids, reader, metrics, exclude_zero, sums, k, factor, first_bin):
+def _interval_stripes(sim, plan, ids, reader, metrics, exclude_zero, sums, k, factor, first_bin, scc=None):
     """write_stripes' callback.  The reference's pixels of the interval's chromosome are scattered into a band
     of the interval's own shape at the comparison's bin size on the device (api.LoadedBands.load_pixels at the
     interval's first bin in the file), the run's band is coarsened there where `factor` is above 1, the sums of
     the stripes are formed from the two where they lie and checked (check_stripes) against the contacts the
     reference band was loaded with and those of the run's band -- `sums[k]` of the cooler at the base bin size,
-    else counted on the coarse band --, and the reference band is let go."""
+    else counted on the coarse band --, and the reference band is let go.  Before it goes, `scc(k, ref, rid,
+    nrows, ncols, factor, first_bin)` is called where it is given (_interval_scc): the reference is loaded once."""
     from . import pixels
 
     entry = plan[k]
@@ -1011,6 +1110,8 @@ def _interval_stripes(sim, plan, ids, reader, metrics, exclude_zero, sums, k, fa
         rows = sim.stripe_moments(ids[k], ref, rid, stripes_what(metrics, exclude_zero), factor, first_bin)
         run_sum = sums[k] if factor == 1 and k in sums else sim.contact_sum(ids[k], factor, first_bin)
         check_stripes(interval_name(iv), rows, nr, st.sum_in, run_sum)
+        if scc is not None:
+            scc(k, ref, rid, nr, nc, factor, first_bin)
     finally:
         ref.close()
     return [tuple(pixels.stripe_scores(rows[d], m, exclude_zero) for d in (0, 1)) for m in metrics]
@@ -1152,24 +1253,32 @@ def pileup_file(sim, cfg, plan, ids, sums, marginals, log, pileup, interval_dots
     log(f"written {pileup.path}")
 
 
-def stripes_file(sim, cfg, plan, ids, sums, marginals, log, stripes):
+def stripes_file(sim, cfg, plan, ids, sums, marginals, log, stripes, scc=None):
     """<prefix>_stripes.tsv of the cli.Stripes `stripes`: the reference cooler is opened here, the one time after
-    the launch, for its pixels"""
+    the launch, for its pixels.  With a cli.Scc `scc` the sums of the strata are taken while every reference
+    band lies on the device, and <prefix>_scc.tsv is written after the stripes."""
     from . import cooler
 
+    taken = {}
+    each = None if scc is None else functools.partial(_interval_scc, sim, plan, ids, marginals, scc,
+                                                      int(stripes.resolution), taken)
     with cooler.CoolerReader(stripes.reference) as reader:
         write_stripes(stripes.path, plan, int(cfg.bin_size), stripes.reference, stripes.resolution,
                       stripes.exclude_zero, stripes.metrics,
                       functools.partial(_interval_stripes, sim, plan, ids, reader, list(stripes.metrics),
-                                        bool(stripes.exclude_zero), sums))
+                                        bool(stripes.exclude_zero), sums, scc=each))
     log(f"written {stripes.path}")
+    if scc is not None:
+        write_scc(scc.path, plan, int(cfg.bin_size), stripes.reference, stripes.resolution, scc.smooth,
+                  scc.include_zeros, taken.get)
+        log(f"written {scc.path}")
 
 
 def write_files(sim, cfg, plan, ids, missed, pre, regions, log, **attrs):
     """Rank 0's files of the plan `pre`, in this order: the cooler or .mcool with the missing-interactions
     warnings (`missed`: of collect_outputs), the sampled matrices (sample_matrices), the dense `regions`, the
     distance-decay curves at every bin size of the file, the coverage without the diagonals below
-    `pre.coverage_min_diag`, then insulation_file, dots_file, pileup_file and stripes_file.  All of them read
+    `pre.coverage_min_diag`, then insulation_file, dots_file, pileup_file and stripes_file (with `pre.scc` the SCC file too).  All of them read
     the matrices where they lie (with several ranks: the reduced tensors), after the cooler's INT32 range check
     has passed.  `attrs`: write_pixels' keywords."""
     outputs, bin_sizes = pre.outputs, pre.bin_sizes
@@ -1197,7 +1306,7 @@ def write_files(sim, cfg, plan, ids, missed, pre, regions, log, **attrs):
     if pre.pileup is not None:
         pileup_file(*shared, pre.pileup, interval_dots)
     if pre.stripes is not None:
-        stripes_file(*shared, pre.stripes)
+        stripes_file(*shared, pre.stripes, pre.scc)
 
 
 def write_outputs(sim, cfg, plan, ids, tensors, pre, regions=(), log=print, backend="nccl", **attrs):

@@ -6,7 +6,9 @@ over sliding diamond windows; its dots, the pixels enriched over their HiCCUPS n
 its pileups, the windows around anchor pairs summed into one; and its random sampling, every contact
 kept with one probability by a generator keyed by the pixel's coordinates; the way back, sorted pixels
 checked and scattered into a band on the GPU; and two bands compared stripe by stripe, the integer sums of
-every bin's vertical and horizontal stripe formed on the GPU and turned into scores by stripe_scores.
+every bin's vertical and horizontal stripe formed on the GPU and turned into scores by stripe_scores, and
+diagonal by diagonal, the sums of every stratum of the two smoothed matrices formed on the GPU and turned into
+HiCRep's stratum-adjusted correlation coefficient by scc_scores.
 There is no host fallback: without the library or
 without a device the calls fail."""
 import ctypes as C
@@ -31,6 +33,8 @@ BAND_TILE_COLS, BAND_TILE_DIAGS = 64, 128  # MODLE_PIXELS_BAND_TILE_COLS, _DIAGS
 STRIPES_MOMENTS, STRIPES_MASKED, STRIPES_RANKS = 1, 2, 4  # MODLE_PIXELS_STRIPES_MOMENTS, _MASKED, _RANKS
 MAX_STRIPE = 4096  # MODLE_PIXELS_MAX_STRIPE: the deepest band the rank sums are formed of
 STRIPE_METRICS = ("pearson", "spearman", "rmse", "eucl_dist")  # what stripe_scores forms (evaluate.METRICS)
+SCC_ROWS = 11  # MODLE_PIXELS_SCC_ROWS: n and the five 128-bit sums of a stratum
+MAX_SCC_SMOOTH = 20  # MODLE_PIXELS_MAX_SCC_SMOOTH: the largest half-width of the smoothing box
 DOT_FOLDS = (1.75, 1.75, 1.5, 1.5)  # HiCCUPS' thresholds: donut, lower-left, horizontal, vertical
 EXPORTS = ["modle_pixels_create", "modle_pixels_destroy", "modle_pixels_count", "modle_pixels_extract",
            "modle_pixels_to_host", "modle_pixels_coarse_shape", "modle_pixels_coarsen",
@@ -43,7 +47,8 @@ EXPORTS = ["modle_pixels_create", "modle_pixels_destroy", "modle_pixels_count", 
            "modle_pixels_coarse_pileup_to_host", "modle_pixels_sample_pixels", "modle_pixels_sample",
            "modle_pixels_sample_to_host", "modle_pixels_band_classify", "modle_pixels_band_check",
            "modle_pixels_band_fill", "modle_pixels_band_from_host", "modle_pixels_stripes_rows",
-           "modle_pixels_stripes", "modle_pixels_stripes_to_host",
+           "modle_pixels_stripes", "modle_pixels_stripes_to_host", "modle_pixels_scc_groups", "modle_pixels_scc",
+           "modle_pixels_scc_to_host",
            "modle_pixels_build_caps"]  # every symbol include/modle_pixels.h declares
 # what modle_pixels_build_caps reports of the default build: the workgroups of a stripes launch, the grid's y of
 # the band fill, the workgroups of the band check, the threads of the bin1_offset scan
@@ -161,6 +166,11 @@ def lib():
         lb.modle_pixels_stripes_rows.argtypes = [C.c_uint64]
         lb.modle_pixels_stripes.argtypes = pair + [C.c_void_p, C.c_uint64, C.c_void_p] + err
         lb.modle_pixels_stripes_to_host.argtypes = pair + [C.POINTER(C.c_void_p), C.c_void_p] + err
+        strata = [C.c_void_p] * 3 + [C.c_uint64] * 5  # handle, d_ref, d_tgt, nrows, ncols, smooth, min_diag, max_diag
+        lb.modle_pixels_scc_groups.argtypes = []
+        lb.modle_pixels_scc_groups.restype = C.c_uint64
+        lb.modle_pixels_scc.argtypes = strata + [C.c_void_p, C.c_uint64, C.c_void_p] + err
+        lb.modle_pixels_scc_to_host.argtypes = strata + [C.POINTER(C.c_void_p), C.c_void_p] + err
         lb.modle_pixels_build_caps.argtypes = [u64p]
         lb.modle_pixels_build_caps.restype = None
         for name in EXPORTS:
@@ -514,6 +524,57 @@ def stripe_scores(rows, metric, masked=False):
     return out
 
 
+def scc_groups():
+    """the workgroups per strip of 64 strata at most that the loaded library was compiled with
+    (modle_pixels_scc_groups; no device is needed): 128 unless MODLE_PIXELS_LIB names a test build"""
+    return int(lib().modle_pixels_scc_groups())
+
+
+def _strata(smooth, min_diag, max_diag):
+    """the three numbers of an scc call, refused outside uint64 (ctypes would wrap them silently)"""
+    got = tuple(int(x) for x in (smooth, min_diag, max_diag))
+    if not all(0 <= x < 1 << 64 for x in got):
+        raise PixelsError(ERR_ARG, f"scc: smooth, min_diag, max_diag = {got} are no uint64")
+    return got
+
+
+def scc_scores(rows, ncols, min_diag, max_diag, include_zeros=False):
+    """(scc, rho, weight): the stratum-adjusted correlation coefficient of HiCRep (Yang et al., Genome Research
+    2017) from the integer sums `rows`, uint64 [SCC_ROWS, nrows] (Extractor.scc, or the sums restated on the
+    host), of the strata min_diag .. max_diag of two bands of `ncols` bins.  The one statement of what the score
+    is, formed in Python integers, exactly, up to a final division and root.  Per stratum d:
+        n       rows[0][d], the entries that are non-zero in either matrix; with `include_zeros` all ncols - d
+                entries (an entry that is zero in both adds nothing to any sum, so n alone changes)
+        rho_d   (n Sab - Sa Sb) / sqrt((n Saa - Sa^2)(n Sbb - Sb^2)), clipped to [-1, 1]; NaN when a variance
+                is 0 or n < 2
+        w_d     n (1 + 1 / n) (1 - 1 / n) / 12 = (n^2 - 1) / (12 n) for n >= 2, else 0: n times the variance of
+                the ranks of n distinct values scaled to (0, 1], HiCRep's variance-stabilised weight
+        scc     sum of w_d rho'_d / sum of w_d, rho'_d = rho_d with 0 where it is not finite (such a stratum
+                keeps its weight); NaN when the weights add up to 0
+    `rho` and `weight` are float64 arrays of max_diag - min_diag + 1 entries; `rho` keeps its NaNs.  The rule is
+    modelled on the Python package `hicrep`; where the two differ, what is written here holds."""
+    rows = np.asarray(rows)
+    ncols, lo, hi = int(ncols), int(min_diag), int(max_diag)
+    if rows.ndim != 2 or rows.dtype != np.uint64 or rows.shape[0] != SCC_ROWS:
+        raise ValueError(f"scc_scores: rows of shape {rows.shape} and type {rows.dtype} are no uint64 [{SCC_ROWS}, nrows]")
+    if not 0 <= lo <= hi < rows.shape[1] or hi >= ncols:
+        raise ValueError(f"scc_scores: the strata {lo} .. {hi} are not strata of a band of {rows.shape[1]} diagonals "
+                         f"and {ncols} bins")
+    rho = np.empty(hi - lo + 1, dtype=np.float64)
+    weight = np.empty(hi - lo + 1, dtype=np.float64)
+    top, bottom = 0.0, 0.0
+    for d in range(lo, hi + 1):
+        w = [int(rows[k][d]) for k in range(SCC_ROWS)]
+        n = ncols - d if include_zeros else w[0]
+        sa, sb, saa, sbb, sab = (w[k] | (w[k + 1] << 64) for k in (1, 3, 5, 7, 9))
+        r = _pearson(n, sa, sb, saa, sbb, sab) if n >= 2 else math.nan
+        wd = (n * n - 1) / (12 * n) if n >= 2 else 0.0  # (the quotient of two ints is correctly rounded)
+        rho[d - lo], weight[d - lo] = r, wd
+        top += wd * (r if math.isfinite(r) else 0.0)
+        bottom += wd
+    return (top / bottom if bottom > 0 else math.nan), rho, weight
+
+
 class Extractor:
     """One context of the library on one device (modle_pixels_create)."""
 
@@ -804,6 +865,26 @@ class Extractor:
         rows = stripes_rows(what)
         return _host_array(ptr.value, 2 * rows * int(ncols), np.uint64).reshape(2, rows, int(ncols))
 
+    def scc_into(self, d_ref, d_tgt, nrows, ncols, smooth, min_diag, max_diag, d_out, out_words, stream=None):
+        """enqueues the comparison of the bands at `d_ref` and `d_tgt` (one shape; they may be the same)
+        diagonal by diagonal into the caller-owned device array `d_out` (uint64[SCC_ROWS][nrows], 8-byte aligned,
+        `out_words` == SCC_ROWS * nrows): per stratum min_diag <= d <= max_diag of the matrices smoothed by a box
+        of half-width `smooth` <= MAX_SCC_SMOOTH (max_diag + 2 * smooth <= nrows - 1) n and the 128-bit sums of
+        a, b, a * a, b * b and a * b; the other columns hold 0; every word is written (modle_pixels_scc)"""
+        _call(self._L.modle_pixels_scc, self._h, d_ref, d_tgt, int(nrows), int(ncols),
+              *_strata(smooth, min_diag, max_diag), d_out, int(out_words), _stream_ptr(stream))
+
+    def scc(self, d_ref, d_tgt, nrows, ncols, smooth=0, min_diag=1, max_diag=None, stream=None):
+        """the sums of scc_into as a numpy uint64[SCC_ROWS, nrows] the caller owns, formed on the device
+        (modle_pixels_scc_to_host); `max_diag` None: the widest the band allows, nrows - 1 - 2 * smooth;
+        scc_scores turns it into the score"""
+        if max_diag is None:
+            max_diag = int(nrows) - 1 - 2 * int(smooth)
+        ptr = C.c_void_p()
+        _call(self._L.modle_pixels_scc_to_host, self._h, d_ref, d_tgt, int(nrows), int(ncols),
+              *_strata(smooth, min_diag, max_diag), C.byref(ptr), _stream_ptr(stream))
+        return _host_array(ptr.value, SCC_ROWS * int(nrows), np.uint64).reshape(SCC_ROWS, int(nrows))
+
 
 def extractor(device=0):
     """the process-wide context of `device`"""
@@ -957,3 +1038,15 @@ def stripes(d_ref, d_tgt, nrows, ncols, what=STRIPES_MOMENTS, stream=None, devic
     """The sums of the stripes of the bands at device pointers `d_ref` and `d_tgt`: numpy uint64[2,
     stripes_rows(what), ncols], formed on the device."""
     return extractor(device).stripes(d_ref, d_tgt, nrows, ncols, what, stream)
+
+
+def scc_into(d_ref, d_tgt, nrows, ncols, smooth, min_diag, max_diag, d_out, out_words, stream=None, device=0):
+    """The sums of the strata of the bands at device pointers `d_ref` and `d_tgt`, into the device array `d_out`
+    (uint64[SCC_ROWS][nrows]); enqueued on `stream`, nothing crosses to the host."""
+    extractor(device).scc_into(d_ref, d_tgt, nrows, ncols, smooth, min_diag, max_diag, d_out, out_words, stream)
+
+
+def scc(d_ref, d_tgt, nrows, ncols, smooth=0, min_diag=1, max_diag=None, stream=None, device=0):
+    """The sums of the strata of the bands at device pointers `d_ref` and `d_tgt`: numpy uint64[SCC_ROWS, nrows],
+    formed on the device."""
+    return extractor(device).scc(d_ref, d_tgt, nrows, ncols, smooth, min_diag, max_diag, stream)

@@ -23,6 +23,10 @@
 #ifndef MODLE_PIXELS_SCAN_THREADS  // threads of the one workgroup of pixels_scan (modle_pixels.hip)
 #define MODLE_PIXELS_SCAN_THREADS 1024u
 #endif
+#ifndef MODLE_SCC_MAX_GROUPS  // workgroups per strip of 64 strata at most (modle_scc.hip); modle_pixels_scc_groups
+#define MODLE_SCC_MAX_GROUPS 128u
+#endif
+static_assert(MODLE_SCC_MAX_GROUPS >= 1 && MODLE_SCC_MAX_GROUPS <= 65535u, "a grid's y");
 static_assert(MODLE_STRIPES_MAX_GRID >= 1 && MODLE_STRIPES_MAX_GRID <= (1u << 20), "a grid's x");
 static_assert(MODLE_BAND_FILL_MAX_Y >= 1 && MODLE_BAND_FILL_MAX_Y <= 65535u, "a grid's y");
 static_assert(MODLE_BAND_CHECK_GROUPS >= 1 && MODLE_BAND_CHECK_GROUPS <= 1024u, "workgroups of band_check");
@@ -145,6 +149,10 @@ struct modle_pixels_handle {
   GrowBuf<int32_t> band_count;
   // modle_pixels_stripes_to_host: two directions of rows(what) rows of ncols words (modle_stripes.hip)
   GrowBuf<uint64_t, true> stripes;
+  // modle_pixels_scc*: the workgroups' partial sums (per strip and group 11 rows of 64 words), and of the
+  // to-host form the 11 rows of nrows words (modle_scc.hip)
+  GrowBuf<uint64_t> scc_partial;
+  GrowBuf<uint64_t, true> scc;
 };
 
 #endif
