@@ -317,6 +317,93 @@ int modle_pixels_coarse_dots_to_host(modle_pixels_handle* h, const uint32_t* d_b
                                      const int64_t** bin1_offset, modle_pixels_stats* stats,
                                      void* stream, char* err, size_t errlen);
 
+/* ---- Dots, the statistical test: lambda-chunk histograms and count thresholds -------------------
+ *
+ * The other half of HiCCUPS (Rao et al. 2014; `cooltools dots`): every pixel is binned by its locally
+ * adjusted expected value into logarithmic "lambda chunks", the observed counts of every chunk are
+ * histogrammed over the whole genome, the host turns every chunk's histogram into a count threshold (a
+ * Poisson tail under a Benjamini-Hochberg rule: pixels.dot_thresholds) and a pixel is called when it
+ * clears the threshold of its chunk for all four neighbourhoods.  Shape, `w`, `p`, `min_diag`, the VALID
+ * pixels, O_k and the acceptance rule 4w + 1 + min_diag <= nrows are those of modle_pixels_dots.
+ *
+ *   lam[4][nrows]   HOST doubles; at the valid d every entry >= 0 and no NaN (+inf is allowed), only those
+ *                   are read.  In the front end e[d] / X_k[d], pixels.dot_scales with folds of 1.  The
+ *                   lambda of a valid pixel is lambda_k = (double)O_k * lam[k][d]: one IEEE-754 double
+ *                   product, never contracted.
+ *   edges[n_edges]  HOST doubles, 1 <= n_edges <= MODLE_PIXELS_MAX_DOT_EDGES, finite, > 0, strictly
+ *                   increasing; n_chunks = n_edges + 1.
+ *   chunk(lambda)   the number of edges strictly below lambda: chunk c is (edges[c-1], edges[c]], the
+ *                   pd.cut convention of cooltools.  A NaN lambda (0 * inf) goes to the top chunk n_edges;
+ *                   +inf goes there by the rule itself.  The top chunk has no finite upper edge.
+ *
+ * HISTOGRAM: uint64 hist[4][n_chunks][n_obs], 2 <= n_obs <= MODLE_PIXELS_MAX_DOT_OBS.  For every VALID
+ * pixel (a zero is a pixel too) and every k, modle_pixels_dot_hist ADDS one to
+ *     hist[k][chunk(lambda_k)][min(obs, n_obs - 1)]:
+ * the caller zeroes the table, and the intervals of a genome accumulate into one.  Nothing else is
+ * written.  d_hist is 8-byte aligned and does not overlap the band.  The adds are integer atomics, so
+ * the table does not depend on their order.
+ *
+ * DECISION: thr[4][n_chunks] is a HOST table of uint32, 0 = "never".  A valid pixel is a CANDIDATE when
+ * obs >= min_count (>= 1), for every k  t = thr[k][chunk(lambda_k)] != 0 and obs >= t, and, when `scale`
+ * is not NULL, also the fold test of modle_pixels_dots, (double)obs >= (double)O_k * scale[k][d] (the
+ * table as there).  d_cand is that of modle_pixels_dots: the call defines every word, the trailing one
+ * included.
+ *
+ * MODLE_PIXELS_ERR_ARG, with nothing written: what modle_pixels_dots refuses of handle, band, shape, w, p,
+ * min_diag (and of min_count, scale and d_cand in the decision), a null lam, edges, thr or output, a NaN or
+ * negative lam entry at a valid d, n_edges or n_obs out of range, edges that are not finite, positive and
+ * strictly increasing, a misaligned d_hist, an output that overlaps the band. */
+#define MODLE_PIXELS_MAX_DOT_EDGES 63
+#define MODLE_PIXELS_MAX_DOT_OBS 16384
+
+/* Enqueues the work on `stream`; the call does not wait. */
+int modle_pixels_dot_hist(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols,
+                          uint64_t w, uint64_t p, uint64_t min_diag, const double* lam,
+                          const double* edges, uint64_t n_edges, uint64_t n_obs, uint64_t* d_hist,
+                          void* stream, char* err, size_t errlen);
+
+/* One call: zeroes a scratch table of the context, runs the kernel, copies the table to pinned memory of
+ * the context (*hist: uint64[4][n_chunks][n_obs], valid until the next call on it) and waits. */
+int modle_pixels_dot_hist_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                                  uint64_t ncols, uint64_t w, uint64_t p, uint64_t min_diag,
+                                  const double* lam, const double* edges, uint64_t n_edges,
+                                  uint64_t n_obs, const uint64_t** hist, void* stream, char* err,
+                                  size_t errlen);
+
+/* The same at `factor` times the bin size, as modle_pixels_coarse_dots_to_host: `w`, `p`, `min_diag` count
+ * coarse bins and lam has nrows' columns. */
+int modle_pixels_coarse_dot_hist_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                                         uint64_t ncols, uint64_t factor, uint64_t first_bin, uint64_t w,
+                                         uint64_t p, uint64_t min_diag, const double* lam,
+                                         const double* edges, uint64_t n_edges, uint64_t n_obs,
+                                         const uint64_t** hist, void* stream, char* err, size_t errlen);
+
+/* The decision into d_cand; enqueues the work on `stream`, the call does not wait. */
+int modle_pixels_dots_fdr(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols,
+                          uint64_t w, uint64_t p, uint64_t min_diag, uint64_t min_count,
+                          const double* lam, const double* edges, uint64_t n_edges, const uint32_t* thr,
+                          const double* scale, uint32_t* d_cand, void* stream, char* err, size_t errlen);
+
+/* The candidates as sorted pixels, as modle_pixels_dots_to_host. */
+int modle_pixels_dots_fdr_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                                  uint64_t ncols, uint64_t w, uint64_t p, uint64_t min_diag,
+                                  uint64_t min_count, const double* lam, const double* edges,
+                                  uint64_t n_edges, const uint32_t* thr, const double* scale,
+                                  int64_t bin_offset, const int64_t** bin1, const int64_t** bin2,
+                                  const int32_t** count, const int64_t** bin1_offset,
+                                  modle_pixels_stats* stats, void* stream, char* err, size_t errlen);
+
+/* The same at `factor` times the bin size, as modle_pixels_coarse_dots_to_host. */
+int modle_pixels_coarse_dots_fdr_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                                         uint64_t ncols, uint64_t factor, uint64_t first_bin, uint64_t w,
+                                         uint64_t p, uint64_t min_diag, uint64_t min_count,
+                                         const double* lam, const double* edges, uint64_t n_edges,
+                                         const uint32_t* thr, const double* scale, int64_t bin_offset,
+                                         const int64_t** bin1, const int64_t** bin2,
+                                         const int32_t** count, const int64_t** bin1_offset,
+                                         modle_pixels_stats* stats, void* stream, char* err,
+                                         size_t errlen);
+
 /* ---- Pileups: windows around anchor pairs, summed ------------------------------------------------
  *
  * M(x, y) is the symmetric matrix of the band: M(x, y) = band[j * nrows + (j - i)], i = min(x, y),

@@ -394,6 +394,14 @@ class BandAnalyses:
         d_band, nrows, ncols, _keep = self._band(interval_id, factor, first_bin, None)
         return pixels.extractor(self.device).count(d_band, nrows, ncols).sum  # (waits: a scratch may go)
 
+    def contact_max(self, interval_id, factor=1, first_bin=0):
+        """The largest count of the interval's band at `factor` times the bin size, found on the device
+        (pixels.Stats.max_count of pixels.count; `first_bin` as for pixels()).  Call it after wait()."""
+        from . import pixels
+
+        d_band, nrows, ncols, _keep = self._band(interval_id, factor, first_bin, None)
+        return pixels.extractor(self.device).count(d_band, nrows, ncols).max_count  # (waits: a scratch may go)
+
     def dot_table(self, interval_id, w, p, folds=None, min_diag=2, factor=1, first_bin=0, stream=None):
         """(scale, expected) of the interval for dots(): the table pixels.dot_scales builds from the
         diagonal sums of the marginals pass (float64 [4, nrows]) and the expected count per diagonal,
@@ -406,7 +414,8 @@ class BandAnalyses:
         e = diag_sum.astype(np.float64) / (np.float64(ncols) - np.arange(len(diag_sum), dtype=np.float64))
         return scale, e
 
-    def dots(self, interval_id, w=5, p=2, min_count=1, folds=None, min_diag=2, factor=1, first_bin=0, stream=None):
+    def dots(self, interval_id, w=5, p=2, min_count=1, folds=None, min_diag=2, factor=1, first_bin=0, stream=None,
+             thresholds=None, edges=None):
         """The dot candidates of the interval: (bin1, bin2, count, expected), numpy int64, int64, int32
         and float64 arrays in cooler order.  A candidate is a pixel (bin1, bin2) whose whole window of
         half-width `w` bins lies in the band on or above diagonal `min_diag`, with count >= `min_count`
@@ -417,17 +426,24 @@ class BandAnalyses:
         simulated counts need no balancing.  `expected` is e at each candidate's distance.  Only the
         diagonal sums and the candidates cross to the host.  Call it after wait().  `factor`,
         `first_bin`: as for pixels(); `w`, `p`, `min_diag` then count coarse bins.  cluster_dots() thins
-        the candidates to local maxima."""
+        the candidates to local maxima.  With `thresholds` (uint32 [4, len(edges) + 1], what dots_fdr() and
+        pixels.dot_thresholds give; `edges` None: HiCCUPS' lambda chunks) a candidate must also clear, for
+        every k, the threshold of the lambda chunk that e[d] * O_k / X_k falls in: the statistical test."""
         from . import pixels
 
         scale, e = self.dot_table(interval_id, w, p, folds, min_diag, factor, first_bin, stream)
         d_band, _, nrows, ncols = self.outputs(interval_id)
-        px = pixels.extractor(self.device).dots(d_band, nrows, ncols, w, p, min_diag, min_count, scale, 0, stream,
-                                                factor, first_bin)
+        if thresholds is None:
+            px = pixels.extractor(self.device).dots(d_band, nrows, ncols, w, p, min_diag, min_count, scale, 0, stream,
+                                                    factor, first_bin)
+        else:
+            lam = self.dot_lambda_table(interval_id, w, p, min_diag, factor, first_bin, stream)
+            px = pixels.extractor(self.device).dots_fdr(d_band, nrows, ncols, w, p, min_diag, min_count, lam, edges,
+                                                        thresholds, scale, 0, stream, factor, first_bin)
         return px.bin1, px.bin2, px.count, e[px.bin2 - px.bin1]
 
     def dots_tensors(self, interval_id, w=5, p=2, min_count=1, folds=None, min_diag=2, factor=1, first_bin=0,
-                     stream=None):
+                     stream=None, thresholds=None, edges=None):
         """The dot candidates of dots() as three torch tensors (bin1, bin2 int64, count int32) on the
         simulator's device: the kernel fills a candidate band there, which is counted and extracted
         into tensors of exactly nnz entries.  Only nnz and the nrows diagonal sums cross to the host."""
@@ -436,12 +452,18 @@ class BandAnalyses:
         from . import pixels
 
         scale, _ = self.dot_table(interval_id, w, p, folds, min_diag, factor, first_bin, stream)
+        lam = None if thresholds is None else self.dot_lambda_table(interval_id, w, p, min_diag, factor, first_bin,
+                                                                    stream)
         d_band, nrows, ncols, keep = self._band(interval_id, factor, first_bin, stream)
         dev = torch.device("cuda", self.device)
         ex = pixels.extractor(self.device)
         cand = torch.empty(nrows * ncols + 1, dtype=torch.int32, device=dev)
         offsets = torch.empty(ncols + 1, dtype=torch.int64, device=dev)
-        ex.dots_into(d_band, nrows, ncols, w, p, min_diag, min_count, scale, cand.data_ptr(), None, stream)
+        if thresholds is None:
+            ex.dots_into(d_band, nrows, ncols, w, p, min_diag, min_count, scale, cand.data_ptr(), None, stream)
+        else:
+            ex.dots_fdr_into(d_band, nrows, ncols, w, p, min_diag, min_count, lam, edges, thresholds, scale,
+                             cand.data_ptr(), stream)
         nnz = ex.count(cand.data_ptr(), nrows, ncols, offsets.data_ptr(), stream).nnz  # (waits)
         del keep
         bin1 = torch.empty(nnz, dtype=torch.int64, device=dev)
@@ -451,6 +473,80 @@ class BandAnalyses:
                         count.data_ptr(), nnz, stream)
         torch.cuda.synchronize(dev)  # the candidate band and the index go when this returns
         return bin1, bin2, count
+
+    def dot_lambda_table(self, interval_id, w, p, min_diag=2, factor=1, first_bin=0, stream=None):
+        """The table the lambda chunks are formed with, float64 [4, nrows]: e[d] / X_k[d], pixels.dot_scales with
+        folds of 1, so that O_k times it is the locally adjusted expected count of the pixel"""
+        return self.dot_table(interval_id, w, p, (1.0, 1.0, 1.0, 1.0), min_diag, factor, first_bin, stream)[0]
+
+    def dot_histogram(self, interval_id, w=5, p=2, edges=None, n_obs=None, min_diag=2, factor=1, first_bin=0,
+                      stream=None):
+        """The lambda-chunk histogram of the interval, numpy uint64 [4, len(edges) + 1, n_obs], counted on the
+        device (pixels.dot_hist): [k][c][o] is the number of valid pixels whose locally adjusted expected count
+        for neighbourhood k, e[d] * O_k / X_k, lies in chunk c = (edges[c - 1], edges[c]] and whose count is o;
+        the last bin holds every count >= n_obs - 1.  `edges` None: HiCCUPS' (pixels.dot_lambda_edges); `n_obs`
+        None: pixels.MAX_DOT_OBS.  The histograms of several intervals add up to the table
+        pixels.dot_thresholds wants."""
+        from . import pixels
+
+        lam = self.dot_lambda_table(interval_id, w, p, min_diag, factor, first_bin, stream)
+        d_band, _, nrows, ncols = self.outputs(interval_id)
+        return pixels.extractor(self.device).dot_hist(d_band, nrows, ncols, w, p, min_diag, lam, edges,
+                                                      pixels.MAX_DOT_OBS if n_obs is None else n_obs, stream, factor,
+                                                      first_bin)
+
+    def dot_histogram_tensor(self, interval_id, w=5, p=2, edges=None, n_obs=None, min_diag=2, factor=1, first_bin=0,
+                             stream=None, into=None):
+        """dot_histogram() as a torch int64 tensor [4, len(edges) + 1, n_obs] on the simulator's device, ADDED to
+        `into` (a contiguous tensor of that shape there; None: a new one of zeros), which is returned: the
+        intervals of a genome accumulate into one table and only the diagonal sums cross to the host.  The words
+        hold the uint64 counts bit for bit."""
+        import torch
+
+        from . import pixels
+
+        n_edges = pixels.DOT_LAMBDA_CHUNKS if edges is None else len(edges)
+        n_obs = pixels.MAX_DOT_OBS if n_obs is None else int(n_obs)
+        dev = torch.device("cuda", self.device)
+        if into is None:
+            into = torch.zeros((4, n_edges + 1, n_obs), dtype=torch.int64, device=dev)
+        elif (tuple(into.shape) != (4, n_edges + 1, n_obs) or into.dtype != torch.int64 or into.device != dev
+              or not into.is_contiguous()):
+            raise ValueError(f"dot_histogram_tensor: `into` is not a contiguous int64 tensor of shape "
+                             f"{(4, n_edges + 1, n_obs)} on {dev}")
+        lam = self.dot_lambda_table(interval_id, w, p, min_diag, factor, first_bin, stream)
+        d_band, nrows, ncols, keep = self._band(interval_id, factor, first_bin, stream)
+        pixels.extractor(self.device).dot_hist_into(d_band, nrows, ncols, w, p, min_diag, lam, edges, n_obs,
+                                                    into.data_ptr(), stream)
+        if keep is not None:  # the scratch band goes when this returns
+            torch.cuda.synchronize(dev)
+        return into
+
+    def dots_fdr(self, interval_ids, w=5, p=2, fdr=0.1, min_count=1, folds=None, min_diag=2, factor=1, first_bins=None,
+                 edges=None, n_obs=None, stream=None):
+        """The statistical test of HiCCUPS over the intervals `interval_ids` as one genome: their lambda-chunk
+        histograms are added on the device, pixels.dot_thresholds turns the table into the count thresholds at
+        the false discovery rate `fdr`, and every interval's candidates are found against them, with the fold
+        test of dots() still on.  Returns (thresholds, {interval_id: (bin1, bin2, count, expected)}).
+        `first_bins`: the first_bin of every interval at `factor` > 1 (None: 0)."""
+        from . import pixels
+
+        ids = list(interval_ids)
+        firsts = [0] * len(ids) if first_bins is None else [int(f) for f in first_bins]
+        if len(firsts) != len(ids):
+            raise ValueError(f"dots_fdr: {len(firsts)} first bins for {len(ids)} intervals")
+        e = pixels.dot_lambda_edges() if edges is None else np.asarray(edges, dtype=np.float64)
+        table = None
+        for iid, first in zip(ids, firsts):
+            table = self.dot_histogram_tensor(iid, w, p, e, n_obs, min_diag, factor, first, stream, into=table)
+        if table is None:
+            return np.zeros((4, len(e) + 1), dtype=np.uint32), {}
+        import torch
+
+        torch.cuda.synchronize(table.device)
+        thresholds = pixels.dot_thresholds(table.cpu().numpy().view(np.uint64), e, fdr)
+        return thresholds, {iid: self.dots(iid, w, p, min_count, folds, min_diag, factor, first, stream, thresholds, e)
+                            for iid, first in zip(ids, firsts)}
 
     def dot_sums_tensor(self, interval_id, w, p, min_diag=2, factor=1, first_bin=0, stream=None):
         """The four neighbourhood sums of every pixel of the interval as one torch int64 tensor

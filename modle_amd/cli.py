@@ -28,6 +28,11 @@ widest the band allows with that smoothing), --scc-ignore-diags N (the first dia
 excluded main diagonal) and --scc-include-zeros (a diagonal counts all its pixels, not only those that are
 non-zero in either matrix).  HiCRep compares at equal depth: sample the deeper matrix first (--subsample-to).
 The score is the one pixels.scc_scores states, modelled on the Python package `hicrep`, not a run of it.
+With --dots --dots-fdr Q (0 < Q < 1) the dots also pass the statistical test of HiCCUPS: every pixel is binned by
+its locally adjusted expected count into --dots-lambda-chunks N (1 to 63, default 40) logarithmic chunks, the
+counts of every chunk are histogrammed over all intervals on the GPU, a Poisson tail under the Benjamini-Hochberg
+rule at the rate Q gives every chunk a count threshold (`<prefix>_dots_thresholds.tsv`), and a dot must clear the
+threshold of its chunk for all four neighbourhoods; the fold test of --dots-folds stays on.
 Everything heavy is native: parsing and
 task generation in libmodle_hip.so (host), the simulation on the MI355X (one process per GPU;
 under torch.distributed.run the cells are sharded over the ranks and the matrices are summed
@@ -193,6 +198,10 @@ def dots_path(prefix):
     return prefix + "_dots.bedpe"
 
 
+def dots_thresholds_path(prefix):
+    return prefix + "_dots_thresholds.tsv"
+
+
 def pileup_path(prefix):
     return prefix + "_pileup.tsv"
 
@@ -316,6 +325,10 @@ def add_analysis_arguments(io):
     io.add_argument("--scc-max-distance", type=genomic_distance, default=None, metavar="D", help=argparse.SUPPRESS)
     io.add_argument("--scc-ignore-diags", type=int, default=None, metavar="N", help=argparse.SUPPRESS)
     io.add_argument("--scc-include-zeros", action="store_true", default=None, help=argparse.SUPPRESS)
+    # The statistical test of the dot calling (<prefix>_dots_thresholds.tsv; the module's text describes the
+    # two options), kept out of the generated help likewise
+    io.add_argument("--dots-fdr", type=float, default=None, metavar="Q", help=argparse.SUPPRESS)
+    io.add_argument("--dots-lambda-chunks", type=int, default=None, metavar="N", help=argparse.SUPPRESS)
 
 
 def build_parser():
@@ -482,8 +495,10 @@ Outputs = collections.namedtuple("Outputs", "cooler bigwig dense state_log expec
 # windows in base pairs as given and the diagonals left out
 Insulation = collections.namedtuple("Insulation", "path resolution windows min_diag")
 # what --dots asks for: the file (None with --skip-output), the bin size, window, peak and cluster radius
-# in base pairs, the smallest count, the four folds and the diagonals no window may reach below
-Dots = collections.namedtuple("Dots", "path resolution window peak min_count folds min_diag radius")
+# in base pairs, the smallest count, the four folds and the diagonals no window may reach below; and of
+# --dots-fdr the rate (None: the fold test alone), the number of lambda-chunk edges and the file of the thresholds
+Dots = collections.namedtuple("Dots", "path resolution window peak min_count folds min_diag radius fdr chunks "
+                                      "thresholds_path", defaults=(None, pixels.DOT_LAMBDA_CHUNKS, None))
 # what --pileup-at asks for: the file (None with --skip-output), the bin size, the flank and the corner of
 # the APA scores in base pairs, and the sources in the order given (`dots`, `barriers` or a BEDPE path)
 Pileup = collections.namedtuple("Pileup", "path resolution flank corner sources")
@@ -588,7 +603,8 @@ def dots_options(a, cfg):
     is not below the window, a window above 20 bins."""
     given = (("--dots-resolution", a.dots_resolution), ("--dots-window", a.dots_window), ("--dots-peak", a.dots_peak),
              ("--dots-min-count", a.dots_min_count), ("--dots-folds", a.dots_folds),
-             ("--dots-ignore-diags", a.dots_ignore_diags), ("--dots-cluster-radius", a.dots_cluster_radius))
+             ("--dots-ignore-diags", a.dots_ignore_diags), ("--dots-cluster-radius", a.dots_cluster_radius),
+             ("--dots-fdr", a.dots_fdr), ("--dots-lambda-chunks", a.dots_lambda_chunks))
     if not a.dots:
         _needs("--dots", given)
         return None
@@ -612,7 +628,16 @@ def dots_options(a, cfg):
     if window // res > MAX_DOT_WINDOW_BINS:
         raise SystemExit(f"--dots-window: {window} is {window // res} bins of {res}: at most {MAX_DOT_WINDOW_BINS}")
     folds = list(DOT_FOLDS if a.dots_folds is None else a.dots_folds)
-    return Dots(_file(a, dots_path), res, window, peak, min_count, folds, min_diag, radius)
+    if a.dots_fdr is None:
+        _needs("--dots-fdr", (("--dots-lambda-chunks", a.dots_lambda_chunks),))
+        return Dots(_file(a, dots_path), res, window, peak, min_count, folds, min_diag, radius)
+    if not 0.0 < a.dots_fdr < 1.0:  # (false for NaN)
+        raise SystemExit(f"--dots-fdr: {a.dots_fdr} is not in (0, 1)")
+    chunks = pixels.DOT_LAMBDA_CHUNKS if a.dots_lambda_chunks is None else a.dots_lambda_chunks
+    if not 1 <= chunks <= pixels.MAX_DOT_EDGES:
+        raise SystemExit(f"--dots-lambda-chunks: {chunks} is not in [1, {pixels.MAX_DOT_EDGES}]")
+    return Dots(_file(a, dots_path), res, window, peak, min_count, folds, min_diag, radius, a.dots_fdr, chunks,
+                _file(a, dots_thresholds_path))
 
 
 def stripes_options(a, cfg):
@@ -739,6 +764,7 @@ def preflight(a, cfg):
         os.makedirs(os.path.dirname(os.path.abspath(cool_path)), exist_ok=True)
         planned = [outputs.cooler, outputs.bigwig, outputs.dense, outputs.expected, outputs.coverage]
         planned += [r.path for r in (ins, dots, pile, sub) if r is not None]
+        planned += [dots.thresholds_path] if dots is not None else []
         planned += [sub.rest_path] if sub is not None and sub.split else []
         planned += [cmp_.path] if cmp_ is not None else []
         planned += [scc.path] if scc is not None else []

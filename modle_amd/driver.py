@@ -690,17 +690,96 @@ def write_dots(path, plan, base, resolution, dots):
 
 
 @_needs_matrix
-def _interval_dots(sim, plan, ids, w, p, min_count, folds, min_diag, radius, k, factor, first_bin):
+def _interval_dots(sim, plan, ids, w, p, min_count, folds, min_diag, radius, k, factor, first_bin, fdr=None):
     """write_dots' callback: the candidates found on the device in the matrix where it lies (with several
     ranks: the reduced tensor) for `w`, `p`, `radius` in bins, verified (check_dots) and thinned to local
-    maxima (api.cluster_dots)"""
+    maxima (api.cluster_dots).  `fdr`: None, or (thresholds, edges) of dot_thresholds_of_plan, which the
+    candidates must clear as well."""
+    more = {} if fdr is None else {"thresholds": fdr[0], "edges": fdr[1]}
     bin1, bin2, count, expected = sim.dots(ids[k], w=w, p=p, min_count=min_count, folds=folds, min_diag=min_diag,
-                                           factor=factor, first_bin=first_bin)
+                                           factor=factor, first_bin=first_bin, **more)
     entry = plan[k]
     nr, nc = insulation_shape(entry["nrows"], entry["ncols"], first_bin, factor)
     check_dots(interval_name(entry["interval"]), nr, nc, w, min_diag, min_count, bin1, bin2, count)
     keep = api.cluster_dots(bin1, bin2, count, radius)
     return bin1[keep], bin2[keep], count[keep], expected[keep]
+
+
+DOT_NEIGHBOURHOODS = ("donut", "lower_left", "horizontal", "vertical")
+
+
+def dot_valid_pixels(nrows, ncols, w, min_diag):
+    """the number of valid pixels of a band for dots with a window of `w` bins (include/modle_pixels.h): on
+    diagonal d = 2 w + min_diag .. nrows - 1 - 2 w the bins j with j - d >= w and j + w < ncols"""
+    w = int(w)
+    return sum(max(0, int(ncols) - 2 * w - d) for d in range(2 * w + int(min_diag), int(nrows) - 2 * w))
+
+
+def check_dot_hist(hist, n_valid):
+    """What the lambda-chunk histogram of a plan (uint64 [4, n_chunks, n_obs], api.BandAnalyses.dot_histogram
+    summed over the entries) must satisfy before thresholds are taken from it, in exact integers: for every
+    neighbourhood the table sums to `n_valid`, the valid pixels of the plan, and summed over the chunks it is the
+    same vector of counts for all four.  RuntimeError when it does not hold."""
+    h = np.asarray(hist)
+    if h.ndim != 3 or h.shape[0] != 4:
+        raise RuntimeError(f"the dot histogram has shape {h.shape}, not (4, chunks, counts)")
+    by_count = [[int(x) for x in h[k].astype(np.uint64).sum(axis=0, dtype=np.uint64)] for k in range(4)]
+    for k, name in enumerate(DOT_NEIGHBOURHOODS):
+        if sum(by_count[k]) != int(n_valid):
+            raise RuntimeError(f"the dot histogram of the {name} neighbourhood holds {sum(by_count[k])} pixels, the "
+                               f"plan has {int(n_valid)} valid ones")
+        if by_count[k] != by_count[0]:
+            o = next(o for o in range(h.shape[2]) if by_count[k][o] != by_count[0][o])
+            raise RuntimeError(f"the dot histogram of the {name} neighbourhood holds {by_count[k][o]} pixels with "
+                               f"count {o}, that of the {DOT_NEIGHBOURHOODS[0]} neighbourhood {by_count[0][o]}")
+
+
+def dot_thresholds_header():
+    """the header line of <prefix>_dots_thresholds.tsv"""
+    return "resolution\tneighbourhood\tchunk\tupper_edge\tpixels\tthreshold\n"
+
+
+def dot_thresholds_lines(resolution, edges, hist, thresholds):
+    """the rows of <prefix>_dots_thresholds.tsv: per neighbourhood and lambda chunk the bin size, the
+    neighbourhood's name, the chunk, the repr of its upper edge (inf: the top chunk), its pixels and its count
+    threshold (0: never)"""
+    uppers = [float(e) for e in edges] + [float("inf")]
+    return [f"{int(resolution)}\t{name}\t{c}\t{uppers[c]!r}\t{int(np.asarray(hist[k][c], dtype=np.uint64).sum(dtype=np.uint64))}\t"
+            f"{int(thresholds[k][c])}\n" for k, name in enumerate(DOT_NEIGHBOURHOODS) for c in range(len(uppers))]
+
+
+def dot_thresholds_of_plan(sim, plan, ids, base, resolution, w, p, min_diag, fdr, chunks, log):
+    """The statistical test's first pass over every entry of the plan that has a matrix, at the bin size
+    `resolution`: their lambda-chunk histograms added into one table on the device (with several ranks: of the
+    reduced tensors), n_obs = min(the largest count of any band + 2, 16384); check_dot_hist; then
+    pixels.dot_thresholds at the rate `fdr`.  Returns (thresholds, edges, the table); a chunk with pixels and no
+    threshold is named in the log."""
+    from . import pixels
+
+    edges = pixels.dot_lambda_edges(chunks)
+    bands = [(ids[k], first_bin, factor, shape) for k, _, first_bin, factor, shape in plan_bands(plan, base, resolution)
+             if ids[k] is not None]
+    largest = max((int(sim.contact_max(iid, factor, first_bin)) for iid, first_bin, factor, _ in bands), default=0)
+    n_obs = min(largest + 2, pixels.MAX_DOT_OBS)
+    table, n_valid = None, 0
+    for iid, first_bin, factor, (nr, nc) in bands:
+        table = sim.dot_histogram_tensor(iid, w, p, edges, n_obs, min_diag, factor, first_bin, into=table)
+        n_valid += dot_valid_pixels(nr, nc, w, min_diag)
+    if table is None:
+        hist = np.zeros((4, len(edges) + 1, n_obs), dtype=np.uint64)
+    else:
+        import torch
+
+        torch.cuda.synchronize(table.device)
+        hist = table.cpu().numpy().view(np.uint64)
+    check_dot_hist(hist, n_valid)
+    thresholds = pixels.dot_thresholds(hist, edges, fdr)
+    for k, name in enumerate(DOT_NEIGHBOURHOODS):
+        never = [c for c in range(len(edges)) if thresholds[k][c] == 0 and hist[k][c].any()]
+        if never:
+            log(f"--dots-fdr: the {name} neighbourhood has no threshold up to a count of {n_obs - 1} in the lambda "
+                f"chunks {', '.join(map(str, never))}: no dot is called there")
+    return thresholds, edges, hist
 
 
 def read_bedpe(path):
@@ -1226,9 +1305,19 @@ def dots_file(sim, cfg, plan, ids, sums, marginals, log, dots):
     """<prefix>_dots.bedpe of the cli.Dots `dots`; returns write_dots' callback, which keeps the dots per entry:
     a pileup at the dots reads them again"""
     res = int(dots.resolution)
-    interval_dots = functools.lru_cache(maxsize=None)(
-        functools.partial(_interval_dots, sim, plan, ids, int(dots.window) // res, int(dots.peak) // res,
-                          int(dots.min_count), list(dots.folds), int(dots.min_diag), int(dots.radius) // res))
+    each = functools.partial(_interval_dots, sim, plan, ids, int(dots.window) // res, int(dots.peak) // res,
+                             int(dots.min_count), list(dots.folds), int(dots.min_diag), int(dots.radius) // res)
+    if getattr(dots, "fdr", None) is not None:
+        # the statistical test: one histogram over the whole plan, its thresholds, then the candidates per entry
+        thresholds, edges, hist = dot_thresholds_of_plan(sim, plan, ids, int(cfg.bin_size), res, int(dots.window) // res,
+                                                         int(dots.peak) // res, int(dots.min_diag), float(dots.fdr),
+                                                         int(dots.chunks), log)
+        with open(dots.thresholds_path, "w") as fh:
+            fh.write(dot_thresholds_header())
+            fh.writelines(dot_thresholds_lines(res, edges, hist, thresholds))
+        log(f"written {dots.thresholds_path}")
+        each = functools.partial(each, fdr=(thresholds, edges))
+    interval_dots = functools.lru_cache(maxsize=None)(each)
     write_dots(dots.path, plan, int(cfg.bin_size), res, interval_dots)
     log(f"written {dots.path}")
     return interval_dots

@@ -2,7 +2,8 @@
 built by `make -C modle_amd/pixels`): the non-zero pixels of a band matrix that lies in device
 memory, in cooler order, found on the GPU; the band at a multiple of its bin size; square regions
 of it as dense matrices; its marginals, the sums per diagonal and per bin; its insulation sums
-over sliding diamond windows; its dots, the pixels enriched over their HiCCUPS neighbourhoods;
+over sliding diamond windows; its dots, the pixels enriched over their HiCCUPS neighbourhoods, by fold and by
+the statistical test (the lambda-chunk histogram counted on the GPU, dot_thresholds, the threshold decision);
 its pileups, the windows around anchor pairs summed into one; and its random sampling, every contact
 kept with one probability by a generator keyed by the pixel's coordinates; the way back, sorted pixels
 checked and scattered into a band on the GPU; and two bands compared stripe by stripe, the integer sums of
@@ -36,13 +37,17 @@ STRIPE_METRICS = ("pearson", "spearman", "rmse", "eucl_dist")  # what stripe_sco
 SCC_ROWS = 11  # MODLE_PIXELS_SCC_ROWS: n and the five 128-bit sums of a stratum
 MAX_SCC_SMOOTH = 20  # MODLE_PIXELS_MAX_SCC_SMOOTH: the largest half-width of the smoothing box
 DOT_FOLDS = (1.75, 1.75, 1.5, 1.5)  # HiCCUPS' thresholds: donut, lower-left, horizontal, vertical
+MAX_DOT_EDGES, MAX_DOT_OBS = 63, 16384  # MODLE_PIXELS_MAX_DOT_EDGES, MODLE_PIXELS_MAX_DOT_OBS
+DOT_LAMBDA_CHUNKS = 40  # HiCCUPS' number of lambda-chunk edges (dot_lambda_edges)
 EXPORTS = ["modle_pixels_create", "modle_pixels_destroy", "modle_pixels_count", "modle_pixels_extract",
            "modle_pixels_to_host", "modle_pixels_coarse_shape", "modle_pixels_coarsen",
            "modle_pixels_coarse_to_host", "modle_pixels_tiles_fit", "modle_pixels_dense_tiles",
            "modle_pixels_dense_to_host", "modle_pixels_marginals", "modle_pixels_marginals_to_host",
            "modle_pixels_coarse_marginals_to_host", "modle_pixels_insulation_n_valid", "modle_pixels_insulation",
            "modle_pixels_insulation_to_host", "modle_pixels_coarse_insulation_to_host", "modle_pixels_dots",
-           "modle_pixels_dots_to_host", "modle_pixels_coarse_dots_to_host", "modle_pixels_pileup_accepts",
+           "modle_pixels_dots_to_host", "modle_pixels_coarse_dots_to_host", "modle_pixels_dot_hist",
+           "modle_pixels_dot_hist_to_host", "modle_pixels_coarse_dot_hist_to_host", "modle_pixels_dots_fdr",
+           "modle_pixels_dots_fdr_to_host", "modle_pixels_coarse_dots_fdr_to_host", "modle_pixels_pileup_accepts",
            "modle_pixels_pileup", "modle_pixels_pileup_to_host",
            "modle_pixels_coarse_pileup_to_host", "modle_pixels_sample_pixels", "modle_pixels_sample",
            "modle_pixels_sample_to_host", "modle_pixels_band_classify", "modle_pixels_band_check",
@@ -138,6 +143,17 @@ def lib():
         lb.modle_pixels_dots.argtypes = shape + dots + [C.c_void_p, C.c_void_p, C.c_void_p] + err
         lb.modle_pixels_dots_to_host.argtypes = shape + dots + pix
         lb.modle_pixels_coarse_dots_to_host.argtypes = shape + [C.c_uint64] * 2 + dots + pix
+        f64p = C.POINTER(C.c_double)
+        chunks = [f64p, f64p, C.c_uint64]  # lam, edges (host tables), n_edges
+        hist = [C.c_uint64] * 3 + chunks + [C.c_uint64]  # w, p, min_diag, the tables, n_obs
+        fdr = [C.c_uint64] * 4 + chunks + [C.POINTER(C.c_uint32), f64p]  # w .. min_count, the tables, thr, scale
+        lb.modle_pixels_dot_hist.argtypes = shape + hist + [C.c_void_p, C.c_void_p] + err
+        lb.modle_pixels_dot_hist_to_host.argtypes = shape + hist + [C.POINTER(C.c_void_p), C.c_void_p] + err
+        lb.modle_pixels_coarse_dot_hist_to_host.argtypes = shape + [C.c_uint64] * 2 + hist + \
+            [C.POINTER(C.c_void_p), C.c_void_p] + err
+        lb.modle_pixels_dots_fdr.argtypes = shape + fdr + [C.c_void_p, C.c_void_p] + err
+        lb.modle_pixels_dots_fdr_to_host.argtypes = shape + fdr + pix
+        lb.modle_pixels_coarse_dots_fdr_to_host.argtypes = shape + [C.c_uint64] * 2 + fdr + pix
         i64p = C.POINTER(C.c_int64)
         piled = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p] + err  # pile, n_used, stream
         lb.modle_pixels_pileup_accepts.argtypes = [C.c_uint64] * 3 + [C.c_int64, i64p, i64p, C.c_uint64,
@@ -329,6 +345,81 @@ def _scale_table(scale, nrows):
     if t.ndim != 2 or t.shape[0] != 4 or (nrows is not None and t.shape[1] != int(nrows)):
         raise PixelsError(ERR_ARG, f"dots: the scale table has shape {t.shape}, not (4, nrows)")
     return t, t.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def dot_lambda_edges(n=DOT_LAMBDA_CHUNKS):
+    """HiCCUPS' lambda-chunk edges, numpy float64[n]: 2 ** (i / 3), i = 0 .. n - 1 (n = 40: up to 8192).  Chunk c
+    is (edges[c - 1], edges[c]]; the chunk above the last edge never calls."""
+    n = int(n)
+    if not 1 <= n <= MAX_DOT_EDGES:
+        raise ValueError(f"dots: {n} lambda chunks are not in [1, {MAX_DOT_EDGES}]")
+    return np.float64(2.0) ** (np.arange(n, dtype=np.float64) / np.float64(3.0))
+
+
+def _edge_table(edges):
+    """(the float64 array to keep alive, its ctypes pointer, n_edges) of the lambda-chunk edges; None: HiCCUPS'"""
+    e = dot_lambda_edges() if edges is None else np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+    return e, e.ctypes.data_as(C.POINTER(C.c_double)), len(e)
+
+
+def _thr_table(thresholds, n_edges):
+    """(the uint32 [4, n_edges + 1] array to keep alive, its ctypes pointer) of a table of dot_thresholds' shape"""
+    raw = np.asarray(thresholds)
+    if raw.shape != (4, n_edges + 1) or raw.dtype.kind not in "iu" or (raw < 0).any() or (raw > 0xFFFFFFFF).any():
+        raise PixelsError(ERR_ARG, f"dots: the threshold table has shape {raw.shape} and type {raw.dtype}, not "
+                                   f"(4, {n_edges + 1}) of uint32 values")
+    t = np.ascontiguousarray(raw, dtype=np.uint32)
+    return t, t.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+def poisson_tail(mean, n):
+    """P(Poisson(mean) >= t) for t = 0 .. n - 1, numpy float64[n], for a finite mean > 0.  The probabilities are
+    formed relative to the one at the mode, by the recurrence p(k + 1) = p(k) * mean / (k + 1) upwards and downwards
+    from it, summed from the far tail towards it, the small terms first, and divided by their total: nothing
+    depends on exp(-mean), which underflows beyond 745, and only a term below 1e-308 of the mode's is lost."""
+    mean, n = float(mean), int(n)
+    if not (mean > 0 and math.isfinite(mean)) or n < 1:
+        raise ValueError(f"dots: the Poisson tail needs a finite mean > 0 and n >= 1, not {mean!r}, {n}")
+    mode = int(mean)
+    top = max(n, mode + int(40.0 * math.sqrt(mean) + 64.0))  # beyond it the terms add nothing to a double
+    rel = np.ones(top + 1, dtype=np.float64)
+    with np.errstate(under="ignore"):
+        rel[mode + 1:] = np.cumprod(mean / np.arange(mode + 1, top + 1, dtype=np.float64))
+        rel[:mode] = np.cumprod(np.arange(mode, 0, -1, dtype=np.float64) / mean)[::-1]
+    tail = np.cumsum(rel[::-1])[::-1]
+    return tail[:n] / tail[0]
+
+
+def dot_thresholds(hist, edges, fdr):
+    """The count thresholds of the lambda chunks, numpy uint32 [4, n_chunks], from the histograms of
+    modle_pixels_dot_hist (uint64 [4, n_chunks, n_obs]): for neighbourhood k and chunk c below the top one, with
+    L = edges[c], N the chunk's pixels and tail[t] those with a count >= t, the smallest t in 1 .. n_obs - 1 with
+    tail[t] > 0 and N * P(Poisson(L) >= t) <= fdr * tail[t] -- the Benjamini-Hochberg rule against the Poisson
+    law of the chunk's upper edge (Rao et al. 2014) -- and 0, "never", where there is none and for the top chunk.
+    The last bin holds every count >= n_obs - 1, so tail[n_obs - 1] and with it every threshold is exact."""
+    h = np.asarray(hist)
+    e = np.asarray(edges, dtype=np.float64).reshape(-1)
+    fdr = float(fdr)
+    if h.ndim != 3 or h.shape[0] != 4 or h.shape[1] != len(e) + 1 or h.shape[2] < 2 or h.dtype.kind not in "iu":
+        raise ValueError(f"dots: a histogram of shape {h.shape} is not (4, {len(e) + 1}, n_obs >= 2) of integers")
+    if not 0.0 < fdr < 1.0:
+        raise ValueError(f"dots: the false discovery rate {fdr!r} is not in (0, 1)")
+    if len(e) < 1 or not np.isfinite(e).all() or not (e > 0).all() or not (np.diff(e) > 0).all():
+        raise ValueError("dots: the lambda-chunk edges are not finite, positive and strictly increasing")
+    n_obs = h.shape[2]
+    out = np.zeros((4, len(e) + 1), dtype=np.uint32)
+    for c in range(len(e)):
+        if not h[:, c].any():
+            continue
+        q = poisson_tail(e[c], n_obs)
+        for k in range(4):
+            above = np.cumsum(h[k, c][::-1].astype(np.uint64))[::-1]  # above[t]: the pixels with a count >= t
+            n = float(int(above[0]))
+            met = (above > 0) & (n * q <= fdr * above.astype(np.float64))
+            met[0] = False
+            if met.any():
+                out[k, c] = int(np.argmax(met))
+    return out
 
 
 def _anchors(bin1, bin2):
@@ -762,6 +853,69 @@ class Extractor:
         float64 [4, nrows'] of coarse_shape and `bin_offset` counts coarse bins"""
         return self.dots(d_band, nrows, ncols, w, p, min_diag, min_count, scale, bin_offset, stream, factor,
                          first_bin, True)
+
+    def dot_hist_into(self, d_band, nrows, ncols, w, p, min_diag, lam, edges, n_obs, d_hist, stream=None):
+        """enqueues the lambda-chunk histogram (modle_pixels_dot_hist): ADDS, for every valid pixel and every
+        neighbourhood k, one to the caller-owned device array `d_hist` (uint64[4][len(edges) + 1][n_obs], 8-byte
+        aligned, zeroed by the caller before the first band) at [k][chunk of O_k * lam[k][d]][min(count,
+        n_obs - 1)].  `lam`: float64 [4, nrows] (dot_scales with folds of 1); `edges`: None for HiCCUPS'."""
+        keep, ptr = _scale_table(lam, nrows)
+        e, eptr, n_edges = _edge_table(edges)
+        _call(self._L.modle_pixels_dot_hist, self._h, d_band, int(nrows), int(ncols), int(w), int(p), int(min_diag),
+              ptr, eptr, n_edges, int(n_obs), d_hist, _stream_ptr(stream))
+        del keep, e
+
+    def dot_hist(self, d_band, nrows, ncols, w, p, min_diag, lam, edges, n_obs, stream=None, factor=1, first_bin=0,
+                 coarse=None):
+        """the lambda-chunk histogram of the band alone as a numpy uint64 [4, len(edges) + 1, n_obs] the caller
+        owns (modle_pixels_dot_hist_to_host)"""
+        fn, band, shape = self._form("dot_hist_", d_band, nrows, ncols, factor, first_bin, coarse)
+        keep, ptr = _scale_table(lam, shape()[0])
+        e, eptr, n_edges = _edge_table(edges)
+        out = C.c_void_p()
+        _call(fn, self._h, *band, int(w), int(p), int(min_diag), ptr, eptr, n_edges, int(n_obs), C.byref(out),
+              _stream_ptr(stream))
+        del keep, e
+        return _host_array(out.value, 4 * (n_edges + 1) * int(n_obs), np.uint64).reshape(4, n_edges + 1, int(n_obs))
+
+    def coarse_dot_hist(self, d_band, nrows, ncols, factor, first_bin, w, p, min_diag, lam, edges, n_obs,
+                        stream=None):
+        """`dot_hist` of the band at `factor` times its bin size, coarsened on the device
+        (modle_pixels_coarse_dot_hist_to_host): `w`, `p`, `min_diag` count coarse bins, `lam` is float64
+        [4, nrows'] of coarse_shape"""
+        return self.dot_hist(d_band, nrows, ncols, w, p, min_diag, lam, edges, n_obs, stream, factor, first_bin, True)
+
+    def dots_fdr_into(self, d_band, nrows, ncols, w, p, min_diag, min_count, lam, edges, thresholds, scale, d_cand,
+                      stream=None):
+        """enqueues the threshold decision (modle_pixels_dots_fdr) into the caller-owned device array `d_cand`
+        (uint32[nrows * ncols + 1], every word written): the count where a valid pixel has count >= min_count,
+        clears the non-zero threshold `thresholds[k][chunk of O_k * lam[k][d]]` (uint32 [4, len(edges) + 1],
+        dot_thresholds) for every k and, with a `scale` table (dot_scales; or None), passes the fold test too."""
+        keep, ptr = _scale_table(lam, nrows)
+        e, eptr, n_edges = _edge_table(edges)
+        t, tptr = _thr_table(thresholds, n_edges)
+        keep_s, sptr = _scale_table(scale, nrows)
+        _call(self._L.modle_pixels_dots_fdr, self._h, d_band, int(nrows), int(ncols), int(w), int(p), int(min_diag),
+              int(min_count), ptr, eptr, n_edges, tptr, sptr, d_cand, _stream_ptr(stream))
+        del keep, e, t, keep_s
+
+    def dots_fdr(self, d_band, nrows, ncols, w, p, min_diag, min_count, lam, edges, thresholds, scale=None,
+                 bin_offset=0, stream=None, factor=1, first_bin=0, coarse=None):
+        """the candidates of the threshold decision as Pixels (modle_pixels_dots_fdr_to_host)"""
+        fn, band, shape = self._form("dots_fdr_", d_band, nrows, ncols, factor, first_bin, coarse)
+        keep, ptr = _scale_table(lam, shape()[0])
+        e, eptr, n_edges = _edge_table(edges)
+        t, tptr = _thr_table(thresholds, n_edges)
+        keep_s, sptr = _scale_table(scale, shape()[0])
+        return self._to_host(fn, shape, *band, int(w), int(p), int(min_diag), int(min_count), ptr, eptr, n_edges, tptr,
+                             sptr, int(bin_offset), stream=stream)
+
+    def coarse_dots_fdr(self, d_band, nrows, ncols, factor, first_bin, w, p, min_diag, min_count, lam, edges,
+                        thresholds, scale=None, bin_offset=0, stream=None):
+        """`dots_fdr` of the band at `factor` times its bin size, coarsened on the device
+        (modle_pixels_coarse_dots_fdr_to_host)"""
+        return self.dots_fdr(d_band, nrows, ncols, w, p, min_diag, min_count, lam, edges, thresholds, scale,
+                             bin_offset, stream, factor, first_bin, True)
 
     def pileup_into(self, d_band, nrows, ncols, flank, d_bin1, d_bin2, n, d_pile, d_n_used=None, bin_offset=0,
                     stream=None):

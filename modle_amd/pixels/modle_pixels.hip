@@ -274,6 +274,7 @@ extern "C" void modle_pixels_destroy(modle_pixels_handle* h) {
   (void)hipFree(h->d_stats);
   (void)hipHostFree(h->h_stats);
   if (h->dot_scale_copied != nullptr) (void)hipEventDestroy(h->dot_scale_copied);
+  if (h->dot_lam_copied != nullptr) (void)hipEventDestroy(h->dot_lam_copied);
   delete h;  // (releases every buffer of the context)
 }
 

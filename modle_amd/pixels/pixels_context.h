@@ -135,6 +135,12 @@ struct modle_pixels_handle {
   GrowBuf<uint32_t> dot_cand;
   GrowBuf<double, true> dot_scale;
   hipEvent_t dot_scale_copied = nullptr;
+  // modle_pixels_dot_hist* / _dots_fdr*: the lambda table (4 rows of nrows doubles), then 64 doubles of
+  // edges, then 4 x 64 words of thresholds, with the event that marks the pinned copy as read; and of
+  // modle_pixels_dot_hist_to_host the table 4 x n_chunks x n_obs (modle_dots.hip)
+  GrowBuf<double, true> dot_lam;
+  hipEvent_t dot_lam_copied = nullptr;
+  GrowBuf<uint64_t, true> dot_hist;
   // modle_pixels_pileup*: the workgroups' partial sums (S * S words each, then their counts), and of the
   // to-host forms the anchors (bin1, then bin2) and the pile with n_used behind it (modle_pileup.hip)
   GrowBuf<uint64_t> pile_partial;
