@@ -1,7 +1,8 @@
 /* modle_pixels.h -- C ABI of the sparse-pixel extraction (modle_amd/libmodle_pixels.so), of the
  * coarsening of a band, of its dense regions, of its marginals, of its insulation sums, of its
- * dot candidates, of its pileups and of its random sampling, of the way back from sorted pixels to
- * a band, and of the comparison of two bands stripe by stripe and diagonal by diagonal (further down).
+ * dot candidates, of its pileups (fixed windows and rescaled ones) and of its random sampling, of the
+ * way back from sorted pixels to a band, and of the comparison of two bands stripe by stripe and diagonal
+ * by diagonal (further down).
  *
  * The simulation leaves every interval as a dense band matrix in device memory
  * (modle_hip_interval_outputs).  A cooler file is made of the non-zero pixels only, sorted by
@@ -459,6 +460,72 @@ int modle_pixels_coarse_pileup_to_host(modle_pixels_handle* h, const uint32_t* d
                                        int64_t bin_offset, const int64_t* bin1, const int64_t* bin2,
                                        uint64_t n, const uint64_t** pile, const uint64_t** n_used,
                                        void* stream, char* err, size_t errlen);
+
+/* ---- Rescaled pileups: windows of different sizes on the diagonal, rescaled to one grid and summed ---
+ *
+ * The average domain (coolpup.py's --rescale; Flyamer et al. 2017).  M is the symmetric matrix of the band
+ * as above.  For a grid side R = `size`, 1 <= R <= MODLE_PIXELS_MAX_RESCALE, and `n` windows
+ * [s_t, e_t) = [start[t] - bin_offset, end[t] - bin_offset) from int64 arrays, window t of width W = e - s
+ * is ACCEPTED when
+ *     0 <= s < e <= ncols,   R <= W,   W <= nrows:
+ * every cell of the W x W square on the diagonal lies in the matrix and in the band, so no word that is no
+ * pixel (left-edge triangle, trailing word) is ever read, and no output cell is empty of source pixels.  The
+ * rule is evaluated without signed overflow for any int64 value and a `bin_offset` of either sign.  With
+ * u(x) = floor(x * R / W) for 0 <= x < W the outputs are
+ *     pile[u][v] = sum over the accepted t, over 0 <= x, y < W with u(x) == u, u(y) == v,
+ *                  of M(s_t + x, s_t + y)                                       uint64[R][R], row-major
+ *     area[u][v] = sum over the accepted t of #{x : u(x) == u} * #{y : u(y) == v}      uint64[R][R]
+ *     n_used     = the number of accepted windows                               uint64[1]
+ * A diagonal pixel counts once and an off-diagonal one in both places, as in the on-diagonal pileup above.
+ * pile / area is the POOLED mean of a cell: every source pixel weighs the same, so large windows weigh more.
+ * It is not coolpup.py's mean of per-snippet interpolations.  Duplicates count as often as they are listed,
+ * the order of the windows is free, and n == 0 or no accepted window gives zeros.  EVERY output word is
+ * written exactly once, with a plain store: the caller does not pre-zero.  The sums are exact 64-bit
+ * integers whatever the order of summation and the launch geometry: the windows are spread over at most
+ * modle_pixels_rescale_groups() workgroups, whose partial sums meet in scratch of the context (grown on
+ * demand).
+ *
+ * MODLE_PIXELS_ERR_ARG, with nothing written, judged from the arguments alone: a null handle or band, null
+ * windows with n > 0, size == 0, size > 128, nrows == 0, nrows > ncols, n >= 2^31,
+ * n * ceil(min(nrows, ncols) / size)^2 >= 2^32 (a cell of a window has at most that many source pixels, each a
+ * word below 2^32: with this bound no sum can wrap), an output that is not 8-byte aligned or overlaps the
+ * band, the windows or another output. */
+#define MODLE_PIXELS_MAX_RESCALE 128
+
+/* The workgroups at most that this build of the library was compiled with (256; a test build lowers it).
+ * No result depends on it.  Host only: no device is needed. */
+uint64_t modle_pixels_rescale_groups(void);
+
+/* accept[t] = 1 when window t is accepted, else 0: the rule above on HOST arrays.  Host only: no device is
+ * needed.  The shapes, sizes and counts modle_pixels_rescale refuses, and a null pointer with n > 0, are
+ * MODLE_PIXELS_ERR_ARG. */
+int modle_pixels_rescale_accepts(uint64_t nrows, uint64_t ncols, uint64_t size, int64_t bin_offset,
+                                 const int64_t* start, const int64_t* end, uint64_t n, uint8_t* accept);
+
+/* Enqueues the sums of the DEVICE windows d_start, d_end (int64[n]) into the device arrays d_pile
+ * (uint64[R * R]), d_area (uint64[R * R]; may be NULL) and d_n_used (uint64[1]; may be NULL) on `stream`;
+ * the call does not wait. */
+int modle_pixels_rescale(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols,
+                         uint64_t size, int64_t bin_offset, const int64_t* d_start, const int64_t* d_end,
+                         uint64_t n, uint64_t* d_pile, uint64_t* d_area, uint64_t* d_n_used, void* stream,
+                         char* err, size_t errlen);
+
+/* The same for HOST windows, which are copied up, into pinned host buffers of the context (grown on demand,
+ * freed by modle_pixels_destroy): *pile and *area (R * R entries each) and *n_used (one) stay valid until
+ * the next call on the context.  Waits for `stream`. */
+int modle_pixels_rescale_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                                 uint64_t ncols, uint64_t size, int64_t bin_offset, const int64_t* start,
+                                 const int64_t* end, uint64_t n, const uint64_t** pile, const uint64_t** area,
+                                 const uint64_t** n_used, void* stream, char* err, size_t errlen);
+
+/* One call at `factor` times the bin size: coarsens into the scratch band of the context (like
+ * modle_pixels_coarse_pileup_to_host), then modle_pixels_rescale_to_host on it.  The windows count coarse
+ * bins, and `size` and the acceptance rule hold against nrows' / ncols' (modle_pixels_coarse_shape). */
+int modle_pixels_coarse_rescale_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                                        uint64_t ncols, uint64_t factor, uint64_t first_bin, uint64_t size,
+                                        int64_t bin_offset, const int64_t* start, const int64_t* end,
+                                        uint64_t n, const uint64_t** pile, const uint64_t** area,
+                                        const uint64_t** n_used, void* stream, char* err, size_t errlen);
 
 /* ---- Random sampling: binomial thinning of the band -----------------------------------------------
  *

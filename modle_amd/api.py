@@ -247,6 +247,116 @@ def apa_scores(pile, corner):
     return out
 
 
+def rescaled_block_edges(width, size):
+    """lo[0 .. size] of a window of `width` bins on a grid of `size`: block u of the rescaled pileup holds the
+    x with floor(x * size / width) == u, that is lo[u] <= x < lo[u + 1], lo[u] = ceil(u * width / size)"""
+    w, r = int(width), int(size)
+    return [-((-u * w) // r) for u in range(r + 1)]
+
+
+def rescaled_area(width_hist, size):
+    """The area of a rescaled pileup (Simulator.rescaled_pileup) in closed form, numpy uint64 [size, size]:
+    the sum over the widths W of width_hist[W] * (the bins of block u) * (the bins of block v)."""
+    r = int(size)
+    area = np.zeros((r, r), dtype=np.uint64)
+    for w, k in enumerate(int(x) for x in np.asarray(width_hist).reshape(-1)):
+        if k != 0:
+            lo = rescaled_block_edges(w, r)
+            n = np.array([lo[u + 1] - lo[u] for u in range(r)], dtype=np.uint64)
+            area += np.uint64(k) * np.outer(n, n)
+    return area
+
+
+def rescaled_expected_counts(width_hist, size):
+    """cnt of rescaled_expected_terms: numpy int64 [size * (size + 1) / 2, D] over the cells u <= v (cell
+    v * (v + 1) / 2 + u) and the distances d < D = the largest width in use (1 without one); cnt[q][d] is the sum
+    over the widths W of width_hist[W] times the number of (x, y), 0 <= x, y < W, x in block u, y in block v, with
+    abs(y - x) == d.  Block u against block v holds max(0, min(x1, y1 - k) - max(x0, y0 - k)) pairs with
+    y - x == k."""
+    hist = [int(x) for x in np.asarray(width_hist).reshape(-1)]
+    r = int(size)
+    used = [w for w, k in enumerate(hist) if k != 0]
+    if r < 1 or (used and used[0] < r):
+        raise ValueError(f"rescaled_expected: a grid of {r} and a width of {used[0] if used else 0}")
+    uu, vv = np.triu_indices(r)
+    q = vv * (vv + 1) // 2 + uu
+    cnt = np.zeros((r * (r + 1) // 2, max(used[-1] if used else 1, 1)), dtype=np.int64)
+    for w in used:
+        lo = np.array(rescaled_block_edges(w, r), dtype=np.int64)
+        x0, x1, y0, y1 = lo[uu], lo[uu + 1], lo[vv], lo[vv + 1]
+        k_lo, k_hi = y0 - x1 + 1, y1 - 1 - x0  # the differences y - x a cell holds
+        for j in range(int((k_hi - k_lo).max()) + 1):  # (within one j every cell is touched once)
+            k = k_lo + j
+            c = np.minimum(x1, y1 - k) - np.maximum(x0, y0 - k)
+            on = (k <= k_hi) & (c > 0)
+            cnt[q[on], np.abs(k[on])] += hist[w] * c[on]
+    return cnt
+
+
+def rescaled_expected_terms(width_hist, diag_sum, ncols, size):
+    """The terms of rescaled_expected: a list of size * size lists (cell (u, v) at u * size + v), each holding
+    float(cnt[u][v][d]) * E[d] for the d with cnt[u][v][d] != 0, ascending in d, with cnt of
+    rescaled_expected_counts (exact integers) and E[d] = float(diag_sum[d]) / float(ncols - d)."""
+    hist = [int(x) for x in np.asarray(width_hist).reshape(-1)]
+    diag = [int(x) for x in np.asarray(diag_sum).reshape(-1)]
+    r, ncols = int(size), int(ncols)
+    used = [w for w, k in enumerate(hist) if k != 0]
+    if ncols < len(diag) or (used and used[-1] > len(diag)):
+        raise ValueError(f"rescaled_expected: widths up to {used[-1] if used else 0}, {len(diag)} diagonals, "
+                         f"{ncols} columns")
+    cnt = rescaled_expected_counts(hist, r)
+    e = [float(s) / float(ncols - d) for d, s in enumerate(diag)]
+    upper = [[float(int(row[d])) * e[d] for d in np.flatnonzero(row)] for row in cnt]
+    return [upper[max(u, v) * (max(u, v) + 1) // 2 + min(u, v)] for u in range(r) for v in range(r)]
+
+
+def rescaled_expected(width_hist, diag_sum, ncols, size):
+    """What the distance-decay curve of the interval expects a rescaled pileup (Simulator.rescaled_pileup) to
+    hold, numpy float64 [size, size]: with E[d] = float(diag_sum[d]) / float(ncols - d) (one division), cell
+    (u, v) is math.fsum of float(cnt[u][v][d]) * E[d] over the d with cnt[u][v][d] != 0, cnt the number of
+    source pixels of the cell at distance d over all accepted windows (rescaled_expected_counts).  fsum is
+    correctly rounded, so the result does not depend on the order of the terms."""
+    r = int(size)
+    terms = rescaled_expected_terms(width_hist, diag_sum, ncols, size)
+    return np.array([math.fsum(t) for t in terms], dtype=np.float64).reshape(r, r)
+
+
+def domain_strength_blocks(size, flank_percent):
+    """(g0, g1) of domain_strength: the domain itself covers the grid rows g0 <= u < g1 of a rescaled pileup
+    whose windows were padded by `flank_percent` of the domain on either side:
+    g0 = ceil(R P / (100 + 2 P)), g1 = floor(R (100 + P) / (100 + 2 P))"""
+    r, p = int(size), int(flank_percent)
+    if r < 1 or p < 0:
+        raise ValueError(f"domain_strength: a grid of {r} and a flank of {p} percent")
+    return -((-r * p) // (100 + 2 * p)), (r * (100 + p)) // (100 + 2 * p)
+
+
+def domain_strength(pile, expected, size, flank_percent):
+    """The strength of the average domain, a float: (obs_within / exp_within) / (obs_between / exp_between).
+    With (g0, g1) of domain_strength_blocks, `within` is the cells g0 <= u <= v < g1 of the rescaled pileup, the
+    domain's own triangle, and `between` the cells with u < g0 <= v < g1 or g0 <= u < g1 <= v, the domain
+    against its two flanks.  The observed sums are Python integers of `pile`, the expected sums math.fsum of
+    `expected` (rescaled_expected).  nan when flank_percent is 0, when a block is empty or when a denominator
+    is 0.  This is the project's own definition, in the spirit of the TAD strength of Flyamer et al. 2017
+    (observed over expected inside the domain against the same between it and its neighbourhood); it is not
+    that paper's formula."""
+    r = int(size)
+    g0, g1 = domain_strength_blocks(r, flank_percent)
+    p, e = np.asarray(pile), np.asarray(expected)
+    if p.shape != (r, r) or e.shape != (r, r):
+        raise ValueError(f"domain_strength: a pile of shape {p.shape}, an expected of shape {e.shape}, a grid of {r}")
+    within = [(u, v) for u in range(g0, g1) for v in range(u, g1)]
+    between = [(u, v) for u in range(0, g0) for v in range(g0, g1)] + \
+              [(u, v) for u in range(g0, g1) for v in range(g1, r)]
+    if int(flank_percent) == 0 or not within or not between:
+        return math.nan
+    ow, ob = sum(int(p[c]) for c in within), sum(int(p[c]) for c in between)
+    ew, eb = math.fsum(float(e[c]) for c in within), math.fsum(float(e[c]) for c in between)
+    if ew == 0.0 or eb == 0.0 or ob == 0:
+        return math.nan
+    return (float(ow) / ew) / (float(ob) / eb)
+
+
 class BandAnalyses:
     """The analyses of a band matrix in device memory, for any owner of bands that has `device` and
     `outputs(id)` -> (device pointer of the band, occupancy pointer or None, nrows, ncols): the Simulator, whose
@@ -614,6 +724,61 @@ class BandAnalyses:
         pixels.pileup_into(d_band, nrows, ncols, flank, bin1.data_ptr() if n else None, bin2.data_ptr() if n else None,
                            n, pile.data_ptr(), n_used.data_ptr(), bin_offset, stream, device=self.device)
         return pile, n_used
+
+    def rescaled_pileup(self, interval_id, start, end, size, factor=1, first_bin=0, bin_offset=0):
+        """The rescaled pileup of the interval over the windows [start[t] - bin_offset, end[t] - bin_offset) on
+        the diagonal, the average domain: (pile, area, n_used, width_hist).  An accepted window [s, e) --
+        0 <= s < e <= ncols and size <= e - s <= nrows (pixels.rescale_accepts) -- of width W is cut into
+        size x size blocks, block u holding the x with floor(x * size / W) == u; pile[u][v], numpy uint64
+        [size, size], is the sum of the symmetric matrix over block u x block v of every accepted window, formed
+        on the device from the band where it lies (pixels.rescale), and area[u][v] the number of source pixels
+        it took.  pile / area is the pooled mean of a cell, in which large windows weigh more: not the mean of
+        per-window interpolations.  n_used is the number of accepted windows and width_hist[W], numpy uint64
+        [nrows + 1], the number of them of width W, which rescaled_expected() wants.  Only the windows and the
+        results cross between host and device.  Call it after wait().  With `factor` > 1 the band is first
+        coarsened on the device (`first_bin` as for pixels()) and the windows count coarse bins."""
+        from . import pixels
+
+        d_band, _, nrows, ncols = self.outputs(interval_id)
+        nr, nc = pixels.band_shape(nrows, ncols, factor, first_bin)
+        pile, area, n_used = pixels.extractor(self.device).rescale(d_band, nrows, ncols, size, start, end, bin_offset,
+                                                                   None, factor, first_bin)
+        s = np.asarray(start, dtype=np.int64).reshape(-1)
+        e = np.asarray(end, dtype=np.int64).reshape(-1)
+        ok = pixels.rescale_accepts(nr, nc, size, s, e, bin_offset)
+        width_hist = np.bincount(e[ok] - s[ok], minlength=nr + 1).astype(np.uint64)
+        return pile, area, n_used, width_hist
+
+    def rescaled_pileup_tensors(self, interval_id, start, end, size, bin_offset=0, stream=None):
+        """(pile, area, n_used) of rescaled_pileup() for windows that are torch int64 tensors on the simulator's
+        device, as three torch int64 tensors, [size, size], [size, size] and [1], on that device, filled there
+        by the kernels: nothing crosses to the host.  The words hold the uint64 sums bit for bit.  The work is
+        enqueued on `stream` (None: the default stream, on which torch orders its own work) and not waited
+        for."""
+        import torch
+
+        from . import pixels
+
+        d_band, _, nrows, ncols = self.outputs(interval_id)
+        dev = torch.device("cuda", self.device)
+        for t in (start, end):
+            if t.dtype != torch.int64 or t.device != dev or t.dim() != 1:
+                raise ValueError("rescaled_pileup_tensors: the windows must be one-dimensional int64 tensors on the "
+                                 "simulator's device")
+        if start.numel() != end.numel():
+            raise ValueError(f"rescaled_pileup_tensors: {start.numel()} starts and {end.numel()} ends")
+        start, end = start.contiguous(), end.contiguous()
+        r = int(size)
+        if not 1 <= r <= pixels.MAX_RESCALE:
+            raise ValueError(f"rescaled_pileup_tensors: a grid of {r} is not in [1, {pixels.MAX_RESCALE}]")
+        pile = torch.empty((r, r), dtype=torch.int64, device=dev)
+        area = torch.empty((r, r), dtype=torch.int64, device=dev)
+        n_used = torch.empty(1, dtype=torch.int64, device=dev)
+        n = start.numel()
+        pixels.rescale_into(d_band, nrows, ncols, r, start.data_ptr() if n else None, end.data_ptr() if n else None,
+                            n, pile.data_ptr(), area.data_ptr(), n_used.data_ptr(), bin_offset, stream,
+                            device=self.device)
+        return pile, area, n_used
 
     def sample_tensors(self, interval_id, frac, seed, salt=0, bin_offset=0, rest=False, stream=None):
         """The interval's matrix at the fraction `frac` of its depth: every contact is kept with

@@ -33,6 +33,13 @@ its locally adjusted expected count into --dots-lambda-chunks N (1 to 63, defaul
 counts of every chunk are histogrammed over all intervals on the GPU, a Poisson tail under the Benjamini-Hochberg
 rule at the rate Q gives every chunk a count threshold (`<prefix>_dots_thresholds.tsv`), and a dot must clear the
 threshold of its chunk for all four neighbourhoods; the fold test of --dots-folds stays on.
+With --domains-at FILE.bed (three columns; may be given several times) `<prefix>_domains.tsv`, the average domain:
+every domain of the file, padded by --domains-flank-percent P (0 to 200, default 100) of its own bins on either
+side, is cut into --domains-size N (1 to 128, default 60) blocks a side, and the blocks of all of them are summed
+on the GPU into one N x N pile with the number of source pixels of every cell, at --domains-resolution R (a
+multiple of -r, coarsened on the GPU; default -r); the file also holds what the distance-decay curve expects of
+every cell and the strength of the average domain (api.domain_strength).  observed / area is the pooled mean of a
+cell, in which large domains weigh more: it is not the mean of per-domain interpolations of coolpup.py --rescale.
 Everything heavy is native: parsing and
 task generation in libmodle_hip.so (host), the simulation on the MI355X (one process per GPU;
 under torch.distributed.run the cells are sharded over the ranks and the matrices are summed
@@ -206,6 +213,10 @@ def pileup_path(prefix):
     return prefix + "_pileup.tsv"
 
 
+def domains_path(prefix):
+    return prefix + "_domains.tsv"
+
+
 def stripes_path(prefix):
     return prefix + "_stripes.tsv"
 
@@ -329,6 +340,12 @@ def add_analysis_arguments(io):
     # two options), kept out of the generated help likewise
     io.add_argument("--dots-fdr", type=float, default=None, metavar="Q", help=argparse.SUPPRESS)
     io.add_argument("--dots-lambda-chunks", type=int, default=None, metavar="N", help=argparse.SUPPRESS)
+    # The average domain (<prefix>_domains.tsv; the module's text describes the four options), kept out of the
+    # generated help likewise
+    io.add_argument("--domains-at", action="append", default=None, metavar="FILE.bed", help=argparse.SUPPRESS)
+    io.add_argument("--domains-size", type=int, default=None, metavar="N", help=argparse.SUPPRESS)
+    io.add_argument("--domains-flank-percent", type=int, default=None, metavar="P", help=argparse.SUPPRESS)
+    io.add_argument("--domains-resolution", type=genomic_distance, default=None, metavar="R", help=argparse.SUPPRESS)
 
 
 def build_parser():
@@ -514,13 +531,17 @@ Stripes = collections.namedtuple("Stripes", "path reference resolution metrics e
 # smoothing box and the last diagonal in base pairs (None: the widest the band allows), the first diagonal, and
 # whether a diagonal counts the pixels that are zero in both matrices; the bin size is Stripes.resolution
 Scc = collections.namedtuple("Scc", "path smooth max_distance min_diag include_zeros")
+# what --domains-at asks for: the file (None with --skip-output), the bin size, the side of the grid in cells, the
+# padding of a domain in percent of its bins, and the BED files in the order given
+Domains = collections.namedtuple("Domains", "path resolution size flank_percent sources")
 # The whole plan of a run, which preflight makes once: the bin sizes of the .mcool (None: a .cool), the
 # Outputs, this rank among the ranks and its device, the five records above (None: not asked for), the
-# diagonals --coverage leaves out, and the Scc.  (The first five fields are also made positionally: the others
-# default.)
+# diagonals --coverage leaves out, the Domains and the Scc.  (The first five fields are also made positionally:
+# the others default.)
 Preflight = collections.namedtuple(
-    "Preflight", "bin_sizes outputs rank world device insulation dots pileup subsample stripes coverage_min_diag scc",
-    defaults=(None, None, None, None, None, 0, None))
+    "Preflight", "bin_sizes outputs rank world device insulation dots pileup subsample stripes coverage_min_diag "
+                 "domains scc",
+    defaults=(None, None, None, None, None, 0, None, None))
 
 
 def subsample_options(a, cfg):
@@ -594,6 +615,27 @@ def pileup_options(a, cfg, dots):
             raise SystemExit(f"--pileup-at dots: the pileup resolution ({res}) is not the dots resolution "
                              f"({int(dots.resolution)})")
     return Pileup(_file(a, pileup_path), res, flank, corner, list(a.pileup_at))
+
+
+MAX_DOMAINS_FLANK_PERCENT = 200
+
+
+def domains_options(a, cfg):
+    """The average domain the arguments ask for, as a Domains, or None.  SystemExit: a --domains-* option without
+    --domains-at, a resolution that is no multiple of -r, a size outside 1..128, a flank outside 0..200 percent."""
+    if not a.domains_at:
+        _needs("--domains-at", (("--domains-size", a.domains_size),
+                                ("--domains-flank-percent", a.domains_flank_percent),
+                                ("--domains-resolution", a.domains_resolution)))
+        return None
+    res = _analysis_resolution("--domains-resolution", a.domains_resolution, cfg)
+    size = 60 if a.domains_size is None else int(a.domains_size)
+    if not 1 <= size <= pixels.MAX_RESCALE:
+        raise SystemExit(f"--domains-size: {size} is not in [1, {pixels.MAX_RESCALE}]")
+    percent = 100 if a.domains_flank_percent is None else int(a.domains_flank_percent)
+    if not 0 <= percent <= MAX_DOMAINS_FLANK_PERCENT:
+        raise SystemExit(f"--domains-flank-percent: {percent} is not in [0, {MAX_DOMAINS_FLANK_PERCENT}]")
+    return Domains(_file(a, domains_path), res, size, percent, list(a.domains_at))
 
 
 def dots_options(a, cfg):
@@ -729,11 +771,12 @@ def preflight(a, cfg):
     """The whole plan of the run, a Preflight: what the arguments alone settle and refuse, without a genome or
     a GPU.  Nothing after it derives an analysis from the arguments again.  SystemExit:
     --coverage-ignore-diags without --coverage, or negative; what insulation_options, dots_options,
-    pileup_options, subsample_options, stripes_options and scc_options refuse, in that order (stripes_options
+    pileup_options, domains_options, subsample_options, stripes_options and scc_options refuse, in that order
+    (stripes_options
     opens the reference cooler, the one time it is opened before the launch); a bad --mcool-resolutions list; on
     rank 0, an output that exists without --force (cooler or .mcool, then bigwig, then .npz, then the expected,
-    the coverage, the insulation, the dots and the pileup file, then the sampled files, then the stripes, then
-    the SCC).  With
+    the coverage, the insulation, the dots, the pileup and the domains file, then the sampled files, then the
+    stripes, then the SCC).  With
     --skip-output no file is planned and none is looked at."""
     if a.coverage_ignore_diags is not None:
         if not a.coverage:
@@ -743,6 +786,7 @@ def preflight(a, cfg):
     ins = insulation_options(a, cfg)
     dots = dots_options(a, cfg)
     pile = pileup_options(a, cfg, dots)
+    dom = domains_options(a, cfg)
     sub = subsample_options(a, cfg)
     cmp_ = stripes_options(a, cfg)
     scc = scc_options(a, cfg, cmp_)
@@ -751,7 +795,7 @@ def preflight(a, cfg):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     device = a.device if a.device is not None else int(os.environ.get("LOCAL_RANK", "0"))
-    analyses = (ins, dots, pile, sub, cmp_, a.coverage_ignore_diags or 0, scc)
+    analyses = (ins, dots, pile, sub, cmp_, a.coverage_ignore_diags or 0, dom, scc)
     if a.skip_output:
         return Preflight(bin_sizes, Outputs(None, None, None, None), rank, world, device, *analyses)
     cool_path, bw_path = output_paths(a.output_prefix, mcool=bin_sizes is not None)
@@ -763,7 +807,7 @@ def preflight(a, cfg):
     if rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(cool_path)), exist_ok=True)
         planned = [outputs.cooler, outputs.bigwig, outputs.dense, outputs.expected, outputs.coverage]
-        planned += [r.path for r in (ins, dots, pile, sub) if r is not None]
+        planned += [r.path for r in (ins, dots, pile, dom, sub) if r is not None]
         planned += [dots.thresholds_path] if dots is not None else []
         planned += [sub.rest_path] if sub is not None and sub.split else []
         planned += [cmp_.path] if cmp_ is not None else []
@@ -815,6 +859,14 @@ def check_plan(a, cfg, pre, plan, chroms):
             raise SystemExit(f"--pileup-flank: the flank of {bad[2]} ({bad[3]} bins of {pre.pileup.resolution}) does "
                              f"not fit the band of {bad[1]} ({bad[4]} diagonals): the largest flank that fits is "
                              f"{bad[5]} ({bad[5] // pre.pileup.resolution} bins)")
+    if pre.domains is not None and pre.domains.path is not None:
+        bad = driver.domains_misfit(plan, int(cfg.bin_size), pre.domains.resolution, pre.domains.size,
+                                    pre.domains.sources)
+        if bad is not None and bad[0] == "bed":
+            raise SystemExit(f"--domains-at {bad[1]}: the file cannot be read as BED: {bad[2]}")
+        if bad is not None:
+            raise SystemExit(f"--domains-size: no window reaches {bad[1]} bins of {pre.domains.resolution}: the "
+                             f"deepest band has {bad[2]} diagonals")
     cmp_ = pre.stripes
     if cmp_ is not None:
         bad = driver.stripes_misfit(plan, int(cfg.bin_size), cmp_.resolution, cmp_.metrics, cmp_.ref_bin_size,

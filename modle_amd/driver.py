@@ -986,6 +986,209 @@ def _interval_pileup(sim, plan, ids, marginals, cache, flank, name, k, factor, f
     return pile, n_used, api.pileup_expected_terms(dist_hist, diag_sum, nc, flank)
 
 
+def read_bed(path):
+    """The domains of a BED file as a list of (chrom, start, end): the first three columns of every line that is
+    neither empty nor starts with `#`.  OSError when the file cannot be opened, ValueError, naming the line, for
+    one with fewer than three columns or a coordinate that is no non-negative integer or ends before it
+    starts."""
+    domains = []
+    with open(path) as fh:
+        for n, line in enumerate(fh, 1):
+            if not line.strip() or line.startswith("#"):
+                continue
+            cols = line.rstrip("\r\n").split("\t")
+            if len(cols) < 3:
+                cols = line.split()
+            try:
+                if len(cols) < 3:
+                    raise ValueError("fewer than three columns")
+                s, e = int(cols[1]), int(cols[2])
+                if s < 0 or e < s:
+                    raise ValueError("a negative start or an end before its start")
+            except ValueError as e:
+                raise ValueError(f"{path}, line {n}: {e}") from None
+            domains.append((cols[0], s, e))
+    return domains
+
+
+def place_domains(plan, base, resolution, flank_percent, domains):
+    """Where the domains of read_bed lie in the plan at the bin size `resolution` (a multiple of `base`), each
+    padded by `flank_percent` of its bins on either side: ({k: (start, end)}, unplaced).  A domain goes to the
+    first entry k of the plan that has a matrix, is of its chromosome and contains it; in the columns of that
+    entry's band it covers [s, e), s = start // resolution - first, e = max(s + 1, ceil(end / resolution) -
+    first), first = (start of the interval // base) // factor, and its window is [s - pad, e + pad) with
+    pad = (e - s) * flank_percent // 100 (int64 arrays, in file order).  A window that leaves the band is not
+    clipped: the kernel's rule rejects it.  `unplaced` counts the domains that no such entry contains."""
+    base, res, percent = int(base), int(resolution), int(flank_percent)
+    factor = res // base
+    placed, unplaced = {}, 0
+    for chrom, start, end in domains:
+        for k, entry in enumerate(plan):
+            iv = entry["interval"]
+            if entry["skipped"] or entry["ncols"] == 0 or iv["name"] != chrom:
+                continue
+            if int(iv["start"]) <= start and end <= int(iv["end"]):
+                first = (int(iv["start"]) // base) // factor
+                s = start // res - first
+                e = max(s + 1, -(-end // res) - first)
+                pad = (e - s) * percent // 100
+                placed.setdefault(k, ([], []))
+                placed[k][0].append(s - pad), placed[k][1].append(e + pad)
+                break
+        else:
+            unplaced += 1
+    return {k: (np.array(s, dtype=np.int64), np.array(e, dtype=np.int64)) for k, (s, e) in placed.items()}, unplaced
+
+
+def domains_misfit(plan, base, resolution, size, sources=()):
+    """What refuses the average domain before anything is simulated, or None: ("bed", path, why) for the first
+    source that read_bed cannot read, else ("size", the grid side, the diagonals of the deepest band) when the
+    plan has matrices and no window reaches `size` bins in any of them at `resolution`, size > nrows' of every
+    band."""
+    for what in sources:
+        try:
+            read_bed(what)
+        except (OSError, ValueError) as e:
+            return "bed", what, str(e)
+    depths = [nr for _, entry, _, _, (nr, _) in plan_bands(plan, base, int(resolution)) if entry["ncols"] != 0]
+    if depths and int(size) > max(depths):
+        return "size", int(size), max(depths)
+    return None
+
+
+RESCALE_CHECKED_WINDOWS = 4096  # how many accepted windows of an interval check_rescaled piles again, each alone
+
+
+def window_total(px, s, e):
+    """the sum of the symmetric matrix over the square [s, e) x [s, e) from the extracted pixels `px`
+    (pixels.Pixels with the band's own columns as bin ids): a diagonal pixel once, another one twice"""
+    lo, hi = int(px.bin1_offset[s]), int(px.bin1_offset[e])
+    b1, b2, c = px.bin1[lo:hi], px.bin2[lo:hi], px.count[lo:hi].astype(np.int64)
+    inside = b2 < e
+    on = inside & (b1 == b2)
+    return 2 * int(c[inside].sum()) - int(c[on].sum())
+
+
+def check_rescaled(name, source, size, pile, area, n_used, width_hist, windows=(), totals=(), alone=None):
+    """What a rescaled pileup of a band (api.Simulator.rescaled_pileup) must satisfy before a row is written, in
+    exact integers: n_used is the sum of width_hist; the area equals the closed form of the widths
+    (api.rescaled_area), word for word; pile and area are symmetric; and for every (s, e) of `windows` (accepted
+    ones; the caller gives RESCALE_CHECKED_WINDOWS at most) the window's total from the extracted pixels,
+    `totals`, equals the sum of what `alone(s, e)`, the window piled alone, returns.  RuntimeError, naming the
+    interval and the source, when one does not hold."""
+    r = int(size)
+    p, ar = np.asarray(pile), np.asarray(area)
+    if p.shape != (r, r) or ar.shape != (r, r):
+        raise RuntimeError(f"{name}: the rescaled pileup at {source} has the shapes {p.shape} and {ar.shape}, not "
+                           f"{r} x {r}")
+    total = sum(int(x) for x in width_hist)
+    if int(n_used) != total:
+        raise RuntimeError(f"{name}: the rescaled pileup at {source} used {int(n_used)} windows, their widths count "
+                           f"{total}")
+    want = api.rescaled_area(width_hist, r)
+    if not np.array_equal(ar.astype(np.uint64), want):
+        u, v = (int(x[0]) for x in np.nonzero(ar.astype(np.uint64) != want))
+        raise RuntimeError(f"{name}: cell ({u}, {v}) of the rescaled pileup at {source} took {int(ar[u, v])} source "
+                           f"pixels, the widths of the used windows give {int(want[u, v])}")
+    for what, m in (("pile", p), ("area", ar)):
+        if not np.array_equal(m, m.T):
+            raise RuntimeError(f"{name}: the {what} of the rescaled pileup at {source} is not symmetric")
+    for (s, e), t in zip(windows, totals):
+        got = sum(int(x) for x in np.asarray(alone(s, e)).reshape(-1))
+        if got != int(t):
+            raise RuntimeError(f"{name}: the window [{int(s)}, {int(e)}) of the rescaled pileup at {source} piles "
+                               f"{got} alone, its pixels add up to {int(t)}")
+
+
+def domains_header(source, resolution, size, flank_percent, given, placed, used, strength):
+    """the `#` line in front of a source's block of <prefix>_domains.tsv: the source, the bin size, the side of
+    the grid, the padding in percent, the domains given, placed in an interval and used (accepted by the kernel),
+    and the repr of api.domain_strength of the block"""
+    return (f"#source={source}\tresolution={int(resolution)}\tsize={int(size)}\tflank_percent={int(flank_percent)}"
+            f"\tgiven={int(given)}\tplaced={int(placed)}\tused={int(used)}\tstrength={float(strength)!r}\n")
+
+
+def domains_lines(size, observed, area, expected):
+    """the rows of a source's block, one per cell, row-major: the row, the column, the observed sum and the
+    number of source pixels (integers) and the repr of the expected sum.  `observed`, `area`, `expected`:
+    size * size values."""
+    r = int(size)
+    return [f"{q // r}\t{q % r}\t{int(o)}\t{int(a)}\t{float(e)!r}\n"
+            for q, (o, a, e) in enumerate(zip(observed, area, expected))]
+
+
+def write_domains(path, plan, base, resolution, size, flank_percent, sources, windows, rescaled, unplaced=None):
+    """<prefix>_domains.tsv: one block per BED file of `sources`, in the order given: domains_header, then
+    domains_lines, at the bin size `resolution` (a multiple of `base`).  `windows(name, k)` returns the windows
+    (start, end) of source `name` in plan entry k, columns of its band, or None; `rescaled(name, k, factor,
+    first_bin, start, end)` returns (pile, area, n_used, terms) of them -- what api.Simulator.rescaled_pileup
+    returns and the terms of api.rescaled_expected_terms for its width_hist -- or None for an entry without a
+    matrix.  The observed pile and the area are sums over the entries in Python ints, the expected pile
+    math.fsum over the entries of the terms.  `unplaced`: {name: the domains given that lie in no entry}.
+    Returns [(name, given, placed, used)]."""
+    res, r = int(resolution), int(size)
+    done = []
+    with open(path, "w") as fh:
+        for name in sources:
+            observed, area, terms = [0] * (r * r), [0] * (r * r), [[] for _ in range(r * r)]
+            placed = used = 0
+            for k, _, first_bin, factor, _ in plan_bands(plan, base, res):
+                se = windows(name, k)
+                if se is None:
+                    continue
+                got = rescaled(name, k, factor, first_bin, se[0], se[1])
+                if got is None:
+                    continue
+                placed += len(se[0])
+                used += int(got[2])
+                for q, x in enumerate(np.asarray(got[0]).reshape(-1)):
+                    observed[q] += int(x)
+                for q, x in enumerate(np.asarray(got[1]).reshape(-1)):
+                    area[q] += int(x)
+                for q, t in enumerate(got[3]):
+                    terms[q] += list(t)
+            given = placed + int((unplaced or {}).get(name, 0))
+            expected = [math.fsum(t) for t in terms]
+            strength = api.domain_strength(np.array(observed, dtype=object).reshape(r, r),
+                                           np.array(expected, dtype=np.float64).reshape(r, r), r, flank_percent)
+            fh.write(domains_header(name, res, r, flank_percent, given, placed, used, strength))
+            fh.writelines(domains_lines(r, observed, area, expected))
+            done.append((name, given, placed, used))
+    return done
+
+
+@_needs_matrix
+def _interval_windows(plan, ids, placed, name, k):
+    """write_domains' first callback: the windows of a BED file that place_domains put into entry k"""
+    return placed[name].get(k, (np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)))
+
+
+@_needs_matrix
+def _interval_rescaled(sim, plan, ids, marginals, cache, size, name, k, factor, first_bin, start, end):
+    """write_domains' second callback: summed on the device from the matrix where it lies (with several ranks:
+    the reduced tensor) on a grid of `size`, and verified (check_rescaled) against the pixels of the band at
+    that bin size, extracted once per entry (`cache`): up to RESCALE_CHECKED_WINDOWS evenly spaced accepted
+    windows are piled again, each alone.  The terms of the expected pile come from the diagonal sums of the
+    marginals pass (`marginals`: _interval_marginals)."""
+    from . import pixels
+
+    entry = plan[k]
+    nr, nc = insulation_shape(entry["nrows"], entry["ncols"], first_bin, factor)
+    pile, area, n_used, width_hist = sim.rescaled_pileup(ids[k], start, end, size, factor, first_bin)
+    if k not in cache:
+        cache[k] = sim.pixels(ids[k], 0, factor=factor, first_bin=first_bin)
+    px = cache[k]
+    ok = np.flatnonzero(pixels.rescale_accepts(nr, nc, size, start, end))
+    if len(ok) > RESCALE_CHECKED_WINDOWS:
+        ok = ok[np.unique(np.linspace(0, len(ok) - 1, RESCALE_CHECKED_WINDOWS).astype(np.int64))]
+    picked = [(int(start[t]), int(end[t])) for t in ok]
+    check_rescaled(interval_name(entry["interval"]), name, size, pile, area, n_used, width_hist, picked,
+                   [window_total(px, s, e) for s, e in picked],
+                   lambda s, e: sim.rescaled_pileup(ids[k], [s], [e], size, factor, first_bin)[0])
+    diag_sum = marginals(k, factor, first_bin)[0]
+    return pile, area, n_used, api.rescaled_expected_terms(width_hist, diag_sum, nc, size)
+
+
 def stripes_what(metrics, exclude_zero):
     """the mask of pixels.stripes for the `metrics` of --compare-metrics: the moments always (check_stripes
     reads them), the masked moments with --compare-exclude-zero-pixels, the rank sums for spearman"""
@@ -1342,6 +1545,21 @@ def pileup_file(sim, cfg, plan, ids, sums, marginals, log, pileup, interval_dots
     log(f"written {pileup.path}")
 
 
+def domains_file(sim, cfg, plan, ids, sums, marginals, log, domains):
+    """<prefix>_domains.tsv of the cli.Domains `domains`"""
+    base, res = int(cfg.bin_size), int(domains.resolution)
+    placed, unplaced = {}, {}
+    for what in domains.sources:
+        if what not in placed:
+            placed[what], unplaced[what] = place_domains(plan, base, res, domains.flank_percent, read_bed(what))
+            if unplaced[what]:
+                log(f"--domains-at {what}: {unplaced[what]} domains lie in no simulated interval")
+    write_domains(domains.path, plan, base, res, domains.size, domains.flank_percent, domains.sources,
+                  functools.partial(_interval_windows, plan, ids, placed),
+                  functools.partial(_interval_rescaled, sim, plan, ids, marginals, {}, int(domains.size)), unplaced)
+    log(f"written {domains.path}")
+
+
 def stripes_file(sim, cfg, plan, ids, sums, marginals, log, stripes, scc=None):
     """<prefix>_stripes.tsv of the cli.Stripes `stripes`: the reference cooler is opened here, the one time after
     the launch, for its pixels.  With a cli.Scc `scc` the sums of the strata are taken while every reference
@@ -1367,7 +1585,7 @@ def write_files(sim, cfg, plan, ids, missed, pre, regions, log, **attrs):
     """Rank 0's files of the plan `pre`, in this order: the cooler or .mcool with the missing-interactions
     warnings (`missed`: of collect_outputs), the sampled matrices (sample_matrices), the dense `regions`, the
     distance-decay curves at every bin size of the file, the coverage without the diagonals below
-    `pre.coverage_min_diag`, then insulation_file, dots_file, pileup_file and stripes_file (with `pre.scc` the SCC file too).  All of them read
+    `pre.coverage_min_diag`, then insulation_file, dots_file, pileup_file, domains_file and stripes_file (with `pre.scc` the SCC file too).  All of them read
     the matrices where they lie (with several ranks: the reduced tensors), after the cooler's INT32 range check
     has passed.  `attrs`: write_pixels' keywords."""
     outputs, bin_sizes = pre.outputs, pre.bin_sizes
@@ -1394,6 +1612,8 @@ def write_files(sim, cfg, plan, ids, missed, pre, regions, log, **attrs):
     interval_dots = dots_file(*shared, pre.dots) if pre.dots is not None else None
     if pre.pileup is not None:
         pileup_file(*shared, pre.pileup, interval_dots)
+    if pre.domains is not None:
+        domains_file(*shared, pre.domains)
     if pre.stripes is not None:
         stripes_file(*shared, pre.stripes, pre.scc)
 

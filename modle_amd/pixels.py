@@ -4,7 +4,8 @@ memory, in cooler order, found on the GPU; the band at a multiple of its bin siz
 of it as dense matrices; its marginals, the sums per diagonal and per bin; its insulation sums
 over sliding diamond windows; its dots, the pixels enriched over their HiCCUPS neighbourhoods, by fold and by
 the statistical test (the lambda-chunk histogram counted on the GPU, dot_thresholds, the threshold decision);
-its pileups, the windows around anchor pairs summed into one; and its random sampling, every contact
+its pileups, the windows around anchor pairs summed into one, and its rescaled pileups, windows of different
+sizes on the diagonal cut into one grid of blocks and summed; and its random sampling, every contact
 kept with one probability by a generator keyed by the pixel's coordinates; the way back, sorted pixels
 checked and scattered into a band on the GPU; and two bands compared stripe by stripe, the integer sums of
 every bin's vertical and horizontal stripe formed on the GPU and turned into scores by stripe_scores, and
@@ -26,6 +27,7 @@ ERR_ARG, ERR_DEVICE, ERR_RANGE, ERR_ORDER = -1, -2, -3, -4
 MAX_WINDOW, MAX_WINDOWS = 1024, 8  # MODLE_PIXELS_MAX_WINDOW, MODLE_PIXELS_MAX_WINDOWS
 MAX_DOT_WINDOW = 20  # MODLE_PIXELS_MAX_DOT_WINDOW
 MAX_PILEUP_FLANK, PILEUP_GROUPS = 32, 256  # MODLE_PIXELS_MAX_PILEUP_FLANK, MODLE_PIXELS_PILEUP_GROUPS
+MAX_RESCALE = 128  # MODLE_PIXELS_MAX_RESCALE: the largest grid side of a rescaled pileup
 SAMPLE_TIER1_TRIALS = 64  # MODLE_PIXELS_SAMPLE_TIER1_TRIALS: what a lane draws of its own pixel
 MAX_SAMPLE_TRIALS = 1 << 40  # MODLE_PIXELS_MAX_SAMPLE_TRIALS
 SAMPLE_KEPT, SAMPLE_REST = 0, 1  # MODLE_PIXELS_SAMPLE_KEPT, MODLE_PIXELS_SAMPLE_REST
@@ -49,7 +51,9 @@ EXPORTS = ["modle_pixels_create", "modle_pixels_destroy", "modle_pixels_count", 
            "modle_pixels_dot_hist_to_host", "modle_pixels_coarse_dot_hist_to_host", "modle_pixels_dots_fdr",
            "modle_pixels_dots_fdr_to_host", "modle_pixels_coarse_dots_fdr_to_host", "modle_pixels_pileup_accepts",
            "modle_pixels_pileup", "modle_pixels_pileup_to_host",
-           "modle_pixels_coarse_pileup_to_host", "modle_pixels_sample_pixels", "modle_pixels_sample",
+           "modle_pixels_coarse_pileup_to_host", "modle_pixels_rescale_groups", "modle_pixels_rescale_accepts",
+           "modle_pixels_rescale", "modle_pixels_rescale_to_host", "modle_pixels_coarse_rescale_to_host",
+           "modle_pixels_sample_pixels", "modle_pixels_sample",
            "modle_pixels_sample_to_host", "modle_pixels_band_classify", "modle_pixels_band_check",
            "modle_pixels_band_fill", "modle_pixels_band_from_host", "modle_pixels_stripes_rows",
            "modle_pixels_stripes", "modle_pixels_stripes_to_host", "modle_pixels_scc_groups", "modle_pixels_scc",
@@ -163,6 +167,16 @@ def lib():
         lb.modle_pixels_pileup_to_host.argtypes = shape + [C.c_uint64, C.c_int64, i64p, i64p, C.c_uint64] + piled
         lb.modle_pixels_coarse_pileup_to_host.argtypes = shape + [C.c_uint64] * 3 + [C.c_int64, i64p, i64p,
                                                                                      C.c_uint64] + piled
+        scaled = [C.POINTER(C.c_void_p)] * 3 + [C.c_void_p] + err  # pile, area, n_used, stream
+        lb.modle_pixels_rescale_groups.argtypes = []
+        lb.modle_pixels_rescale_groups.restype = C.c_uint64
+        lb.modle_pixels_rescale_accepts.argtypes = [C.c_uint64] * 3 + [C.c_int64, i64p, i64p, C.c_uint64,
+                                                                       C.POINTER(C.c_uint8)]
+        lb.modle_pixels_rescale.argtypes = shape + [C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + err
+        lb.modle_pixels_rescale_to_host.argtypes = shape + [C.c_uint64, C.c_int64, i64p, i64p, C.c_uint64] + scaled
+        lb.modle_pixels_coarse_rescale_to_host.argtypes = shape + [C.c_uint64] * 3 + [C.c_int64, i64p, i64p,
+                                                                                      C.c_uint64] + scaled
         u32p = C.POINTER(C.c_uint32)
         draw = [C.c_int64, C.c_uint64, C.c_uint64, C.c_uint32]  # bin_offset, threshold, seed, salt
         lb.modle_pixels_sample_pixels.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_int64, i64p, i64p, u32p,
@@ -454,6 +468,35 @@ def pileup_accepts(nrows, ncols, flank, bin1, bin2, bin_offset=0):
     if rc != 0:
         raise PixelsError(rc, "pileup_accepts: invalid argument (0 < nrows <= ncols, flank <= 32, "
                               "2 * flank + 1 <= nrows, n < 2^31)")
+    return out.astype(bool)
+
+
+def rescale_groups():
+    """the workgroups of a rescaled pileup at most that the loaded library was compiled with
+    (modle_pixels_rescale_groups; no device is needed): 256 unless MODLE_PIXELS_LIB names a test build"""
+    return int(lib().modle_pixels_rescale_groups())
+
+
+def _size(size):
+    if int(size) < 0:
+        raise PixelsError(ERR_ARG, "rescale: negative size")
+    return int(size)
+
+
+def rescale_accepts(nrows, ncols, size, start, end, bin_offset=0):
+    """which windows [start[t] - bin_offset, end[t] - bin_offset) = [s, e) a rescaled pileup on a grid of
+    `size` uses, a numpy bool array: 0 <= s < e <= ncols, size <= e - s <= nrows, for any int64 values
+    (modle_pixels_rescale_accepts; no device is needed)"""
+    if min(int(nrows), int(ncols)) < 0:
+        raise PixelsError(ERR_ARG, "rescale_accepts: negative shape")
+    keep, p1, p2, n = _anchors(start, end)
+    out = np.zeros(n, dtype=np.uint8)
+    rc = lib().modle_pixels_rescale_accepts(int(nrows), int(ncols), _size(size), int(bin_offset), p1, p2, n,
+                                            out.ctypes.data_as(C.POINTER(C.c_uint8)))
+    del keep
+    if rc != 0:
+        raise PixelsError(rc, "rescale_accepts: invalid argument (0 < nrows <= ncols, 1 <= size <= 128, n < 2^31, "
+                              "n * ceil(nrows / size)^2 < 2^32)")
     return out.astype(bool)
 
 
@@ -945,6 +988,36 @@ class Extractor:
         (modle_pixels_coarse_pileup_to_host): `flank` and the anchors count coarse bins"""
         return self.pileup(d_band, nrows, ncols, flank, bin1, bin2, bin_offset, stream, factor, first_bin, True)
 
+    def rescale_into(self, d_band, nrows, ncols, size, d_start, d_end, n, d_pile, d_area=None, d_n_used=None,
+                     bin_offset=0, stream=None):
+        """enqueues the rescaled pileup of the `n` windows in the device arrays `d_start`, `d_end` (int64) into
+        the caller-owned device arrays `d_pile` (uint64[size][size]), `d_area` (the same, or None) and
+        `d_n_used` (uint64[1], or None), all 8-byte aligned; every word is written (modle_pixels_rescale)"""
+        _call(self._L.modle_pixels_rescale, self._h, d_band, int(nrows), int(ncols), _size(size), int(bin_offset),
+              d_start, d_end, int(n), d_pile, d_area, d_n_used, _stream_ptr(stream))
+
+    def rescale(self, d_band, nrows, ncols, size, start, end, bin_offset=0, stream=None, factor=1, first_bin=0,
+                coarse=None):
+        """(pile, area, n_used): the accepted ones (rescale_accepts) of the host windows
+        [start[t] - bin_offset, end[t] - bin_offset) of the symmetric matrix, each cut into size x size blocks
+        and the blocks summed, numpy uint64[size, size]; how many source pixels every cell took; and how many
+        windows were accepted, summed on the device (modle_pixels_rescale_to_host).  pile / area is the pooled
+        mean of a cell: large windows weigh more."""
+        fn, band, _ = self._form("rescale_", d_band, nrows, ncols, factor, first_bin, coarse)
+        keep, p1, p2, n = _anchors(start, end)
+        pp, pa, pn = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _call(fn, self._h, *band, _size(size), int(bin_offset), p1, p2, n, C.byref(pp), C.byref(pa), C.byref(pn),
+              _stream_ptr(stream))
+        del keep
+        r = int(size)
+        return _host_array(pp.value, r * r, np.uint64).reshape(r, r), \
+            _host_array(pa.value, r * r, np.uint64).reshape(r, r), int(_host_array(pn.value, 1, np.uint64)[0])
+
+    def coarse_rescale(self, d_band, nrows, ncols, factor, first_bin, size, start, end, bin_offset=0, stream=None):
+        """`rescale` of the band at `factor` times its bin size, coarsened on the device
+        (modle_pixels_coarse_rescale_to_host): the windows count coarse bins"""
+        return self.rescale(d_band, nrows, ncols, size, start, end, bin_offset, stream, factor, first_bin, True)
+
     def sample_into(self, d_band, nrows, ncols, threshold, seed, stats, d_kept, d_rest=None, salt=0, bin_offset=0,
                     stream=None):
         """enqueues the sampling of the band (modle_pixels_sample): of the n contacts of pixel (i, j) those
@@ -1147,6 +1220,26 @@ def coarse_pileup(d_band, nrows, ncols, factor, first_bin, flank, bin1, bin2, bi
     and summed on the device."""
     return extractor(device).coarse_pileup(d_band, nrows, ncols, factor, first_bin, flank, bin1, bin2, bin_offset,
                                            stream)
+
+
+def rescale_into(d_band, nrows, ncols, size, d_start, d_end, n, d_pile, d_area=None, d_n_used=None, bin_offset=0,
+                 stream=None, device=0):
+    """The rescaled pileup of the band at device pointer `d_band` over `n` windows in device arrays, into the
+    device arrays `d_pile`, `d_area` and `d_n_used`: see Extractor.rescale_into."""
+    extractor(device).rescale_into(d_band, nrows, ncols, size, d_start, d_end, n, d_pile, d_area, d_n_used, bin_offset,
+                                   stream)
+
+
+def rescale(d_band, nrows, ncols, size, start, end, bin_offset=0, stream=None, device=0):
+    """(pile, area, n_used) of the rescaled pileup of the band at device pointer `d_band` over host windows:
+    see Extractor.rescale."""
+    return extractor(device).rescale(d_band, nrows, ncols, size, start, end, bin_offset, stream)
+
+
+def coarse_rescale(d_band, nrows, ncols, factor, first_bin, size, start, end, bin_offset=0, stream=None, device=0):
+    """(pile, area, n_used) of the band at `factor` times its bin size: see Extractor.coarse_rescale."""
+    return extractor(device).coarse_rescale(d_band, nrows, ncols, factor, first_bin, size, start, end, bin_offset,
+                                            stream)
 
 
 def sample_into(d_band, nrows, ncols, threshold, seed, stats, d_kept, d_rest=None, salt=0, bin_offset=0, stream=None,

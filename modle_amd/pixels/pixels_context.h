@@ -26,6 +26,10 @@
 #ifndef MODLE_SCC_MAX_GROUPS  // workgroups per strip of 64 strata at most (modle_scc.hip); modle_pixels_scc_groups
 #define MODLE_SCC_MAX_GROUPS 128u
 #endif
+#ifndef MODLE_RESCALE_MAX_GROUPS  // workgroups of pixels_rescale at most (modle_rescale.hip): _rescale_groups
+#define MODLE_RESCALE_MAX_GROUPS 256u
+#endif
+static_assert(MODLE_RESCALE_MAX_GROUPS >= 1 && MODLE_RESCALE_MAX_GROUPS <= 65535u, "a grid's x; partials in scratch");
 static_assert(MODLE_SCC_MAX_GROUPS >= 1 && MODLE_SCC_MAX_GROUPS <= 65535u, "a grid's y");
 static_assert(MODLE_STRIPES_MAX_GRID >= 1 && MODLE_STRIPES_MAX_GRID <= (1u << 20), "a grid's x");
 static_assert(MODLE_BAND_FILL_MAX_Y >= 1 && MODLE_BAND_FILL_MAX_Y <= 65535u, "a grid's y");
@@ -159,6 +163,12 @@ struct modle_pixels_handle {
   // to-host form the 11 rows of nrows words (modle_scc.hip)
   GrowBuf<uint64_t> scc_partial;
   GrowBuf<uint64_t, true> scc;
+  // modle_pixels_rescale*: the workgroups' partial sums (per workgroup R (R + 1) / 2 words of pile, as many of
+  // area, then their counts), and of the to-host forms the windows (start, then end) and pile, area and n_used
+  // (modle_rescale.hip)
+  GrowBuf<uint64_t> rescale_partial;
+  GrowBuf<int64_t> rescale_windows;
+  GrowBuf<uint64_t, true> rescale_out;
 };
 
 #endif
