@@ -221,7 +221,7 @@ __global__ __launch_bounds__(kFillThreads) void band_fill(const int64_t* __restr
 }
 
 using modle_pixels_detail::bad_shape;
-using modle_pixels_detail::overlap;
+using modle_pixels_detail::any_overlap;
 using modle_pixels_detail::set_err;
 
 bool misaligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) != 0; }
@@ -313,9 +313,7 @@ extern "C" int modle_pixels_band_check(modle_pixels_handle* h, const int64_t* d_
                          "arrays unless n == 0; 8-byte aligned int64 arrays)");
     return MODLE_PIXELS_ERR_ARG;
   }
-  const uint64_t nr = d_row_start != nullptr ? (ncols + 1) * 8 : 0;
-  if (overlap(d_row_start, nr, d_bin1, n * 8) || overlap(d_row_start, nr, d_bin2, n * 8) ||
-      overlap(d_row_start, nr, d_count, n * 4)) {
+  if (any_overlap({{d_row_start, (ncols + 1) * 8}}, {{d_bin1, n * 8}, {d_bin2, n * 8}, {d_count, n * 4}})) {
     set_err(err, errlen, "modle_pixels_band_check: d_row_start overlaps the pixels");
     return MODLE_PIXELS_ERR_ARG;
   }
@@ -335,8 +333,7 @@ extern "C" int modle_pixels_band_fill(modle_pixels_handle* h, const int64_t* d_b
     return MODLE_PIXELS_ERR_ARG;
   }
   const uint64_t nb = modle_pixels_detail::band_bytes(nrows, ncols);
-  if (overlap(d_out, nb, d_bin2, n * 8) || overlap(d_out, nb, d_count, n * 4) ||
-      overlap(d_out, nb, d_row_start, (ncols + 1) * 8)) {
+  if (any_overlap({{d_out, nb}}, {{d_bin2, n * 8}, {d_count, n * 4}, {d_row_start, (ncols + 1) * 8}})) {
     set_err(err, errlen, "modle_pixels_band_fill: d_out overlaps an input");
     return MODLE_PIXELS_ERR_ARG;
   }
@@ -363,8 +360,8 @@ extern "C" int modle_pixels_band_from_host(modle_pixels_handle* h, const int64_t
   if (rc == MODLE_PIXELS_OK) rc = h->band_rows.ensure(ncols + 1, err, errlen);
   if (rc != MODLE_PIXELS_OK) return rc;
   const uint64_t nb = modle_pixels_detail::band_bytes(nrows, ncols);
-  if (overlap(d_out, nb, h->band_bin1.dev, n * 8) || overlap(d_out, nb, h->band_bin2.dev, n * 8) ||
-      overlap(d_out, nb, h->band_count.dev, n * 4) || overlap(d_out, nb, h->band_rows.dev, (ncols + 1) * 8)) {
+  if (any_overlap({{d_out, nb}}, {{h->band_bin1.dev, n * 8}, {h->band_bin2.dev, n * 8}, {h->band_count.dev, n * 4},
+                                  {h->band_rows.dev, (ncols + 1) * 8}})) {
     set_err(err, errlen, "modle_pixels_band_from_host: d_out overlaps the scratch of the context");
     return MODLE_PIXELS_ERR_ARG;
   }

@@ -117,13 +117,30 @@ int coarsen_impl(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
 
 }  // namespace
 
-int modle_pixels_detail::coarsen_to_scratch(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
-                                            uint64_t ncols, uint64_t factor, uint64_t first_bin, uint64_t nr,
-                                            uint64_t nc, hipStream_t stream, char* err, size_t errlen) {
+bool modle_pixels_detail::view_shape(const uint32_t* d_band, uint64_t nrows, uint64_t ncols, const CoarseSpec* cs,
+                                     BandView* v, bool empty_ok) {
+  *v = BandView{d_band, nrows, ncols};
+  if (cs != nullptr)
+    return d_band != nullptr &&
+           modle_pixels_coarse_shape(nrows, ncols, cs->factor, cs->first_bin, &v->nrows, &v->ncols) == MODLE_PIXELS_OK;
+  if (empty_ok ? d_band == nullptr && ncols != 0 : d_band == nullptr || nrows == 0) return false;
+  return !bad_shape(nrows, ncols);
+}
+
+int modle_pixels_detail::resolve_band(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols,
+                                      const CoarseSpec* cs, BandView* v, hipStream_t stream, char* err,
+                                      size_t errlen) {
+  if (cs == nullptr) return MODLE_PIXELS_OK;
   PIX_TRY(hipSetDevice(h->device));
-  const int rc = h->coarse.ensure(nr * nc + 1, err, errlen);
+  const int rc = h->coarse.ensure(v->nrows * v->ncols + 1, err, errlen);
   if (rc != MODLE_PIXELS_OK) return rc;
-  return coarsen_impl(h, d_band, nrows, ncols, factor, first_bin, h->coarse.dev, nr, nc, stream, err, errlen);
+  v->d = h->coarse.dev;
+  return coarsen_impl(h, d_band, nrows, ncols, cs->factor, cs->first_bin, h->coarse.dev, v->nrows, v->ncols, stream,
+                      err, errlen);
+}
+
+std::string modle_pixels_detail::refusal(const char* name, const CoarseSpec* cs, const char* rule) {
+  return std::string(name) + ": invalid argument " + (cs != nullptr ? "(factor >= 2; of the coarse band:) " : "") + rule;
 }
 
 extern "C" int modle_pixels_coarse_shape(uint64_t nrows, uint64_t ncols, uint64_t factor, uint64_t first_bin,
@@ -158,21 +175,7 @@ extern "C" int modle_pixels_coarse_to_host(modle_pixels_handle* h, const uint32_
                                            const int32_t** count, const int64_t** bin1_offset,
                                            modle_pixels_stats* stats, void* stream, char* err,
                                            size_t errlen) {
-  uint64_t nr = 0, nc = 0;
-  if (h == nullptr || d_band == nullptr ||
-      modle_pixels_detail::bad_pixel_outputs(bin1, bin2, count, bin1_offset, stats, bin_offset) ||
-      modle_pixels_coarse_shape(nrows, ncols, factor, first_bin, &nr, &nc) != MODLE_PIXELS_OK) {
-    modle_pixels_detail::set_err(
-        err, errlen, "modle_pixels_coarse_to_host: invalid argument (factor >= 2, 0 < nrows <= ncols)");
-    return MODLE_PIXELS_ERR_ARG;
-  }
-  *bin1 = *bin2 = nullptr;
-  *count = nullptr;
-  *bin1_offset = nullptr;
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = modle_pixels_detail::coarsen_to_scratch(h, d_band, nrows, ncols, factor, first_bin, nr, nc, st, err,
-                                                         errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  return modle_pixels_detail::to_host(h, h->coarse.dev, nr, nc, bin_offset, bin1, bin2, count, bin1_offset, stats,
-                                      st, err, errlen);
+  const modle_pixels_detail::CoarseSpec cs{factor, first_bin};
+  return modle_pixels_detail::pixels_one_call("modle_pixels_coarse_to_host", &cs, h, d_band, nrows, ncols, bin_offset,
+                                              bin1, bin2, count, bin1_offset, stats, stream, err, errlen);
 }

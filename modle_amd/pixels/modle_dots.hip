@@ -435,24 +435,6 @@ int hist_impl(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, ui
   return launch<kHist>(d_band, nrows, ncols, w, p, min_diag, 1, nullptr, nullptr, nullptr, ct, stream, err, errlen);
 }
 
-// zeroes the scratch table of the context, adds the band's histogram, copies it to pinned memory, waits
-int hist_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols, uint64_t w,
-                 uint64_t p, uint64_t min_diag, const double* lam, const double* edges, uint64_t n_edges,
-                 uint64_t n_obs, const uint64_t** hist, hipStream_t stream, char* err, size_t errlen) {
-  PIX_TRY(hipSetDevice(h->device));
-  const uint64_t words = 4 * (n_edges + 1) * n_obs;
-  int rc = h->dot_hist.ensure(words, err, errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  PIX_TRY(hipMemsetAsync(h->dot_hist.dev, 0, words * 8, stream));
-  rc = hist_impl(h, d_band, nrows, ncols, w, p, min_diag, lam, edges, n_edges, n_obs, h->dot_hist.dev, stream, err,
-                 errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  PIX_TRY(hipMemcpyAsync(h->dot_hist.host, h->dot_hist.dev, words * 8, hipMemcpyDeviceToHost, stream));
-  PIX_TRY(hipStreamSynchronize(stream));
-  *hist = h->dot_hist.host;
-  return MODLE_PIXELS_OK;
-}
-
 // enqueues the threshold decision into d_cand on checked arguments; `scale` may be null
 int fdr_impl(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols, uint64_t w, uint64_t p,
              uint64_t min_diag, uint64_t min_count, const double* lam, const double* edges, uint64_t n_edges,
@@ -471,35 +453,30 @@ int fdr_impl(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uin
                       d_cand, nullptr, ct, stream, err, errlen);
 }
 
-// the threshold decision into the scratch band of the context, then count / scan / extract
-int fdr_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols, uint64_t w, uint64_t p,
-                uint64_t min_diag, uint64_t min_count, const double* lam, const double* edges, uint64_t n_edges,
-                const uint32_t* thr, const double* scale, int64_t bin_offset, const int64_t** bin1,
-                const int64_t** bin2, const int32_t** count, const int64_t** bin1_offset, modle_pixels_stats* stats,
-                hipStream_t stream, char* err, size_t errlen) {
+// modle_pixels_dots_to_host (`cs` null) and modle_pixels_coarse_dots_to_host under their `name`: the band resolved,
+// its candidates into the scratch band of the context, then count / scan / extract
+int dots_one_call(const char* name, const modle_pixels_detail::CoarseSpec* cs, modle_pixels_handle* h,
+                  const uint32_t* d_band, uint64_t nrows, uint64_t ncols, uint64_t w, uint64_t p, uint64_t min_diag,
+                  uint64_t min_count, const double* scale, int64_t bin_offset, const int64_t** bin1,
+                  const int64_t** bin2, const int32_t** count, const int64_t** bin1_offset, modle_pixels_stats* stats,
+                  void* stream, char* err, size_t errlen) {
+  modle_pixels_detail::BandView v;
+  if (h == nullptr || bad_pixel_outputs(bin1, bin2, count, bin1_offset, stats, bin_offset) ||
+      !modle_pixels_detail::view_shape(d_band, nrows, ncols, cs, &v) ||
+      bad_dots(v.nrows, v.ncols, w, p, min_diag, min_count, scale, true)) {
+    set_err(err, errlen, modle_pixels_detail::refusal(name, cs, kRule));
+    return MODLE_PIXELS_ERR_ARG;
+  }
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  int rc = modle_pixels_detail::resolve_band(h, d_band, nrows, ncols, cs, &v, st, err, errlen);
+  if (rc != MODLE_PIXELS_OK) return rc;
   PIX_TRY(hipSetDevice(h->device));
-  int rc = h->dot_cand.ensure(nrows * ncols + 1, err, errlen);
+  rc = h->dot_cand.ensure(v.nrows * v.ncols + 1, err, errlen);
+  if (rc == MODLE_PIXELS_OK)
+    rc = dots_impl(h, v.d, v.nrows, v.ncols, w, p, min_diag, min_count, scale, h->dot_cand.dev, nullptr, st, err, errlen);
   if (rc != MODLE_PIXELS_OK) return rc;
-  rc = fdr_impl(h, d_band, nrows, ncols, w, p, min_diag, min_count, lam, edges, n_edges, thr, scale, h->dot_cand.dev,
-                stream, err, errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  return modle_pixels_detail::to_host(h, h->dot_cand.dev, nrows, ncols, bin_offset, bin1, bin2, count, bin1_offset,
-                                      stats, stream, err, errlen);
-}
-
-// the candidates of the band `d_band` into the scratch band of the context, then count / scan / extract
-int dots_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols, uint64_t w,
-                 uint64_t p, uint64_t min_diag, uint64_t min_count, const double* scale, int64_t bin_offset,
-                 const int64_t** bin1, const int64_t** bin2, const int32_t** count, const int64_t** bin1_offset,
-                 modle_pixels_stats* stats, hipStream_t stream, char* err, size_t errlen) {
-  PIX_TRY(hipSetDevice(h->device));
-  int rc = h->dot_cand.ensure(nrows * ncols + 1, err, errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  rc = dots_impl(h, d_band, nrows, ncols, w, p, min_diag, min_count, scale, h->dot_cand.dev, nullptr, stream, err,
-                 errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  return modle_pixels_detail::to_host(h, h->dot_cand.dev, nrows, ncols, bin_offset, bin1, bin2, count, bin1_offset,
-                                      stats, stream, err, errlen);
+  return modle_pixels_detail::to_host(h, h->dot_cand.dev, v.nrows, v.ncols, bin_offset, bin1, bin2, count, bin1_offset,
+                                      stats, st, err, errlen);
 }
 
 }  // namespace
@@ -513,8 +490,7 @@ extern "C" int modle_pixels_dots(modle_pixels_handle* h, const uint32_t* d_band,
     return MODLE_PIXELS_ERR_ARG;
   }
   const uint64_t nb = modle_pixels_detail::band_bytes(nrows, ncols), ns = nrows * ncols * 32;
-  if ((d_cand != nullptr && overlap(d_cand, nb, d_band, nb)) || (d_sums != nullptr && overlap(d_sums, ns, d_band, nb)) ||
-      (d_cand != nullptr && d_sums != nullptr && overlap(d_cand, nb, d_sums, ns))) {
+  if (modle_pixels_detail::any_overlap({{d_cand, nb}, {d_sums, ns}}, {{d_band, nb}})) {
     set_err(err, errlen, "modle_pixels_dots: an output overlaps the band or the other output");
     return MODLE_PIXELS_ERR_ARG;
   }
@@ -528,13 +504,8 @@ extern "C" int modle_pixels_dots_to_host(modle_pixels_handle* h, const uint32_t*
                                          const int64_t** bin1, const int64_t** bin2, const int32_t** count,
                                          const int64_t** bin1_offset, modle_pixels_stats* stats, void* stream,
                                          char* err, size_t errlen) {
-  if (h == nullptr || d_band == nullptr || bad_pixel_outputs(bin1, bin2, count, bin1_offset, stats, bin_offset) ||
-      bad_dots(nrows, ncols, w, p, min_diag, min_count, scale, true)) {
-    set_err(err, errlen, std::string("modle_pixels_dots_to_host: invalid argument ") + kRule);
-    return MODLE_PIXELS_ERR_ARG;
-  }
-  return dots_to_host(h, d_band, nrows, ncols, w, p, min_diag, min_count, scale, bin_offset, bin1, bin2, count,
-                      bin1_offset, stats, static_cast<hipStream_t>(stream), err, errlen);
+  return dots_one_call("modle_pixels_dots_to_host", nullptr, h, d_band, nrows, ncols, w, p, min_diag, min_count, scale,
+                       bin_offset, bin1, bin2, count, bin1_offset, stats, stream, err, errlen);
 }
 
 extern "C" int modle_pixels_coarse_dots_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
@@ -544,21 +515,9 @@ extern "C" int modle_pixels_coarse_dots_to_host(modle_pixels_handle* h, const ui
                                                 const int64_t** bin2, const int32_t** count,
                                                 const int64_t** bin1_offset, modle_pixels_stats* stats,
                                                 void* stream, char* err, size_t errlen) {
-  uint64_t nr = 0, nc = 0;
-  // (modle_pixels_coarse_shape refuses what modle_pixels_coarsen refuses of shape and factor)
-  if (h == nullptr || d_band == nullptr || bad_pixel_outputs(bin1, bin2, count, bin1_offset, stats, bin_offset) ||
-      modle_pixels_coarse_shape(nrows, ncols, factor, first_bin, &nr, &nc) != MODLE_PIXELS_OK ||
-      bad_dots(nr, nc, w, p, min_diag, min_count, scale, true)) {
-    set_err(err, errlen, std::string("modle_pixels_coarse_dots_to_host: invalid argument (factor >= 2; of the "
-                                     "coarse band:) ") + kRule);
-    return MODLE_PIXELS_ERR_ARG;
-  }
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = modle_pixels_detail::coarsen_to_scratch(h, d_band, nrows, ncols, factor, first_bin, nr, nc, st, err,
-                                                         errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  return dots_to_host(h, h->coarse.dev, nr, nc, w, p, min_diag, min_count, scale, bin_offset, bin1, bin2, count,
-                      bin1_offset, stats, st, err, errlen);
+  const modle_pixels_detail::CoarseSpec cs{factor, first_bin};
+  return dots_one_call("modle_pixels_coarse_dots_to_host", &cs, h, d_band, nrows, ncols, w, p, min_diag, min_count,
+                       scale, bin_offset, bin1, bin2, count, bin1_offset, stats, stream, err, errlen);
 }
 
 namespace {
@@ -569,6 +528,65 @@ constexpr const char* kChunkRule =
     "aligned; of the rest:) ";
 
 bool bad_n_obs(uint64_t n_obs) { return n_obs < 2 || n_obs > MODLE_PIXELS_MAX_DOT_OBS; }
+
+// the refusal of the forms with tables; the coarse twins name the factor before and the coarse band behind the tables' rule
+std::string chunk_refusal(const char* name, const modle_pixels_detail::CoarseSpec* cs) {
+  return std::string(name) + ": invalid argument " + (cs != nullptr ? "(factor >= 2) " : "") + kChunkRule +
+         (cs != nullptr ? "(of the coarse band:) " : "") + kRule;
+}
+
+// modle_pixels_dot_hist_to_host (`cs` null) and modle_pixels_coarse_dot_hist_to_host under their `name`: the band
+// resolved, the table in the sums of the context zeroed, the band's histogram added, the copy to the pinned mirror, the wait
+int hist_one_call(const char* name, const modle_pixels_detail::CoarseSpec* cs, modle_pixels_handle* h,
+                  const uint32_t* d_band, uint64_t nrows, uint64_t ncols, uint64_t w, uint64_t p, uint64_t min_diag,
+                  const double* lam, const double* edges, uint64_t n_edges, uint64_t n_obs, const uint64_t** hist,
+                  void* stream, char* err, size_t errlen) {
+  if (hist != nullptr) *hist = nullptr;
+  modle_pixels_detail::BandView v;
+  if (h == nullptr || hist == nullptr || bad_n_obs(n_obs) || bad_chunks(lam, edges, n_edges, nullptr, false) ||
+      !modle_pixels_detail::view_shape(d_band, nrows, ncols, cs, &v) ||
+      bad_dots(v.nrows, v.ncols, w, p, min_diag, 1, lam, true)) {
+    set_err(err, errlen, chunk_refusal(name, cs));
+    return MODLE_PIXELS_ERR_ARG;
+  }
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = modle_pixels_detail::resolve_band(h, d_band, nrows, ncols, cs, &v, st, err, errlen);
+  if (rc != MODLE_PIXELS_OK) return rc;
+  const uint64_t words = 4 * (n_edges + 1) * n_obs;
+  return modle_pixels_detail::sums_to_host(h, words, hist, st, err, errlen, [&](uint64_t* d_hist) {
+    PIX_TRY(hipMemsetAsync(d_hist, 0, words * 8, st));  // (hist_impl adds)
+    return hist_impl(h, v.d, v.nrows, v.ncols, w, p, min_diag, lam, edges, n_edges, n_obs, d_hist, st, err, errlen);
+  });
+}
+
+// modle_pixels_dots_fdr_to_host (`cs` null) and modle_pixels_coarse_dots_fdr_to_host under their `name`: the band
+// resolved, the threshold decision into the scratch band of the context, then count / scan / extract
+int fdr_one_call(const char* name, const modle_pixels_detail::CoarseSpec* cs, modle_pixels_handle* h,
+                 const uint32_t* d_band, uint64_t nrows, uint64_t ncols, uint64_t w, uint64_t p, uint64_t min_diag,
+                 uint64_t min_count, const double* lam, const double* edges, uint64_t n_edges, const uint32_t* thr,
+                 const double* scale, int64_t bin_offset, const int64_t** bin1, const int64_t** bin2,
+                 const int32_t** count, const int64_t** bin1_offset, modle_pixels_stats* stats, void* stream, char* err,
+                 size_t errlen) {
+  modle_pixels_detail::BandView v;
+  if (h == nullptr || bad_pixel_outputs(bin1, bin2, count, bin1_offset, stats, bin_offset) ||
+      bad_chunks(lam, edges, n_edges, thr, true) || !modle_pixels_detail::view_shape(d_band, nrows, ncols, cs, &v) ||
+      bad_dots(v.nrows, v.ncols, w, p, min_diag, min_count, lam, true) ||
+      bad_dots(v.nrows, v.ncols, w, p, min_diag, min_count, scale, false)) {
+    set_err(err, errlen, chunk_refusal(name, cs));
+    return MODLE_PIXELS_ERR_ARG;
+  }
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  int rc = modle_pixels_detail::resolve_band(h, d_band, nrows, ncols, cs, &v, st, err, errlen);
+  if (rc != MODLE_PIXELS_OK) return rc;
+  PIX_TRY(hipSetDevice(h->device));
+  rc = h->dot_cand.ensure(v.nrows * v.ncols + 1, err, errlen);
+  if (rc == MODLE_PIXELS_OK)
+    rc = fdr_impl(h, v.d, v.nrows, v.ncols, w, p, min_diag, min_count, lam, edges, n_edges, thr, scale, h->dot_cand.dev,
+                  st, err, errlen);
+  if (rc != MODLE_PIXELS_OK) return rc;
+  return modle_pixels_detail::to_host(h, h->dot_cand.dev, v.nrows, v.ncols, bin_offset, bin1, bin2, count, bin1_offset,
+                                      stats, st, err, errlen);
+}
 
 }  // namespace
 
@@ -595,14 +613,8 @@ extern "C" int modle_pixels_dot_hist_to_host(modle_pixels_handle* h, const uint3
                                              const double* lam, const double* edges, uint64_t n_edges,
                                              uint64_t n_obs, const uint64_t** hist, void* stream, char* err,
                                              size_t errlen) {
-  if (hist != nullptr) *hist = nullptr;
-  if (h == nullptr || d_band == nullptr || hist == nullptr || bad_n_obs(n_obs) ||
-      bad_chunks(lam, edges, n_edges, nullptr, false) || bad_dots(nrows, ncols, w, p, min_diag, 1, lam, true)) {
-    set_err(err, errlen, std::string("modle_pixels_dot_hist_to_host: invalid argument ") + kChunkRule + kRule);
-    return MODLE_PIXELS_ERR_ARG;
-  }
-  return hist_to_host(h, d_band, nrows, ncols, w, p, min_diag, lam, edges, n_edges, n_obs, hist,
-                      static_cast<hipStream_t>(stream), err, errlen);
+  return hist_one_call("modle_pixels_dot_hist_to_host", nullptr, h, d_band, nrows, ncols, w, p, min_diag, lam, edges,
+                       n_edges, n_obs, hist, stream, err, errlen);
 }
 
 extern "C" int modle_pixels_coarse_dot_hist_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
@@ -610,21 +622,9 @@ extern "C" int modle_pixels_coarse_dot_hist_to_host(modle_pixels_handle* h, cons
                                                     uint64_t p, uint64_t min_diag, const double* lam,
                                                     const double* edges, uint64_t n_edges, uint64_t n_obs,
                                                     const uint64_t** hist, void* stream, char* err, size_t errlen) {
-  if (hist != nullptr) *hist = nullptr;
-  uint64_t nr = 0, nc = 0;
-  if (h == nullptr || d_band == nullptr || hist == nullptr || bad_n_obs(n_obs) ||
-      bad_chunks(lam, edges, n_edges, nullptr, false) ||
-      modle_pixels_coarse_shape(nrows, ncols, factor, first_bin, &nr, &nc) != MODLE_PIXELS_OK ||
-      bad_dots(nr, nc, w, p, min_diag, 1, lam, true)) {
-    set_err(err, errlen, std::string("modle_pixels_coarse_dot_hist_to_host: invalid argument (factor >= 2) ") +
-                             kChunkRule + "(of the coarse band:) " + kRule);
-    return MODLE_PIXELS_ERR_ARG;
-  }
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = modle_pixels_detail::coarsen_to_scratch(h, d_band, nrows, ncols, factor, first_bin, nr, nc, st, err,
-                                                         errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  return hist_to_host(h, h->coarse.dev, nr, nc, w, p, min_diag, lam, edges, n_edges, n_obs, hist, st, err, errlen);
+  const modle_pixels_detail::CoarseSpec cs{factor, first_bin};
+  return hist_one_call("modle_pixels_coarse_dot_hist_to_host", &cs, h, d_band, nrows, ncols, w, p, min_diag, lam, edges,
+                       n_edges, n_obs, hist, stream, err, errlen);
 }
 
 extern "C" int modle_pixels_dots_fdr(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols,
@@ -653,14 +653,8 @@ extern "C" int modle_pixels_dots_fdr_to_host(modle_pixels_handle* h, const uint3
                                              int64_t bin_offset, const int64_t** bin1, const int64_t** bin2,
                                              const int32_t** count, const int64_t** bin1_offset,
                                              modle_pixels_stats* stats, void* stream, char* err, size_t errlen) {
-  if (h == nullptr || d_band == nullptr || bad_pixel_outputs(bin1, bin2, count, bin1_offset, stats, bin_offset) ||
-      bad_chunks(lam, edges, n_edges, thr, true) || bad_dots(nrows, ncols, w, p, min_diag, min_count, lam, true) ||
-      bad_dots(nrows, ncols, w, p, min_diag, min_count, scale, false)) {
-    set_err(err, errlen, std::string("modle_pixels_dots_fdr_to_host: invalid argument ") + kChunkRule + kRule);
-    return MODLE_PIXELS_ERR_ARG;
-  }
-  return fdr_to_host(h, d_band, nrows, ncols, w, p, min_diag, min_count, lam, edges, n_edges, thr, scale, bin_offset,
-                     bin1, bin2, count, bin1_offset, stats, static_cast<hipStream_t>(stream), err, errlen);
+  return fdr_one_call("modle_pixels_dots_fdr_to_host", nullptr, h, d_band, nrows, ncols, w, p, min_diag, min_count, lam,
+                      edges, n_edges, thr, scale, bin_offset, bin1, bin2, count, bin1_offset, stats, stream, err, errlen);
 }
 
 extern "C" int modle_pixels_coarse_dots_fdr_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
@@ -671,20 +665,8 @@ extern "C" int modle_pixels_coarse_dots_fdr_to_host(modle_pixels_handle* h, cons
                                                     const int64_t** bin1, const int64_t** bin2, const int32_t** count,
                                                     const int64_t** bin1_offset, modle_pixels_stats* stats,
                                                     void* stream, char* err, size_t errlen) {
-  uint64_t nr = 0, nc = 0;
-  if (h == nullptr || d_band == nullptr || bad_pixel_outputs(bin1, bin2, count, bin1_offset, stats, bin_offset) ||
-      bad_chunks(lam, edges, n_edges, thr, true) ||
-      modle_pixels_coarse_shape(nrows, ncols, factor, first_bin, &nr, &nc) != MODLE_PIXELS_OK ||
-      bad_dots(nr, nc, w, p, min_diag, min_count, lam, true) ||
-      bad_dots(nr, nc, w, p, min_diag, min_count, scale, false)) {
-    set_err(err, errlen, std::string("modle_pixels_coarse_dots_fdr_to_host: invalid argument (factor >= 2) ") +
-                             kChunkRule + "(of the coarse band:) " + kRule);
-    return MODLE_PIXELS_ERR_ARG;
-  }
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = modle_pixels_detail::coarsen_to_scratch(h, d_band, nrows, ncols, factor, first_bin, nr, nc, st, err,
-                                                         errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  return fdr_to_host(h, h->coarse.dev, nr, nc, w, p, min_diag, min_count, lam, edges, n_edges, thr, scale, bin_offset,
-                     bin1, bin2, count, bin1_offset, stats, st, err, errlen);
+  const modle_pixels_detail::CoarseSpec cs{factor, first_bin};
+  return fdr_one_call("modle_pixels_coarse_dots_fdr_to_host", &cs, h, d_band, nrows, ncols, w, p, min_diag, min_count,
+                      lam, edges, n_edges, thr, scale, bin_offset, bin1, bin2, count, bin1_offset, stats, stream, err,
+                      errlen);
 }

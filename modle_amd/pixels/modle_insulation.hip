@@ -164,19 +164,25 @@ int insulation_impl(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nro
   return MODLE_PIXELS_OK;
 }
 
-// insulation_impl into the context's buffer, the copy to its pinned mirror, the wait
-int insulation_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols,
-                       const uint64_t* windows, uint64_t n_windows, uint64_t min_diag, const uint64_t** ins_sum,
-                       hipStream_t stream, char* err, size_t errlen) {
-  PIX_TRY(hipSetDevice(h->device));
-  int rc = h->insulation.ensure(n_windows * ncols, err, errlen);
+// modle_pixels_insulation_to_host (`cs` null) and modle_pixels_coarse_insulation_to_host under their `name`: the
+// band resolved, insulation_impl into the sums of the context, their copy to the pinned mirror, the wait
+int insulation_one_call(const char* name, const modle_pixels_detail::CoarseSpec* cs, modle_pixels_handle* h,
+                        const uint32_t* d_band, uint64_t nrows, uint64_t ncols, const uint64_t* windows,
+                        uint64_t n_windows, uint64_t min_diag, const uint64_t** ins_sum, void* stream, char* err,
+                        size_t errlen) {
+  if (ins_sum != nullptr) *ins_sum = nullptr;
+  modle_pixels_detail::BandView v;
+  if (h == nullptr || ins_sum == nullptr || !modle_pixels_detail::view_shape(d_band, nrows, ncols, cs, &v) ||
+      bad_windows(windows, n_windows, v.nrows)) {
+    set_err(err, errlen, modle_pixels_detail::refusal(name, cs, kRule));
+    return MODLE_PIXELS_ERR_ARG;
+  }
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = modle_pixels_detail::resolve_band(h, d_band, nrows, ncols, cs, &v, st, err, errlen);
   if (rc != MODLE_PIXELS_OK) return rc;
-  rc = insulation_impl(h, d_band, nrows, ncols, windows, n_windows, min_diag, h->insulation.dev, stream, err, errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  PIX_TRY(hipMemcpyAsync(h->insulation.host, h->insulation.dev, n_windows * ncols * 8, hipMemcpyDeviceToHost, stream));
-  PIX_TRY(hipStreamSynchronize(stream));
-  *ins_sum = h->insulation.host;
-  return MODLE_PIXELS_OK;
+  return modle_pixels_detail::sums_to_host(h, n_windows * v.ncols, ins_sum, st, err, errlen, [&](uint64_t* d_out) {
+    return insulation_impl(h, v.d, v.nrows, v.ncols, windows, n_windows, min_diag, d_out, st, err, errlen);
+  });
 }
 
 }  // namespace
@@ -216,14 +222,8 @@ extern "C" int modle_pixels_insulation_to_host(modle_pixels_handle* h, const uin
                                                uint64_t ncols, const uint64_t* windows, uint64_t n_windows,
                                                uint64_t min_diag, const uint64_t** ins_sum, void* stream,
                                                char* err, size_t errlen) {
-  if (ins_sum != nullptr) *ins_sum = nullptr;
-  if (h == nullptr || d_band == nullptr || ins_sum == nullptr || nrows == 0 ||
-      modle_pixels_detail::bad_shape(nrows, ncols) || bad_windows(windows, n_windows, nrows)) {
-    set_err(err, errlen, std::string("modle_pixels_insulation_to_host: invalid argument ") + kRule);
-    return MODLE_PIXELS_ERR_ARG;
-  }
-  return insulation_to_host(h, d_band, nrows, ncols, windows, n_windows, min_diag, ins_sum,
-                            static_cast<hipStream_t>(stream), err, errlen);
+  return insulation_one_call("modle_pixels_insulation_to_host", nullptr, h, d_band, nrows, ncols, windows, n_windows,
+                             min_diag, ins_sum, stream, err, errlen);
 }
 
 extern "C" int modle_pixels_coarse_insulation_to_host(modle_pixels_handle* h, const uint32_t* d_band,
@@ -232,19 +232,7 @@ extern "C" int modle_pixels_coarse_insulation_to_host(modle_pixels_handle* h, co
                                                       uint64_t n_windows, uint64_t min_diag,
                                                       const uint64_t** ins_sum, void* stream, char* err,
                                                       size_t errlen) {
-  if (ins_sum != nullptr) *ins_sum = nullptr;
-  uint64_t nr = 0, nc = 0;
-  // (modle_pixels_coarse_shape refuses what modle_pixels_coarsen refuses of shape and factor)
-  if (h == nullptr || d_band == nullptr || ins_sum == nullptr ||
-      modle_pixels_coarse_shape(nrows, ncols, factor, first_bin, &nr, &nc) != MODLE_PIXELS_OK ||
-      bad_windows(windows, n_windows, nr)) {
-    set_err(err, errlen, std::string("modle_pixels_coarse_insulation_to_host: invalid argument (factor >= 2; "
-                                     "of the coarse band:) ") + kRule);
-    return MODLE_PIXELS_ERR_ARG;
-  }
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = modle_pixels_detail::coarsen_to_scratch(h, d_band, nrows, ncols, factor, first_bin, nr, nc, st, err,
-                                                         errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  return insulation_to_host(h, h->coarse.dev, nr, nc, windows, n_windows, min_diag, ins_sum, st, err, errlen);
+  const modle_pixels_detail::CoarseSpec cs{factor, first_bin};
+  return insulation_one_call("modle_pixels_coarse_insulation_to_host", &cs, h, d_band, nrows, ncols, windows,
+                             n_windows, min_diag, ins_sum, stream, err, errlen);
 }

@@ -114,13 +114,7 @@ __global__ __launch_bounds__(kDepth) void pixels_marginals(const uint32_t* __res
   }
 }
 
-using modle_pixels_detail::overlap;
 using modle_pixels_detail::set_err;
-
-// what the forms on the fine band refuse, whatever their outputs
-int bad_marginals_args(const modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols) {
-  return h == nullptr || d_band == nullptr || nrows == 0 || modle_pixels_detail::bad_shape(nrows, ncols);
-}
 
 // Clears the context's nrows + ncols sums (diag_sum first, then coverage) and enqueues the kernel;
 // a part that is not wanted is neither cleared nor summed.
@@ -141,20 +135,31 @@ int marginals_impl(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrow
   return MODLE_PIXELS_OK;
 }
 
-// marginals_impl, the copy to the pinned mirror, the wait
-int marginals_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols,
-                      uint64_t min_diag, const uint64_t** diag_sum, const uint64_t** coverage,
-                      hipStream_t stream, char* err, size_t errlen) {
+// modle_pixels_marginals_to_host (`cs` null) and modle_pixels_coarse_marginals_to_host under their `name`: the
+// band resolved, marginals_impl, the copy to the pinned mirror, the wait
+int marginals_one_call(const char* name, const modle_pixels_detail::CoarseSpec* cs, modle_pixels_handle* h,
+                       const uint32_t* d_band, uint64_t nrows, uint64_t ncols, uint64_t min_diag,
+                       const uint64_t** diag_sum, const uint64_t** coverage, void* stream, char* err, size_t errlen) {
   const bool want_diag = diag_sum != nullptr, want_cov = coverage != nullptr;
-  const int rc = marginals_impl(h, d_band, nrows, ncols, min_diag, want_diag, want_cov, stream, err, errlen);
+  if (want_diag) *diag_sum = nullptr;
+  if (want_cov) *coverage = nullptr;
+  modle_pixels_detail::BandView v;
+  if (h == nullptr || (!want_diag && !want_cov) || !modle_pixels_detail::view_shape(d_band, nrows, ncols, cs, &v)) {
+    set_err(err, errlen, std::string(name) + ": invalid argument (" + (cs != nullptr ? "factor >= 2, " : "") +
+                             "0 < nrows <= ncols, an output)");
+    return MODLE_PIXELS_ERR_ARG;
+  }
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  int rc = modle_pixels_detail::resolve_band(h, d_band, nrows, ncols, cs, &v, st, err, errlen);
+  if (rc == MODLE_PIXELS_OK) rc = marginals_impl(h, v.d, v.nrows, v.ncols, min_diag, want_diag, want_cov, st, err, errlen);
   if (rc != MODLE_PIXELS_OK) return rc;
   const uint64_t* dev = h->marginals.dev;
   uint64_t* host = h->marginals.host;
-  if (want_diag) PIX_TRY(hipMemcpyAsync(host, dev, nrows * 8, hipMemcpyDeviceToHost, stream));
-  if (want_cov) PIX_TRY(hipMemcpyAsync(host + nrows, dev + nrows, ncols * 8, hipMemcpyDeviceToHost, stream));
-  PIX_TRY(hipStreamSynchronize(stream));
+  if (want_diag) PIX_TRY(hipMemcpyAsync(host, dev, v.nrows * 8, hipMemcpyDeviceToHost, st));
+  if (want_cov) PIX_TRY(hipMemcpyAsync(host + v.nrows, dev + v.nrows, v.ncols * 8, hipMemcpyDeviceToHost, st));
+  PIX_TRY(hipStreamSynchronize(st));
   if (want_diag) *diag_sum = host;
-  if (want_cov) *coverage = host + nrows;
+  if (want_cov) *coverage = host + v.nrows;
   return MODLE_PIXELS_OK;
 }
 
@@ -163,14 +168,16 @@ int marginals_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t n
 extern "C" int modle_pixels_marginals(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
                                       uint64_t ncols, uint64_t min_diag, uint64_t* d_diag_sum,
                                       uint64_t* d_coverage, void* stream, char* err, size_t errlen) {
-  if (bad_marginals_args(h, d_band, nrows, ncols) || (d_diag_sum == nullptr && d_coverage == nullptr) ||
+  if (h == nullptr || d_band == nullptr || nrows == 0 || modle_pixels_detail::bad_shape(nrows, ncols) ||
+      (d_diag_sum == nullptr && d_coverage == nullptr) ||
       ((reinterpret_cast<uintptr_t>(d_diag_sum) | reinterpret_cast<uintptr_t>(d_coverage)) & 3) != 0) {
     set_err(err, errlen, "modle_pixels_marginals: invalid argument (0 < nrows <= ncols, an output)");
     return MODLE_PIXELS_ERR_ARG;
   }
   const uint64_t nb = modle_pixels_detail::band_bytes(nrows, ncols);
-  if ((d_diag_sum != nullptr && overlap(d_diag_sum, nrows * 8, d_band, nb)) ||
-      (d_coverage != nullptr && overlap(d_coverage, ncols * 8, d_band, nb))) {
+  // (not any_overlap: the header holds the outputs apart from the band only, not from each other)
+  if (modle_pixels_detail::overlap(d_diag_sum, nrows * 8, d_band, nb) ||
+      modle_pixels_detail::overlap(d_coverage, ncols * 8, d_band, nb)) {
     set_err(err, errlen, "modle_pixels_marginals: an output overlaps the band");
     return MODLE_PIXELS_ERR_ARG;
   }
@@ -189,14 +196,8 @@ extern "C" int modle_pixels_marginals_to_host(modle_pixels_handle* h, const uint
                                               uint64_t ncols, uint64_t min_diag, const uint64_t** diag_sum,
                                               const uint64_t** coverage, void* stream, char* err,
                                               size_t errlen) {
-  if (diag_sum != nullptr) *diag_sum = nullptr;
-  if (coverage != nullptr) *coverage = nullptr;
-  if (bad_marginals_args(h, d_band, nrows, ncols) || (diag_sum == nullptr && coverage == nullptr)) {
-    set_err(err, errlen, "modle_pixels_marginals_to_host: invalid argument (0 < nrows <= ncols, an output)");
-    return MODLE_PIXELS_ERR_ARG;
-  }
-  return marginals_to_host(h, d_band, nrows, ncols, min_diag, diag_sum, coverage,
-                           static_cast<hipStream_t>(stream), err, errlen);
+  return marginals_one_call("modle_pixels_marginals_to_host", nullptr, h, d_band, nrows, ncols, min_diag, diag_sum,
+                            coverage, stream, err, errlen);
 }
 
 extern "C" int modle_pixels_coarse_marginals_to_host(modle_pixels_handle* h, const uint32_t* d_band,
@@ -204,19 +205,7 @@ extern "C" int modle_pixels_coarse_marginals_to_host(modle_pixels_handle* h, con
                                                      uint64_t first_bin, uint64_t min_diag,
                                                      const uint64_t** diag_sum, const uint64_t** coverage,
                                                      void* stream, char* err, size_t errlen) {
-  if (diag_sum != nullptr) *diag_sum = nullptr;
-  if (coverage != nullptr) *coverage = nullptr;
-  uint64_t nr = 0, nc = 0;
-  // (modle_pixels_coarse_shape refuses what modle_pixels_coarsen refuses of shape and factor)
-  if (h == nullptr || d_band == nullptr || (diag_sum == nullptr && coverage == nullptr) ||
-      modle_pixels_coarse_shape(nrows, ncols, factor, first_bin, &nr, &nc) != MODLE_PIXELS_OK) {
-    set_err(err, errlen,
-            "modle_pixels_coarse_marginals_to_host: invalid argument (factor >= 2, 0 < nrows <= ncols, an output)");
-    return MODLE_PIXELS_ERR_ARG;
-  }
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = modle_pixels_detail::coarsen_to_scratch(h, d_band, nrows, ncols, factor, first_bin, nr, nc, st, err,
-                                                         errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  return marginals_to_host(h, h->coarse.dev, nr, nc, min_diag, diag_sum, coverage, st, err, errlen);
+  const modle_pixels_detail::CoarseSpec cs{factor, first_bin};
+  return marginals_one_call("modle_pixels_coarse_marginals_to_host", &cs, h, d_band, nrows, ncols, min_diag, diag_sum,
+                            coverage, stream, err, errlen);
 }

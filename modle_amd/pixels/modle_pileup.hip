@@ -152,7 +152,6 @@ __global__ __launch_bounds__(4 * kSumCells) void pixels_pileup_sum(const u64* __
     *n_used = sum;
 }
 
-using modle_pixels_detail::overlap;
 using modle_pixels_detail::set_err;
 
 constexpr const char* kRule =
@@ -199,29 +198,33 @@ int pileup_impl(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, 
   return MODLE_PIXELS_OK;
 }
 
-// the host anchors up, pileup_impl into the context's buffer, the copy to its pinned mirror, the wait
-int pileup_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols, uint64_t f,
-                   int64_t bin_offset, const int64_t* bin1, const int64_t* bin2, uint64_t n, const uint64_t** pile,
-                   const uint64_t** n_used, hipStream_t stream, char* err, size_t errlen) {
-  PIX_TRY(hipSetDevice(h->device));
-  const uint64_t SS = (2 * f + 1) * (2 * f + 1);
-  int rc = h->pile_anchors.ensure(2 * n, err, errlen);
-  if (rc == MODLE_PIXELS_OK) rc = h->pile_out.ensure(SS + 1, err, errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  int64_t* d_bin1 = h->pile_anchors.dev;
-  int64_t* d_bin2 = d_bin1 + n;
-  if (n != 0) {
-    PIX_TRY(hipMemcpyAsync(d_bin1, bin1, n * 8, hipMemcpyHostToDevice, stream));
-    PIX_TRY(hipMemcpyAsync(d_bin2, bin2, n * 8, hipMemcpyHostToDevice, stream));
+// modle_pixels_pileup_to_host (`cs` null) and modle_pixels_coarse_pileup_to_host under their `name`: the band
+// resolved, the host anchors up, pileup_impl into the sums of the context, their copy to the pinned mirror, the wait
+int pileup_one_call(const char* name, const modle_pixels_detail::CoarseSpec* cs, modle_pixels_handle* h,
+                    const uint32_t* d_band, uint64_t nrows, uint64_t ncols, uint64_t f, int64_t bin_offset,
+                    const int64_t* bin1, const int64_t* bin2, uint64_t n, const uint64_t** pile, const uint64_t** n_used,
+                    void* stream, char* err, size_t errlen) {
+  if (pile != nullptr) *pile = nullptr;
+  if (n_used != nullptr) *n_used = nullptr;
+  modle_pixels_detail::BandView v;
+  if (h == nullptr || pile == nullptr || n_used == nullptr ||
+      !modle_pixels_detail::view_shape(d_band, nrows, ncols, cs, &v) || bad_pileup(v.nrows, v.ncols, f, n) ||
+      (n != 0 && (bin1 == nullptr || bin2 == nullptr))) {
+    set_err(err, errlen, modle_pixels_detail::refusal(name, cs, kRule));
+    return MODLE_PIXELS_ERR_ARG;
   }
-  rc = pileup_impl(h, d_band, nrows, ncols, f, bin_offset, d_bin1, d_bin2, n, h->pile_out.dev, h->pile_out.dev + SS,
-                   stream, err, errlen);
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  int rc = modle_pixels_detail::resolve_band(h, d_band, nrows, ncols, cs, &v, st, err, errlen);
   if (rc != MODLE_PIXELS_OK) return rc;
-  PIX_TRY(hipMemcpyAsync(h->pile_out.host, h->pile_out.dev, (SS + 1) * 8, hipMemcpyDeviceToHost, stream));
-  PIX_TRY(hipStreamSynchronize(stream));
-  *pile = h->pile_out.host;
-  *n_used = h->pile_out.host + SS;
-  return MODLE_PIXELS_OK;
+  const uint64_t SS = (2 * f + 1) * (2 * f + 1);
+  rc = modle_pixels_detail::sums_to_host(h, SS + 1, pile, st, err, errlen, [&](uint64_t* d_out) {
+    const int64_t* d[2];
+    const int up = modle_pixels_detail::upload_lists(h, bin1, bin2, n, d, st, err, errlen);
+    if (up != MODLE_PIXELS_OK) return up;
+    return pileup_impl(h, v.d, v.nrows, v.ncols, f, bin_offset, d[0], d[1], n, d_out, d_out + SS, st, err, errlen);
+  });
+  if (rc == MODLE_PIXELS_OK) *n_used = *pile + SS;
+  return rc;
 }
 
 }  // namespace
@@ -247,11 +250,8 @@ extern "C" int modle_pixels_pileup(modle_pixels_handle* h, const uint32_t* d_ban
     set_err(err, errlen, std::string("modle_pixels_pileup: invalid argument ") + kRule);
     return MODLE_PIXELS_ERR_ARG;
   }
-  const uint64_t nb = modle_pixels_detail::band_bytes(nrows, ncols), np = (2 * flank + 1) * (2 * flank + 1) * 8,
-                 nu = d_n_used != nullptr ? 8 : 0, na = n * 8;
-  if (overlap(d_pile, np, d_band, nb) || overlap(d_pile, np, d_bin1, na) || overlap(d_pile, np, d_bin2, na) ||
-      overlap(d_n_used, nu, d_band, nb) || overlap(d_n_used, nu, d_bin1, na) || overlap(d_n_used, nu, d_bin2, na) ||
-      overlap(d_n_used, nu, d_pile, np)) {
+  const uint64_t nb = modle_pixels_detail::band_bytes(nrows, ncols), np = (2 * flank + 1) * (2 * flank + 1) * 8;
+  if (modle_pixels_detail::any_overlap({{d_pile, np}, {d_n_used, 8}}, {{d_band, nb}, {d_bin1, n * 8}, {d_bin2, n * 8}})) {
     set_err(err, errlen, "modle_pixels_pileup: an output overlaps the band, the anchors or the other output");
     return MODLE_PIXELS_ERR_ARG;
   }
@@ -263,15 +263,8 @@ extern "C" int modle_pixels_pileup_to_host(modle_pixels_handle* h, const uint32_
                                            uint64_t ncols, uint64_t flank, int64_t bin_offset, const int64_t* bin1,
                                            const int64_t* bin2, uint64_t n, const uint64_t** pile,
                                            const uint64_t** n_used, void* stream, char* err, size_t errlen) {
-  if (pile != nullptr) *pile = nullptr;
-  if (n_used != nullptr) *n_used = nullptr;
-  if (h == nullptr || d_band == nullptr || pile == nullptr || n_used == nullptr || bad_pileup(nrows, ncols, flank, n) ||
-      (n != 0 && (bin1 == nullptr || bin2 == nullptr))) {
-    set_err(err, errlen, std::string("modle_pixels_pileup_to_host: invalid argument ") + kRule);
-    return MODLE_PIXELS_ERR_ARG;
-  }
-  return pileup_to_host(h, d_band, nrows, ncols, flank, bin_offset, bin1, bin2, n, pile, n_used,
-                        static_cast<hipStream_t>(stream), err, errlen);
+  return pileup_one_call("modle_pixels_pileup_to_host", nullptr, h, d_band, nrows, ncols, flank, bin_offset, bin1, bin2,
+                         n, pile, n_used, stream, err, errlen);
 }
 
 extern "C" int modle_pixels_coarse_pileup_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
@@ -279,20 +272,7 @@ extern "C" int modle_pixels_coarse_pileup_to_host(modle_pixels_handle* h, const 
                                                   int64_t bin_offset, const int64_t* bin1, const int64_t* bin2,
                                                   uint64_t n, const uint64_t** pile, const uint64_t** n_used,
                                                   void* stream, char* err, size_t errlen) {
-  if (pile != nullptr) *pile = nullptr;
-  if (n_used != nullptr) *n_used = nullptr;
-  uint64_t nr = 0, nc = 0;
-  // (modle_pixels_coarse_shape refuses what modle_pixels_coarsen refuses of shape and factor)
-  if (h == nullptr || d_band == nullptr || pile == nullptr || n_used == nullptr ||
-      modle_pixels_coarse_shape(nrows, ncols, factor, first_bin, &nr, &nc) != MODLE_PIXELS_OK ||
-      bad_pileup(nr, nc, flank, n) || (n != 0 && (bin1 == nullptr || bin2 == nullptr))) {
-    set_err(err, errlen, std::string("modle_pixels_coarse_pileup_to_host: invalid argument (factor >= 2; of the "
-                                     "coarse band:) ") + kRule);
-    return MODLE_PIXELS_ERR_ARG;
-  }
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = modle_pixels_detail::coarsen_to_scratch(h, d_band, nrows, ncols, factor, first_bin, nr, nc, st, err,
-                                                         errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  return pileup_to_host(h, h->coarse.dev, nr, nc, flank, bin_offset, bin1, bin2, n, pile, n_used, st, err, errlen);
+  const modle_pixels_detail::CoarseSpec cs{factor, first_bin};
+  return pileup_one_call("modle_pixels_coarse_pileup_to_host", &cs, h, d_band, nrows, ncols, flank, bin_offset, bin1,
+                         bin2, n, pile, n_used, stream, err, errlen);
 }

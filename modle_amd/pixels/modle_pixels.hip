@@ -314,13 +314,29 @@ extern "C" int modle_pixels_to_host(modle_pixels_handle* h, const uint32_t* d_ba
                                     const int64_t** bin2, const int32_t** count,
                                     const int64_t** bin1_offset, modle_pixels_stats* stats, void* stream,
                                     char* err, size_t errlen) {
-  if (h == nullptr || modle_pixels_detail::bad_pixel_outputs(bin1, bin2, count, bin1_offset, stats, bin_offset) ||
-      (d_band == nullptr && ncols != 0) || bad_shape(nrows, ncols)) {
-    set_err(err, errlen, "modle_pixels_to_host: invalid argument (0 < nrows <= ncols, or both 0)");
+  return modle_pixels_detail::pixels_one_call("modle_pixels_to_host", nullptr, h, d_band, nrows, ncols, bin_offset, bin1,
+                                              bin2, count, bin1_offset, stats, stream, err, errlen);
+}
+
+int modle_pixels_detail::pixels_one_call(const char* name, const CoarseSpec* cs, modle_pixels_handle* h,
+                                         const uint32_t* d_band, uint64_t nrows, uint64_t ncols, int64_t bin_offset,
+                                         const int64_t** bin1, const int64_t** bin2, const int32_t** count,
+                                         const int64_t** bin1_offset, modle_pixels_stats* stats, void* stream,
+                                         char* err, size_t errlen) {
+  BandView v;
+  if (h == nullptr || bad_pixel_outputs(bin1, bin2, count, bin1_offset, stats, bin_offset) ||
+      !view_shape(d_band, nrows, ncols, cs, &v, /*empty_ok=*/true)) {
+    set_err(err, errlen, std::string(name) + ": invalid argument " +
+                             (cs != nullptr ? "(factor >= 2, 0 < nrows <= ncols)" : "(0 < nrows <= ncols, or both 0)"));
     return MODLE_PIXELS_ERR_ARG;
   }
-  return modle_pixels_detail::to_host(h, d_band, nrows, ncols, bin_offset, bin1, bin2, count, bin1_offset, stats,
-                                      static_cast<hipStream_t>(stream), err, errlen);
+  *bin1 = *bin2 = nullptr;  // (before the coarsening, which may fail)
+  *count = nullptr;
+  *bin1_offset = nullptr;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = resolve_band(h, d_band, nrows, ncols, cs, &v, st, err, errlen);
+  if (rc != MODLE_PIXELS_OK) return rc;
+  return to_host(h, v.d, v.nrows, v.ncols, bin_offset, bin1, bin2, count, bin1_offset, stats, st, err, errlen);
 }
 
 int modle_pixels_detail::to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols,

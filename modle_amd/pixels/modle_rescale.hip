@@ -159,7 +159,6 @@ __global__ __launch_bounds__(4 * kSumCells) void pixels_rescale_sum(const u64* _
   }
 }
 
-using modle_pixels_detail::overlap;
 using modle_pixels_detail::set_err;
 
 constexpr const char* kRule =
@@ -200,30 +199,36 @@ int rescale_impl(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
   return MODLE_PIXELS_OK;
 }
 
-// the host windows up, rescale_impl into the context's buffer, the copy to its pinned mirror, the wait
-int rescale_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols, uint64_t R,
-                    int64_t bin_offset, const int64_t* start, const int64_t* end, uint64_t n, const uint64_t** pile,
-                    const uint64_t** area, const uint64_t** n_used, hipStream_t stream, char* err, size_t errlen) {
-  PIX_TRY(hipSetDevice(h->device));
-  const uint64_t RR = R * R;
-  int rc = h->rescale_windows.ensure(2 * n, err, errlen);
-  if (rc == MODLE_PIXELS_OK) rc = h->rescale_out.ensure(2 * RR + 1, err, errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  int64_t* d_start = h->rescale_windows.dev;
-  int64_t* d_end = d_start + n;
-  if (n != 0) {
-    PIX_TRY(hipMemcpyAsync(d_start, start, n * 8, hipMemcpyHostToDevice, stream));
-    PIX_TRY(hipMemcpyAsync(d_end, end, n * 8, hipMemcpyHostToDevice, stream));
+// modle_pixels_rescale_to_host (`cs` null) and modle_pixels_coarse_rescale_to_host under their `name`: the band
+// resolved, the host windows up, rescale_impl into the sums of the context, their copy to the pinned mirror, the wait
+int rescale_one_call(const char* name, const modle_pixels_detail::CoarseSpec* cs, modle_pixels_handle* h,
+                     const uint32_t* d_band, uint64_t nrows, uint64_t ncols, uint64_t R, int64_t bin_offset,
+                     const int64_t* start, const int64_t* end, uint64_t n, const uint64_t** pile, const uint64_t** area,
+                     const uint64_t** n_used, void* stream, char* err, size_t errlen) {
+  if (pile != nullptr) *pile = nullptr;
+  if (area != nullptr) *area = nullptr;
+  if (n_used != nullptr) *n_used = nullptr;
+  modle_pixels_detail::BandView v;
+  if (h == nullptr || pile == nullptr || area == nullptr || n_used == nullptr ||
+      !modle_pixels_detail::view_shape(d_band, nrows, ncols, cs, &v) || bad_rescale(v.nrows, v.ncols, R, n) ||
+      (n != 0 && (start == nullptr || end == nullptr))) {
+    set_err(err, errlen, modle_pixels_detail::refusal(name, cs, kRule));
+    return MODLE_PIXELS_ERR_ARG;
   }
-  uint64_t* out = h->rescale_out.dev;
-  rc = rescale_impl(h, d_band, nrows, ncols, R, bin_offset, d_start, d_end, n, out, out + RR, out + 2 * RR, stream,
-                    err, errlen);
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  int rc = modle_pixels_detail::resolve_band(h, d_band, nrows, ncols, cs, &v, st, err, errlen);
   if (rc != MODLE_PIXELS_OK) return rc;
-  PIX_TRY(hipMemcpyAsync(h->rescale_out.host, out, (2 * RR + 1) * 8, hipMemcpyDeviceToHost, stream));
-  PIX_TRY(hipStreamSynchronize(stream));
-  *pile = h->rescale_out.host;
-  *area = h->rescale_out.host + RR;
-  *n_used = h->rescale_out.host + 2 * RR;
+  const uint64_t RR = R * R;
+  rc = modle_pixels_detail::sums_to_host(h, 2 * RR + 1, pile, st, err, errlen, [&](uint64_t* d_out) {
+    const int64_t* d[2];
+    const int up = modle_pixels_detail::upload_lists(h, start, end, n, d, st, err, errlen);
+    if (up != MODLE_PIXELS_OK) return up;
+    return rescale_impl(h, v.d, v.nrows, v.ncols, R, bin_offset, d[0], d[1], n, d_out, d_out + RR, d_out + 2 * RR, st,
+                        err, errlen);
+  });
+  if (rc != MODLE_PIXELS_OK) return rc;
+  *area = *pile + RR;
+  *n_used = *pile + 2 * RR;
   return MODLE_PIXELS_OK;
 }
 
@@ -252,15 +257,9 @@ extern "C" int modle_pixels_rescale(modle_pixels_handle* h, const uint32_t* d_ba
     set_err(err, errlen, std::string("modle_pixels_rescale: invalid argument ") + kRule);
     return MODLE_PIXELS_ERR_ARG;
   }
-  const uint64_t nb = modle_pixels_detail::band_bytes(nrows, ncols), np = size * size * 8,
-                 nr = d_area != nullptr ? np : 0, nu = d_n_used != nullptr ? 8 : 0, nw = n * 8;
-  const void* ins[3] = {d_band, d_start, d_end};
-  const uint64_t in_bytes[3] = {nb, nw, nw};
-  bool clash = overlap(d_pile, np, d_area, nr) || overlap(d_pile, np, d_n_used, nu) || overlap(d_area, nr, d_n_used, nu);
-  for (int k = 0; k < 3; ++k)
-    clash = clash || overlap(d_pile, np, ins[k], in_bytes[k]) || overlap(d_area, nr, ins[k], in_bytes[k]) ||
-            overlap(d_n_used, nu, ins[k], in_bytes[k]);
-  if (clash) {
+  const uint64_t nb = modle_pixels_detail::band_bytes(nrows, ncols), np = size * size * 8;
+  if (modle_pixels_detail::any_overlap({{d_pile, np}, {d_area, np}, {d_n_used, 8}},
+                                       {{d_band, nb}, {d_start, n * 8}, {d_end, n * 8}})) {
     set_err(err, errlen, "modle_pixels_rescale: an output overlaps the band, the windows or another output");
     return MODLE_PIXELS_ERR_ARG;
   }
@@ -273,16 +272,8 @@ extern "C" int modle_pixels_rescale_to_host(modle_pixels_handle* h, const uint32
                                             const int64_t* end, uint64_t n, const uint64_t** pile,
                                             const uint64_t** area, const uint64_t** n_used, void* stream, char* err,
                                             size_t errlen) {
-  if (pile != nullptr) *pile = nullptr;
-  if (area != nullptr) *area = nullptr;
-  if (n_used != nullptr) *n_used = nullptr;
-  if (h == nullptr || d_band == nullptr || pile == nullptr || area == nullptr || n_used == nullptr ||
-      bad_rescale(nrows, ncols, size, n) || (n != 0 && (start == nullptr || end == nullptr))) {
-    set_err(err, errlen, std::string("modle_pixels_rescale_to_host: invalid argument ") + kRule);
-    return MODLE_PIXELS_ERR_ARG;
-  }
-  return rescale_to_host(h, d_band, nrows, ncols, size, bin_offset, start, end, n, pile, area, n_used,
-                         static_cast<hipStream_t>(stream), err, errlen);
+  return rescale_one_call("modle_pixels_rescale_to_host", nullptr, h, d_band, nrows, ncols, size, bin_offset, start, end,
+                          n, pile, area, n_used, stream, err, errlen);
 }
 
 extern "C" int modle_pixels_coarse_rescale_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
@@ -290,22 +281,7 @@ extern "C" int modle_pixels_coarse_rescale_to_host(modle_pixels_handle* h, const
                                                    int64_t bin_offset, const int64_t* start, const int64_t* end,
                                                    uint64_t n, const uint64_t** pile, const uint64_t** area,
                                                    const uint64_t** n_used, void* stream, char* err, size_t errlen) {
-  if (pile != nullptr) *pile = nullptr;
-  if (area != nullptr) *area = nullptr;
-  if (n_used != nullptr) *n_used = nullptr;
-  uint64_t nr = 0, nc = 0;
-  // (modle_pixels_coarse_shape refuses what modle_pixels_coarsen refuses of shape and factor)
-  if (h == nullptr || d_band == nullptr || pile == nullptr || area == nullptr || n_used == nullptr ||
-      modle_pixels_coarse_shape(nrows, ncols, factor, first_bin, &nr, &nc) != MODLE_PIXELS_OK ||
-      bad_rescale(nr, nc, size, n) || (n != 0 && (start == nullptr || end == nullptr))) {
-    set_err(err, errlen, std::string("modle_pixels_coarse_rescale_to_host: invalid argument (factor >= 2; of the "
-                                     "coarse band:) ") + kRule);
-    return MODLE_PIXELS_ERR_ARG;
-  }
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = modle_pixels_detail::coarsen_to_scratch(h, d_band, nrows, ncols, factor, first_bin, nr, nc, st, err,
-                                                         errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  return rescale_to_host(h, h->coarse.dev, nr, nc, size, bin_offset, start, end, n, pile, area, n_used, st, err,
-                         errlen);
+  const modle_pixels_detail::CoarseSpec cs{factor, first_bin};
+  return rescale_one_call("modle_pixels_coarse_rescale_to_host", &cs, h, d_band, nrows, ncols, size, bin_offset, start,
+                          end, n, pile, area, n_used, stream, err, errlen);
 }

@@ -154,7 +154,6 @@ __global__ __launch_bounds__(kThreads) void pixels_sample(const u32* __restrict_
   }
 }
 
-using modle_pixels_detail::overlap;
 using modle_pixels_detail::set_err;
 
 constexpr u64 kTwo32 = 1ull << 32;
@@ -238,8 +237,7 @@ extern "C" int modle_pixels_sample(modle_pixels_handle* h, const uint32_t* d_ban
                   err, errlen);
   if (rc != MODLE_PIXELS_OK) return rc;
   const u64 nb = modle_pixels_detail::band_bytes(nrows, ncols);
-  if ((d_kept != nullptr && overlap(d_kept, nb, d_band, nb)) || (d_rest != nullptr && overlap(d_rest, nb, d_band, nb)) ||
-      (d_kept != nullptr && d_rest != nullptr && overlap(d_kept, nb, d_rest, nb))) {
+  if (modle_pixels_detail::any_overlap({{d_kept, nb}, {d_rest, nb}}, {{d_band, nb}})) {
     set_err(err, errlen, "modle_pixels_sample: an output overlaps the band or the other output");
     return MODLE_PIXELS_ERR_ARG;
   }

@@ -335,8 +335,7 @@ extern "C" int modle_pixels_scc(modle_pixels_handle* h, const uint32_t* d_ref, c
     return MODLE_PIXELS_ERR_ARG;
   }
   const uint64_t band = modle_pixels_detail::band_bytes(nrows, ncols);
-  if (modle_pixels_detail::overlap(d_out, out_words * 8, d_ref, band) ||
-      modle_pixels_detail::overlap(d_out, out_words * 8, d_tgt, band)) {
+  if (modle_pixels_detail::any_overlap({{d_out, out_words * 8}}, {{d_ref, band}, {d_tgt, band}})) {
     set_err(err, errlen, "modle_pixels_scc: the output overlaps a band");
     return MODLE_PIXELS_ERR_ARG;
   }
@@ -355,14 +354,7 @@ extern "C" int modle_pixels_scc_to_host(modle_pixels_handle* h, const uint32_t* 
     return MODLE_PIXELS_ERR_ARG;
   }
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  const uint64_t words = uint64_t{kWords} * nrows;
-  PIX_TRY(hipSetDevice(h->device));
-  int rc = h->scc.ensure(words, err, errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  rc = scc_impl(h, d_ref, d_tgt, nrows, ncols, smooth, min_diag, max_diag, h->scc.dev, st, err, errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  PIX_TRY(hipMemcpyAsync(h->scc.host, h->scc.dev, words * 8, hipMemcpyDeviceToHost, st));
-  PIX_TRY(hipStreamSynchronize(st));
-  *rows = h->scc.host;
-  return MODLE_PIXELS_OK;
+  return modle_pixels_detail::sums_to_host(h, uint64_t{kWords} * nrows, rows, st, err, errlen, [&](uint64_t* d_out) {
+    return scc_impl(h, d_ref, d_tgt, nrows, ncols, smooth, min_diag, max_diag, d_out, st, err, errlen);
+  });
 }

@@ -343,8 +343,7 @@ extern "C" int modle_pixels_stripes(modle_pixels_handle* h, const uint32_t* d_re
     return MODLE_PIXELS_ERR_ARG;
   }
   const uint64_t band = modle_pixels_detail::band_bytes(nrows, ncols);
-  if (modle_pixels_detail::overlap(d_out, out_words * 8, d_ref, band) ||
-      modle_pixels_detail::overlap(d_out, out_words * 8, d_tgt, band)) {
+  if (modle_pixels_detail::any_overlap({{d_out, out_words * 8}}, {{d_ref, band}, {d_tgt, band}})) {
     set_err(err, errlen, "modle_pixels_stripes: the output overlaps a band");
     return MODLE_PIXELS_ERR_ARG;
   }
@@ -361,13 +360,7 @@ extern "C" int modle_pixels_stripes_to_host(modle_pixels_handle* h, const uint32
   }
   const hipStream_t st = static_cast<hipStream_t>(stream);
   const uint64_t words = 2 * static_cast<uint64_t>(rows_of(what)) * ncols;
-  PIX_TRY(hipSetDevice(h->device));
-  int rc = h->stripes.ensure(words, err, errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  rc = stripes_impl(h, d_ref, d_tgt, nrows, ncols, what, h->stripes.dev, st, err, errlen);
-  if (rc != MODLE_PIXELS_OK) return rc;
-  PIX_TRY(hipMemcpyAsync(h->stripes.host, h->stripes.dev, words * 8, hipMemcpyDeviceToHost, st));
-  PIX_TRY(hipStreamSynchronize(st));
-  *rows = h->stripes.host;
-  return MODLE_PIXELS_OK;
+  return modle_pixels_detail::sums_to_host(h, words, rows, st, err, errlen, [&](uint64_t* d_out) {
+    return stripes_impl(h, d_ref, d_tgt, nrows, ncols, what, d_out, st, err, errlen);
+  });
 }

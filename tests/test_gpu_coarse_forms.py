@@ -1,7 +1,8 @@
 """The composites of libmodle_pixels.so on the MI355X (include/modle_pixels.h: modle_pixels_coarse_to_host,
-_coarse_marginals_to_host, _coarse_insulation_to_host, _coarse_dots_to_host, _coarse_pileup_to_host) are the
-fine one-call form on the coarsened band, word for word: the reference of every case is coarsen_into a
-caller-owned buffer and then extract, marginals, insulation, dots and pileup on that buffer.  On ONE
+_coarse_marginals_to_host, _coarse_insulation_to_host, _coarse_dots_to_host, _coarse_pileup_to_host,
+_coarse_dot_hist_to_host, _coarse_dots_fdr_to_host, _coarse_rescale_to_host) are the fine one-call form on the
+coarsened band, word for word: the reference of every case is coarsen_into a caller-owned buffer and then extract,
+marginals, insulation, dots, pileup, dot_hist, dots_fdr and rescale on that buffer.  On ONE
 pixels.Extractor the composites then run on two bands of one shape and different content, alternating
 between the bands from one analysis to the next, so a composite that skipped its coarsening, sized the
 scratch band by the fine shape or mixed up `factor` and `first_bin` would hand back the other band's, or
@@ -20,6 +21,8 @@ CASES = {(2, 0): (12, 35), (2, 5): (12, 36), (3, 4): (9, 24)}
 W, P, MIN_COUNT = 1, 0, 1  # dots with min_diag 0: 5 diagonals
 FOLDS = (0.5, 0.5, 0.5, 0.5)  # half of what the neighbourhoods expect: a band without structure still has dots
 WINDOWS, FLANK = [1, 2], 1
+N_OBS, FDR, SIZE = 33, 0.1, 2  # the histogram's counts, the rate of its thresholds, the grid of the rescaled pileup
+NAMES = ("extract", "marginals", "insulation", "dots", "pileup", "dot_hist", "dots_fdr", "rescale", "dots_fdr_scaled")
 OFFSET = 7  # bin_offset of the pixels and the dots
 
 
@@ -29,6 +32,13 @@ def anchors(nr, nc):
     a = np.array([1, 2, 3, 5, 7, 0, 4, nc - 2, nc - 1, 6, 3, 8], dtype=np.int64)
     d = np.array([0, 1, 2, 3, 6, 0, nr, 0, 0, -1, 4, 5], dtype=np.int64)
     return a, a + d
+
+
+def windows(nr):
+    """windows [start, end) of the coarse band of widths 1, 2, 3, 5, nr and nr + 1 and one that starts before the
+    band: some are accepted, some refused (rescale_accepts)"""
+    start = np.array([1, 2, 3, 4, 0, 0, -1], dtype=np.int64)
+    return start, start + np.array([1, 2, 3, 5, nr, nr + 1, 3], dtype=np.int64)
 
 
 def same(got, want):
@@ -41,7 +51,7 @@ def same(got, want):
 
 
 def fine_forms(ex, d_band, factor, first_bin):
-    """the five analyses of the band at `factor` times its bin size, by the fine forms on a coarsened copy"""
+    """the eight analyses of the band at `factor` times its bin size, by the fine forms on a coarsened copy"""
     from modle_amd import pixels
 
     nr, nc = CASES[(factor, first_bin)]
@@ -58,6 +68,18 @@ def fine_forms(ex, d_band, factor, first_bin):
             "scale": pixels.dot_scales(diag_sum, nc, W, P, FOLDS, 0),
             "pileup": ex.pileup(ptr, nr, nc, FLANK, a, b)}
     want["dots"] = ex.dots(ptr, nr, nc, W, P, 0, MIN_COUNT, want["scale"], OFFSET)
+    want["lam"] = pixels.dot_scales(diag_sum, nc, W, P, (1.0, 1.0, 1.0, 1.0), 0)
+    want["dot_hist"] = ex.dot_hist(ptr, nr, nc, W, P, 0, want["lam"], None, N_OBS)
+    want["thr"] = pixels.dot_thresholds(want["dot_hist"], pixels.dot_lambda_edges(), FDR)
+    want["dots_fdr"] = ex.dots_fdr(ptr, nr, nc, W, P, 0, MIN_COUNT, want["lam"], None, want["thr"], None, OFFSET)
+    want["dots_fdr_scaled"] = ex.dots_fdr(ptr, nr, nc, W, P, 0, MIN_COUNT, want["lam"], None, want["thr"], want["scale"],
+                                          OFFSET)
+    s, e = windows(nr)
+    taken = pixels.rescale_accepts(nr, nc, SIZE, s, e)
+    assert 0 < taken.sum() < len(s)
+    want["rescale"] = ex.rescale(ptr, nr, nc, SIZE, s, e)
+    assert want["rescale"][2] == taken.sum() and want["rescale"][0].any() and want["dot_hist"].any()
+    assert want["dot_hist"].shape == (4, len(pixels.dot_lambda_edges()) + 1, N_OBS)
     assert scratch.guards_intact()
     assert want["extract"].stats.nnz > 0 and want["dots"].stats.nnz > 0 and want["pileup"][1] == ok.sum() and want["pileup"][0].any()
     assert want["extract"].bin1_offset.shape == (nc + 1,) and want["insulation"].shape == (2, nc)
@@ -76,24 +98,33 @@ def test_a_composite_is_the_fine_form_on_the_coarsened_band():
             want = [fine_forms(ex, d, factor, first_bin) for d in d_bands]
             assert not same(want[0]["extract"], want[1]["extract"])  # the bands tell each other apart
             a, b = anchors(nr, nc)
+            s, e = windows(nr)
             shape = (NROWS, NCOLS, factor, first_bin)
             at = dict(factor=factor, first_bin=first_bin)
             for keywords in (False, True):
-                for x, y in ((0, 1), (1, 0)):  # A, B, A, B, A across the analyses, then exchanged
+                for x, y in ((0, 1), (1, 0)):  # A, B, A, B, ... across the analyses, then exchanged
                     px, py, wx, wy = d_bands[x].data_ptr(), d_bands[y].data_ptr(), want[x], want[y]
+                    fdr = (W, P, 0, MIN_COUNT, wx["lam"], None, wx["thr"])
                     if keywords:
                         got = [ex.extract(px, NROWS, NCOLS, OFFSET, **at),
                                ex.marginals(py, NROWS, NCOLS, 1, **at),
                                ex.insulation(px, NROWS, NCOLS, WINDOWS, 1, **at),
                                ex.dots(py, NROWS, NCOLS, W, P, 0, MIN_COUNT, wy["scale"], OFFSET, **at),
-                               ex.pileup(px, NROWS, NCOLS, FLANK, a, b, **at)]
+                               ex.pileup(px, NROWS, NCOLS, FLANK, a, b, **at),
+                               ex.dot_hist(py, NROWS, NCOLS, W, P, 0, wy["lam"], None, N_OBS, **at),
+                               ex.dots_fdr(px, NROWS, NCOLS, *fdr, None, OFFSET, **at),
+                               ex.rescale(py, NROWS, NCOLS, SIZE, s, e, **at),
+                               ex.dots_fdr(px, NROWS, NCOLS, *fdr, wx["scale"], OFFSET, **at)]
                     else:
                         got = [ex.coarse_extract(px, *shape, OFFSET),
                                ex.coarse_marginals(py, *shape, 1),
                                ex.coarse_insulation(px, *shape, WINDOWS, 1),
                                ex.coarse_dots(py, *shape, W, P, 0, MIN_COUNT, wy["scale"], OFFSET),
-                               ex.coarse_pileup(px, *shape, FLANK, a, b)]
-                    for name, g, w in zip(("extract", "marginals", "insulation", "dots", "pileup"), got,
-                                          (wx["extract"], wy["marginals"], wx["insulation"], wy["dots"], wx["pileup"])):
-                        assert same(g, w), (factor, first_bin, keywords, x, name)
+                               ex.coarse_pileup(px, *shape, FLANK, a, b),
+                               ex.coarse_dot_hist(py, *shape, W, P, 0, wy["lam"], None, N_OBS),
+                               ex.coarse_dots_fdr(px, *shape, *fdr, None, OFFSET),
+                               ex.coarse_rescale(py, *shape, SIZE, s, e),
+                               ex.coarse_dots_fdr(px, *shape, *fdr, wx["scale"], OFFSET)]
+                    for n, (name, g) in enumerate(zip(NAMES, got)):
+                        assert same(g, (wx, wy)[n % 2][name]), (factor, first_bin, keywords, x, name)
     assert d_bands[0].unchanged() and d_bands[1].unchanged()
