@@ -189,7 +189,10 @@ int modle_hip_submit_tasks(modle_hip_handle* h, int interval_id, const modle_hip
  * (MODLE_HIP_TAIL_HELPERS=0 turns that off).  Since round 5 the library holds the kernels for 8 and for 12 waves per
  * workgroup and for 16-bit and 32-bit LEF ids and moves (modle_hip_size_class): a launch that fills the GPU and whose
  * epochs re-insert few units runs the 12-wave ones; MODLE_HIP_WAVES=8 / 12 and MODLE_HIP_SIZE_CLASS=wide force the
- * choice (A/B measurements, tests); modle_hip_last_launch_info says what ran.  None of it shows in the results. */
+ * choice (A/B measurements, tests); modle_hip_last_launch_info says what ran.  None of it shows in the results.
+ * The rule itself -- thresholds, order of precedence of the overrides, the measurements behind them -- is stated
+ * once, as `modle_host::plan_launch` (modle_amd/csrc/launch_common.hpp); modle_hip_plan_launch evaluates it
+ * without a device. */
 int modle_hip_launch(modle_hip_handle* h, void* stream, char* err, size_t errlen);
 /* Waits for the launch and collects per-task results (the counterpart of _ctx.shutdown(),
  * scheduler_simulate.cpp:162).  The wait is bounded: when the launch has been running for longer
@@ -224,6 +227,12 @@ typedef struct modle_hip_launch_info {
   uint64_t workspace_probe_worst_us; /* ... and on the slowest candidate */
 } modle_hip_launch_info;
 int modle_hip_last_launch_info(modle_hip_handle* h, modle_hip_launch_info* info);
+/* How modle_hip_launch would lay out `n_tasks` tasks whose largest cell has `max_lefs` LEFs on a device with
+ * `num_cus` compute units (no GPU needed): the launch's own rule, with the environment read as a launch reads it
+ * (MODLE_HIP_GRID, _WAVES, _PAIRED, _TAIL_HELPERS, _ACTIVE_WAVES, _SIZE_CLASS, at every call).  Fills the
+ * geometry fields of `out`; the three workspace fields are 0 (a plan places no workspace). */
+int modle_hip_plan_launch(const modle_hip_config* c, uint64_t n_tasks, uint64_t num_cus, uint64_t max_lefs,
+                          modle_hip_launch_info* out);
 /* Size class of a launch whose largest cell has `max_lefs` LEFs: 0 = NARROW (the kernels keep LEF ids and
  * moves as 16-bit values: fewer than 65 536 LEFs and extrusion speeds whose moves provably fit; every
  * real chromosome at the reference's defaults), 1 = WIDE (32-bit).  modle_hip_launch picks it per launch;

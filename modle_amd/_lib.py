@@ -26,7 +26,7 @@ EXPORTS = [
     "modle_hip_cancel", "modle_hip_test_units", "modle_hip_interval_done",
     "modle_hip_enable_state_log", "modle_hip_get_state_log", "modle_hip_set_wait_timeout",
     "modle_hip_last_launch_info",
-    "modle_hip_runtime_versions", "modle_hip_size_class",
+    "modle_hip_runtime_versions", "modle_hip_size_class", "modle_hip_plan_launch",
 ]
 
 u64p = np.ctypeslib.ndpointer(dtype=np.uint64, flags="C_CONTIGUOUS")
@@ -138,6 +138,7 @@ def lib():
     L.modle_hip_wait.argtypes = [C.c_void_p] + err
     L.modle_hip_set_wait_timeout.argtypes = [C.c_void_p, C.c_double]
     L.modle_hip_last_launch_info.argtypes = [C.c_void_p, P(LaunchInfo)]
+    L.modle_hip_plan_launch.argtypes = [P(Config), C.c_uint64, C.c_uint64, C.c_uint64, P(LaunchInfo)]
     L.modle_hip_last_kernel_ms.argtypes = [C.c_void_p, P(C.c_float)]
     L.modle_hip_get_results.argtypes = [C.c_void_p, C.c_int, P(CellResult), C.c_size_t]
     L.modle_hip_interval_outputs.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p), P(C.c_void_p),

@@ -102,6 +102,16 @@ def make_tasks(cfg, name, chrom_size, start, end, first_task_id=0):
     return tasks
 
 
+def plan_launch(cfg, n_tasks, num_cus, max_lefs):
+    """How a launch of `n_tasks` tasks (largest cell: `max_lefs` LEFs) would be laid out on a device with `num_cus`
+    compute units, environment included: a dict with the keys of `Simulator.launch_info()`, the workspace fields 0.
+    No GPU needed (modle_hip_plan_launch; the rule: modle_host::plan_launch, launch_common.hpp)."""
+    info = LaunchInfo()
+    if lib().modle_hip_plan_launch(C.byref(cfg), int(n_tasks), int(num_cus), int(max_lefs), C.byref(info)) < 0:
+        raise ModleHipError("modle_hip_plan_launch failed", ERR_ARG)
+    return {name: int(getattr(info, name)) for name, _ in LaunchInfo._fields_}
+
+
 def stp_active_from_occupancy(stp_inactive, occupancy):
     return lib().modle_hip_stp_active_from_occupancy(stp_inactive, occupancy)
 

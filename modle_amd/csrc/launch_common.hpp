@@ -88,6 +88,73 @@ inline int size_class_required(const modle_hip_config& c, uint64_t max_lefs) {
   return std::max(own, pair) <= 65533.0 ? 0 : 1;  // (MOVE_LIMIT of the NARROW class)
 }
 
+// ---- how a launch is laid out on the GPU: THE statement of the rule ----
+// What the environment may force (tests, A/B measurements, diagnostics; modle_hip.hip reads it once per launch).
+struct LaunchOverrides {
+  int grid_cap = 0;              // MODLE_HIP_GRID >= 1: at most that many workgroups
+  int waves = 0;                 // MODLE_HIP_WAVES: 8 or 12 (anything else: the rule decides)
+  int paired = -1;               // MODLE_HIP_PAIRED: -1 unset or empty, 0 fixed roles off, 1 on
+  bool no_tail_helpers = false;  // MODLE_HIP_TAIL_HELPERS=0
+  int active_waves = 0;          // MODLE_HIP_ACTIVE_WAVES in [1, waves]: only that many waves pull tasks
+  bool wide = false;             // MODLE_HIP_SIZE_CLASS=wide
+};
+// What a measurement or diagnostic build of the library forces (the default build: nothing).
+struct LaunchBuild {
+  bool eight_waves_only = false;  // the build has no 12-wave geometry on its host side
+  bool no_helpers = false;        // neither fixed roles nor tail helpers
+  bool no_prng_producer = false;  // the generator policy has no block producer
+};
+struct LaunchPlan {
+  uint32_t grid = 1;          // persistent workgroups
+  uint32_t waves = 8;         // per workgroup: which pair of kernels (sim_launch.h)
+  uint32_t pair_mains = 0;    // != 0: fixed roles (sim_pair.h) with that many main waves per workgroup
+  uint32_t tail_helpers = 0;  // waves that find the queue empty help a running cell of their workgroup
+  uint32_t active_waves = 8;  // waves of a workgroup that pull tasks
+  bool wide = false;          // size class (size_class_required)
+  // modle_hip_launch_info's view of the same:
+  uint32_t main_waves_per_workgroup = 8, helper_waves = 0, prng_producer_waves = 0;
+};
+
+// Pure: the same answer on the host of a launch, in the CPU tests (modle_hip_plan_launch) and on paper.
+inline LaunchPlan plan_launch(uint64_t n_tasks, uint64_t num_cus, uint64_t max_lefs, const modle_hip_config& c,
+                              const LaunchOverrides& o, const LaunchBuild& b = LaunchBuild{}) {
+  LaunchPlan p;
+  // Workgroups: one per CU even when there are fewer tasks than waves -- the waves that win a task are then spread
+  // over all CUs instead of being packed 8 to a CU.  MODLE_HIP_GRID (diagnostic): fewer workgroups than CUs (what
+  // do the waves of a CU share, what do the CUs share?)
+  uint64_t grid = std::max<uint64_t>(1, std::min(num_cus, n_tasks));
+  if (o.grid_cap >= 1) grid = std::min<uint64_t>(grid, static_cast<uint64_t>(o.grid_cap));
+  p.grid = static_cast<uint32_t>(grid);
+  // Waves per workgroup (round 5): 12 -- three per SIMD, 168 VGPRs, 256-output PRNG blocks, 256-key LDS buffers -- is
+  // worth 1.2 % on a launch that fills the slots and whose epochs re-insert few units (the default parameters: 70 - 134
+  // per epoch on chr1); a launch whose epochs re-insert more than the small buffers hold (BASELINE configs[4]: 600 - 800)
+  // loses 17 % with them, and the fixed roles of a launch that leaves slots empty are laid out for 8.  Expected
+  // re-insertions per epoch and direction ~ LEFs x release probability.  MODLE_HIP_WAVES=8 / 12 forces it; helper-wave
+  // mode asked for by name (MODLE_HIP_PAIRED=1) means the kernels that have it.
+  constexpr uint64_t kMaxMains = 4;  // (of the 8 waves of the kernels that know fixed roles)
+  const bool leaves_slots_empty = n_tasks <= grid * kMaxMains;
+  const double p_release = std::max(c.prob_of_lef_release, c.prob_of_lef_release_burnin);
+  if (!leaves_slots_empty && n_tasks >= grid * 12 && static_cast<double>(max_lefs) * p_release < 170.0) p.waves = 12;
+  if (o.waves == 8 || o.waves == 12) p.waves = static_cast<uint32_t>(o.waves);
+  if (o.paired == 1 || b.eight_waves_only) p.waves = 8;
+  // Fixed roles -- a helper wave per cell, and a PRNG producer per cell while there are waves to spare -- for launches
+  // that leave at least half of the wave slots empty; MODLE_HIP_PAIRED=0 / 1 turns them off / on whatever the number
+  // of tasks.  Every other launch: tail helpers.
+  bool paired = p.waves == 8 && leaves_slots_empty;
+  if (o.paired >= 0) paired = o.paired != 0;
+  if (b.no_helpers) paired = false;
+  if (paired && p.waves == 8) p.pair_mains = static_cast<uint32_t>(std::min(kMaxMains, (n_tasks + grid - 1) / grid));
+  p.tail_helpers = (p.pair_mains == 0 && !o.no_tail_helpers && !b.no_helpers) ? 1u : 0u;
+  // MODLE_HIP_ACTIVE_WAVES (diagnostic): how the kernel time scales with the waves in flight per CU
+  p.active_waves = (o.active_waves >= 1 && static_cast<uint32_t>(o.active_waves) <= p.waves)
+                       ? static_cast<uint32_t>(o.active_waves) : p.waves;
+  p.wide = o.wide || size_class_required(c, max_lefs) != 0;
+  p.main_waves_per_workgroup = p.pair_mains != 0 ? p.pair_mains : p.active_waves;
+  p.helper_waves = p.pair_mains != 0 ? 1 : 0;
+  p.prng_producer_waves = (p.pair_mains != 0 && p.pair_mains <= 2 && !b.no_prng_producer) ? 1 : 0;
+  return p;
+}
+
 inline uint32_t pos_to_dev(uint64_t v) {
   return v == UINT64_MAX ? modle_dev::UNBOUND : static_cast<uint32_t>(v);
 }

@@ -160,6 +160,31 @@ struct modle_hip_handle {
   modle_hip_launch_info last_launch{};
 };
 
+namespace {
+
+std::chrono::steady_clock::duration as_duration(double seconds) {
+  return std::chrono::duration_cast<std::chrono::steady_clock::duration>(std::chrono::duration<double>(seconds));
+}
+
+// Polls `stream` (no HIP call waits with a deadline) until it is idle -- hipSuccess --, it reports an error, or
+// `give_up` (nullptr: never) has passed: hipErrorNotReady.  The first kYieldPolls polls of a caller's count only
+// yield between two queries, the later ones sleep 200 us.
+constexpr unsigned kYieldPolls = 4096;
+hipError_t poll_stream(hipStream_t stream, const std::chrono::steady_clock::time_point* give_up, unsigned& polls) {
+  for (;;) {
+    const hipError_t q = hipStreamQuery(stream);
+    if (q != hipErrorNotReady) return q;
+    if (give_up != nullptr && std::chrono::steady_clock::now() > *give_up) return hipErrorNotReady;
+    if (++polls < kYieldPolls) {
+      std::this_thread::yield();
+    } else {
+      std::this_thread::sleep_for(std::chrono::microseconds(200));
+    }
+  }
+}
+
+}  // namespace
+
 extern "C" {
 
 modle_hip_handle* modle_hip_create(const modle_hip_config* c, int device, char* err,
@@ -240,20 +265,9 @@ void modle_hip_destroy(modle_hip_handle* h) {
       std::lock_guard<std::mutex> lock(h->abort_mu);
       __atomic_store_n(h->h_abort, 1u, __ATOMIC_RELEASE);
     }
-    const auto give_up = std::chrono::steady_clock::now() +
-                         std::chrono::duration_cast<std::chrono::steady_clock::duration>(
-                             std::chrono::duration<double>(h->drain_timeout_s));
-    bool drained = false;
-    for (;;) {
-      const hipError_t q = hipStreamQuery(h->stream);
-      if (q == hipSuccess) {
-        drained = true;
-        break;
-      }
-      if (q != hipErrorNotReady || std::chrono::steady_clock::now() > give_up) break;
-      std::this_thread::sleep_for(std::chrono::microseconds(200));
-    }
-    if (!drained) {
+    const auto give_up = std::chrono::steady_clock::now() + as_duration(h->drain_timeout_s);
+    unsigned polls = kYieldPolls;  // (nobody waits for the result: a nap between any two polls)
+    if (poll_stream(h->stream, &give_up, polls) != hipSuccess) {
       (void)hipGetLastError();
       std::fprintf(stderr, "modle_hip_destroy: the launch in flight did not drain within %.0f s of the abort word; "
                            "the handle's device memory is leaked (hung device: exit the process)\n",
@@ -465,17 +479,87 @@ static hipError_t place_workspace(modle_hip_handle* h, size_t slot_stride, int g
   return hipSuccess;
 }
 
-int modle_hip_launch(modle_hip_handle* h, void* stream, char* err, size_t errlen) {
-  if (h == nullptr) return MODLE_HIP_ERR_ARG;
-  if (h->in_flight) {
-    set_err(err, errlen, "a launch is already in flight");
-    return MODLE_HIP_ERR_STATE;
-  }
-  HIP_TRY(hipSetDevice(h->device));
-  h->stream = static_cast<hipStream_t>(stream);
-  // Gather pending tasks, largest chromosomes first (long tasks must not start last).  Nothing
-  // of the handle's bookkeeping changes until the kernel has been enqueued: a launch that fails
-  // on the way leaves every task pending and every result slot as it was.
+}  // extern "C"
+
+namespace {
+
+// ---------------------------------------------------------------------------------------------
+// modle_hip_launch, step by step (the order of the HIP calls is the order of the steps)
+// ---------------------------------------------------------------------------------------------
+// What the environment says about a launch, read ONCE per launch (and at every launch: tests and A/B runs change
+// it between the launches of one process).  The layout's share goes to modle_host::plan_launch as it is.
+struct LaunchEnv {
+  modle_host::LaunchOverrides layout;
+  bool poison_workspace = false;    // MODLE_HIP_POISON_WORKSPACE (tests)
+  const char* trace_shm = nullptr;  // MODLE_HIP_TRACE_SHM (diagnostic): file the trace of task 0 is mapped to
+  u32 test_fault = 0;               // MODLE_HIP_TEST_FAULT (tests/test_gpu_wait_deadline.py)
+  u32 exp_flags = 0;                // MODLE_HIP_EXP (MODLE_EXP_SWITCH builds)
+};
+
+LaunchEnv read_launch_env() {
+  const auto number = [](const char* name) {
+    const char* v = std::getenv(name);
+    return v != nullptr ? std::atoi(v) : 0;
+  };
+  const auto first_char = [](const char* name) {  // ('\0': unset or empty)
+    const char* v = std::getenv(name);
+    return v != nullptr ? v[0] : '\0';
+  };
+  LaunchEnv e;
+  e.layout.grid_cap = number("MODLE_HIP_GRID");
+  e.layout.waves = number("MODLE_HIP_WAVES");
+  if (const char pm = first_char("MODLE_HIP_PAIRED"); pm != '\0') e.layout.paired = pm != '0' ? 1 : 0;
+  e.layout.no_tail_helpers = first_char("MODLE_HIP_TAIL_HELPERS") == '0';
+  e.layout.active_waves = number("MODLE_HIP_ACTIVE_WAVES");
+  e.layout.wide = first_char("MODLE_HIP_SIZE_CLASS") == 'w';
+  const char poison = first_char("MODLE_HIP_POISON_WORKSPACE");
+  e.poison_workspace = poison != '\0' && poison != '0';
+  e.trace_shm = std::getenv("MODLE_HIP_TRACE_SHM");
+  if (const char* tf = std::getenv("MODLE_HIP_TEST_FAULT"); tf != nullptr && std::strcmp(tf, "stuck_helper") == 0)
+    e.test_fault = TEST_FAULT_STUCK_HELPER;
+  e.exp_flags = static_cast<u32>(number("MODLE_HIP_EXP"));
+  return e;
+}
+
+// what this build of the library forces on the layout (modle_host::plan_launch knows no build switch)
+constexpr modle_host::LaunchBuild launch_build() {
+  modle_host::LaunchBuild b;
+#if defined(MODLE_EXP_LDS_WS) || defined(MODLE_STAGE_TRACE) || (MODLE_WAVES_PER_CU != 8)
+  b.eight_waves_only = true;  // (measurement / diagnostic builds)
+#endif
+#ifdef MODLE_STAGE_TRACE
+  b.no_helpers = true;  // (the stage trace records the generator position between the phases)
+#endif
+#ifdef MODLE_RNG_PHILOX
+  b.no_prng_producer = true;
+#endif
+  return b;
+}
+
+// the plan as modle_hip_launch_info states it (the workspace fields: 0, a plan places nothing)
+modle_hip_launch_info launch_info_of(const modle_host::LaunchPlan& p, uint64_t n_tasks, uint64_t num_cus) {
+  modle_hip_launch_info info{};
+  info.n_tasks = n_tasks;
+  info.num_cus = num_cus;
+  info.workgroups = p.grid;
+  info.waves_per_workgroup = p.waves;
+  info.main_waves_per_workgroup = p.main_waves_per_workgroup;
+  info.helper_waves = p.helper_waves;
+  info.prng_producer_waves = p.prng_producer_waves;
+  info.tail_helpers = p.tail_helpers;
+  info.size_class = p.wide ? 1 : 0;
+  return info;
+}
+
+// Step 1: the pending tasks of every interval in the order of the device's queue.
+struct PendingTasks {
+  std::vector<Task> tasks;                     // heaviest first
+  std::vector<std::pair<int, size_t>> map;     // launch slot -> (interval, submission index)
+  u32 max_lefs = 1, max_barriers = 0;
+};
+
+// Largest chromosomes first (long tasks must not start last): by LEFs + barriers, ties in submission order.
+PendingTasks gather_pending(const modle_hip_handle* h) {
   std::vector<Task> tasks;
   std::vector<std::pair<int, size_t>> launch_map;
   u32 max_lefs = 1, max_barriers = 0;
@@ -498,11 +582,6 @@ int modle_hip_launch(modle_hip_handle* h, void* stream, char* err, size_t errlen
     }
     if (!rec.pending.empty()) max_barriers = std::max<u32>(max_barriers, static_cast<u32>(rec.n_barriers));
   }
-  if (tasks.empty()) {
-    h->n_launched = 0;
-    h->launch_map.clear();
-    return MODLE_HIP_OK;
-  }
   std::vector<size_t> order(tasks.size());
   std::iota(order.begin(), order.end(), size_t(0));
   std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) {
@@ -512,13 +591,20 @@ int modle_hip_launch(modle_hip_handle* h, void* stream, char* err, size_t errlen
     const uint64_t wb = static_cast<uint64_t>(tasks[b].num_lefs) + ib.n_barriers;
     return wa > wb;
   });
-  std::vector<Task> sorted(tasks.size());
-  std::vector<std::pair<int, size_t>> sorted_map(tasks.size());
+  PendingTasks out;
+  out.tasks.resize(tasks.size());
+  out.map.resize(tasks.size());
   for (size_t i = 0; i < order.size(); ++i) {
-    sorted[i] = tasks[order[i]];
-    sorted_map[i] = launch_map[order[i]];
+    out.tasks[i] = tasks[order[i]];
+    out.map[i] = launch_map[order[i]];
   }
+  out.max_lefs = max_lefs;
+  out.max_barriers = max_barriers;
+  return out;
+}
 
+// Step 2: the intervals as the device reads them.
+std::vector<Interval> device_intervals(const modle_hip_handle* h) {
   std::vector<Interval> ivs(h->intervals.size());
   for (size_t iv = 0; iv < h->intervals.size(); ++iv) {
     const IntervalRec& rec = *h->intervals[iv];
@@ -541,33 +627,16 @@ int modle_hip_launch(modle_hip_handle* h, void* stream, char* err, size_t errlen
     d.bucket_shift = BAR_BUCKET_SHIFT;
     d.n_buckets = static_cast<u32>(rec.n_buckets);
   }
-  // one workgroup per CU even when there are fewer tasks than waves: the waves that win a task
-  // are then spread over all CUs instead of being packed 8 to a CU
-  int grid = std::max(1, static_cast<int>(std::min<size_t>(h->num_cus, sorted.size())));
-  if (const char* g = std::getenv("MODLE_HIP_GRID"); g != nullptr && std::atoi(g) >= 1) {
-    // diagnostic: fewer workgroups than CUs (what do the waves of a CU share, what do the CUs share?)
-    grid = std::min(grid, std::atoi(g));
-  }
-  const auto layout = modle_host::workspace_layout(max_lefs, max_barriers, h->params.hist_len);
-  // Waves per workgroup (round 5): 12 -- three per SIMD, 168 VGPRs, 256-output PRNG blocks, 256-key LDS buffers -- is
-  // worth 1.2 % on a launch that fills the slots and whose epochs re-insert few units (the default parameters: 70 - 134
-  // per epoch on chr1); a launch whose epochs re-insert more than the small buffers hold (BASELINE configs[4]: 600 - 800)
-  // loses 17 % with them, and the fixed roles of a launch that leaves slots empty are laid out for 8.  Expected
-  // re-insertions per epoch and direction ~ LEFs x release probability.  MODLE_HIP_WAVES=8 / 12 forces it.
-  int waves = 8;
-  {
-    const bool paired_launch = sorted.size() <= static_cast<size_t>(grid) * 4;
-    const double p_rel = std::max(h->params.p_release, h->params.p_release_burnin);
-    if (!paired_launch && sorted.size() >= static_cast<size_t>(grid) * 12 && static_cast<double>(max_lefs) * p_rel < 170.0)
-      waves = 12;
-    if (const char* e = std::getenv("MODLE_HIP_WAVES"); e != nullptr && (std::atoi(e) == 8 || std::atoi(e) == 12))
-      waves = std::atoi(e);
-    // (helper-wave mode asked for by name -- tests, A/B runs -- means the kernels that have it)
-    if (const char* pm = std::getenv("MODLE_HIP_PAIRED"); pm != nullptr && pm[0] != '\0' && pm[0] != '0') waves = 8;
-#if defined(MODLE_EXP_LDS_WS) || defined(MODLE_STAGE_TRACE) || (MODLE_WAVES_PER_CU != 8)
-    waves = 8;  // (measurement / diagnostic builds)
-#endif
-  }
+  return ivs;
+}
+
+// Step 4: everything the kernel reads is on the device when this returns -- buffers large enough, the workspace
+// placed, tasks and intervals uploaded, counters and status words reset.
+int stage_buffers(modle_hip_handle* h, const PendingTasks& pending, const std::vector<Interval>& ivs,
+                  const modle_host::LaunchPlan& plan, const modle_host::WorkspaceLayout& layout, const LaunchEnv& env,
+                  char* err, size_t errlen) {
+  const std::vector<Task>& sorted = pending.tasks;
+  const int grid = static_cast<int>(plan.grid), waves = static_cast<int>(plan.waves);
   const size_t n_slots = static_cast<size_t>(grid) * static_cast<size_t>(waves);
 #if defined(MODLE_EXP_LDS_WS) && !defined(MODLE_EXP_LDS_WS_OFF)
   if (layout.u32_words * 4 + layout.u8_bytes + layout.hit_words * 4 > static_cast<size_t>(MODLE_EXP_LDS_WS)) {
@@ -590,7 +659,7 @@ int modle_hip_launch(modle_hip_handle* h, void* stream, char* err, size_t errlen
   }
 #endif
   HIP_TRY(place_workspace(h, layout.total_bytes, grid, waves));
-  if (const char* e = std::getenv("MODLE_HIP_POISON_WORKSPACE"); e != nullptr && e[0] != '\0' && e[0] != '0') {
+  if (env.poison_workspace) {
     // tests: a cell must not depend on what its workspace slot held before (fresh device memory is usually zero, the
     // placement probe and earlier cells leave anything): every byte 0xA5 before the launch
     HIP_TRY(hipMemsetAsync(h->d_workspace.p, 0xA5, layout.total_bytes * n_slots, h->stream));
@@ -617,11 +686,55 @@ int modle_hip_launch(modle_hip_handle* h, void* stream, char* err, size_t errlen
   HIP_TRY(hipMemsetAsync(h->d_status.p, 0xFF, sorted.size() * 4, h->stream));
   // the source vectors must outlive the async copies
   HIP_TRY(hipStreamSynchronize(h->stream));
+  return MODLE_HIP_OK;
+}
 
-  SimArgs a;
+// MODLE_HIP_TRACE_SHM (diagnostic): the trace of task 0 goes to a file-backed, host-coherent mapping so that it
+// survives a GPU fault that aborts the process (mapped and registered once per handle).  A mapping that cannot be
+// made costs the trace, not the launch.
+void map_trace(modle_hip_handle* h, const char* shm, SimArgs& a) {
+  constexpr u32 kTraceEpochs = 4096;
+  const size_t bytes = static_cast<size_t>(kTraceEpochs) * TRACE_STAGES * TRACE_WORDS_PER_STAGE * 8;
+  if (h->trace_host == nullptr) {
+    const int fd = ::open(shm, O_RDWR | O_CREAT | O_TRUNC, 0644);
+    if (fd >= 0 && ::ftruncate(fd, static_cast<off_t>(bytes)) == 0) {
+      void* hp = ::mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
+      void* dp = nullptr;
+      if (hp != MAP_FAILED) {
+        if (hipHostRegister(hp, bytes, hipHostRegisterMapped) == hipSuccess &&
+            hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
+          h->trace_host = hp;
+          h->trace_bytes = bytes;
+          h->trace_dev = static_cast<u64*>(dp);
+        } else {
+          ::munmap(hp, bytes);
+        }
+      }
+    }
+    if (fd >= 0) ::close(fd);
+  }
+  if (h->trace_dev != nullptr) {
+    a.trace = h->trace_dev;
+    a.trace_cap = kTraceEpochs;
+  }
+}
+
+// --log-model-internal-state (modle_hip_enable_state_log): one block of records per task, every word 0xFF = no record
+int attach_state_log(modle_hip_handle* h, size_t n_tasks, SimArgs& a, char* err, size_t errlen) {
+  const size_t words = n_tasks * static_cast<size_t>(h->state_log_cap) * STATE_LOG_WORDS;
+  HIP_TRY(h->d_state_log.ensure(words));
+  HIP_TRY(hipMemsetAsync(h->d_state_log.p, 0xFF, words * 8, h->stream));
+  a.state_log = h->d_state_log.p;
+  a.state_log_cap = h->state_log_cap;
+  return MODLE_HIP_OK;
+}
+
+// Step 5: the kernel's arguments (every field set here: SimArgs has no initialisers).
+int build_args(modle_hip_handle* h, const PendingTasks& pending, const modle_host::LaunchPlan& plan,
+               const modle_host::WorkspaceLayout& layout, const LaunchEnv& env, SimArgs& a, char* err, size_t errlen) {
   a.params = h->params;
 #ifdef MODLE_EXP_SWITCH
-  a.params.exp_flags = std::getenv("MODLE_HIP_EXP") != nullptr ? static_cast<u32>(std::atoi(std::getenv("MODLE_HIP_EXP"))) : 0u;
+  a.params.exp_flags = env.exp_flags;
   a.params.exp_pad_ = 0;
 #endif
   a.tables.jump = h->d_jump.p;
@@ -636,131 +749,108 @@ int modle_hip_launch(modle_hip_handle* h, void* stream, char* err, size_t errlen
   a.trace = nullptr;
   a.trace_cap = 0;
   a.pad2_ = 0;
-  if (const char* shm = std::getenv("MODLE_HIP_TRACE_SHM"); shm != nullptr) {
-    // diagnostic: the trace of task 0 goes to a file-backed, host-coherent mapping so that it
-    // survives a GPU fault that aborts the process (mapped and registered once per handle)
-    constexpr u32 kTraceEpochs = 4096;
-    const size_t bytes = static_cast<size_t>(kTraceEpochs) * TRACE_STAGES * TRACE_WORDS_PER_STAGE * 8;
-    if (h->trace_host == nullptr) {
-      const int fd = ::open(shm, O_RDWR | O_CREAT | O_TRUNC, 0644);
-      if (fd >= 0 && ::ftruncate(fd, static_cast<off_t>(bytes)) == 0) {
-        void* hp = ::mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-        void* dp = nullptr;
-        if (hp != MAP_FAILED) {
-          if (hipHostRegister(hp, bytes, hipHostRegisterMapped) == hipSuccess &&
-              hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
-            h->trace_host = hp;
-            h->trace_bytes = bytes;
-            h->trace_dev = static_cast<u64*>(dp);
-          } else {
-            ::munmap(hp, bytes);
-          }
-        }
-      }
-      if (fd >= 0) ::close(fd);
-    }
-    if (h->trace_dev != nullptr) {
-      a.trace = h->trace_dev;
-      a.trace_cap = kTraceEpochs;
-    }
-  }
+  if (env.trace_shm != nullptr) map_trace(h, env.trace_shm, a);
   a.state_log = nullptr;
   a.state_log_cap = 0;
   a.pad3_ = 0;
   if (h->state_log_cap != 0) {
-    const size_t words = sorted.size() * static_cast<size_t>(h->state_log_cap) * STATE_LOG_WORDS;
-    HIP_TRY(h->d_state_log.ensure(words));
-    HIP_TRY(hipMemsetAsync(h->d_state_log.p, 0xFF, words * 8, h->stream));
-    a.state_log = h->d_state_log.p;
-    a.state_log_cap = h->state_log_cap;
+    if (const int rc = attach_state_log(h, pending.tasks.size(), a, err, errlen); rc != MODLE_HIP_OK) return rc;
   }
   a.phase_ticks = nullptr;
 #ifdef MODLE_PHASE_TIMERS
-  HIP_TRY(h->d_phase_ticks.ensure(20 + 3 * sorted.size()));
-  HIP_TRY(hipMemsetAsync(h->d_phase_ticks.p, 0, (20 + 3 * sorted.size()) * 8, h->stream));
+  HIP_TRY(h->d_phase_ticks.ensure(20 + 3 * pending.tasks.size()));
+  HIP_TRY(hipMemsetAsync(h->d_phase_ticks.p, 0, (20 + 3 * pending.tasks.size()) * 8, h->stream));
   HIP_TRY(hipMemsetAsync(h->d_phase_ticks.p + 18, 0xFF, 8, h->stream));
   a.phase_ticks = h->d_phase_ticks.p;
 #endif
   a.workspace = h->d_workspace.p;
   a.workspace_stride = layout.total_bytes;
-  a.n_tasks = static_cast<u32>(sorted.size());
-  a.max_lefs = max_lefs;
-  a.max_barriers = max_barriers;
-  // helper-wave mode for launches that leave at least half of the wave slots empty (sim_pair.h);
-  // MODLE_HIP_PAIRED=0 / 1 turns it off / on whatever the number of tasks (tests, A/B runs)
-  a.pair_mains = 0;
-  {
-    constexpr size_t kMaxMains = 4;  // (of the 8 waves of the kernels that know fixed roles)
-    bool paired = waves == 8 && sorted.size() <= static_cast<size_t>(grid) * kMaxMains;
-    if (const char* pm = std::getenv("MODLE_HIP_PAIRED"); pm != nullptr && pm[0] != '\0') paired = pm[0] != '0';
-#ifdef MODLE_STAGE_TRACE
-    paired = false;  // (the stage trace records the generator position between the phases)
-#endif
-    if (paired && waves == 8)
-      a.pair_mains = static_cast<u32>(std::min(kMaxMains, (sorted.size() + static_cast<size_t>(grid) - 1) / grid));
+  a.n_tasks = static_cast<u32>(pending.tasks.size());
+  a.max_lefs = pending.max_lefs;
+  a.max_barriers = pending.max_barriers;
+  a.pair_mains = plan.pair_mains;      // (the layout: modle_host::plan_launch)
+  a.tail_helpers = plan.tail_helpers;
+  a.test_fault = env.test_fault;
+  a.active_waves = plan.active_waves;
+  return MODLE_HIP_OK;
+}
+
+// Step 6.  The abort word is cleared, the kernel enqueued and the launch marked as in flight under the
+// lock modle_hip_cancel takes: a cancel from another thread either finds nothing in flight
+// (it came before this launch) or raises the word after the reset -- never in between, where
+// the reset would swallow it.
+int enqueue_and_commit(modle_hip_handle* h, PendingTasks& pending, const modle_host::LaunchPlan& plan, const SimArgs& a,
+                       char* err, size_t errlen) {
+  const int grid = static_cast<int>(plan.grid);
+  std::lock_guard<std::mutex> lock(h->abort_mu);
+  __atomic_store_n(h->h_abort, 0u, __ATOMIC_RELEASE);
+  h->cancelled = false;
+  const bool ev0 = hipEventRecord(h->ev_start, h->stream) == hipSuccess;
+  if (plan.waves == 12) {
+    if (plan.wide) simulate_wide12(grid, h->stream, a); else simulate_narrow12(grid, h->stream, a);
+  } else {
+    if (plan.wide) simulate_wide(grid, h->stream, a); else simulate_narrow(grid, h->stream, a);
   }
-  a.tail_helpers = a.pair_mains == 0 ? 1u : 0u;
-  if (const char* th = std::getenv("MODLE_HIP_TAIL_HELPERS"); th != nullptr && th[0] == '0') a.tail_helpers = 0;
-#ifdef MODLE_STAGE_TRACE
-  a.tail_helpers = 0;
-#endif
-  a.test_fault = 0;
-  if (const char* tf = std::getenv("MODLE_HIP_TEST_FAULT"); tf != nullptr && std::strcmp(tf, "stuck_helper") == 0)
-    a.test_fault = TEST_FAULT_STUCK_HELPER;  // (tests/test_gpu_wait_deadline.py)
-  a.active_waves = static_cast<u32>(waves);
-  if (const char* aw = std::getenv("MODLE_HIP_ACTIVE_WAVES"); aw != nullptr) {
-    // diagnostic: how the kernel time scales with the waves in flight per CU
-    const int v = std::atoi(aw);
-    if (v >= 1 && v <= waves) a.active_waves = static_cast<u32>(v);
+  HIP_TRY(hipGetLastError());
+  // The kernel is enqueued: commit the bookkeeping NOW.  Nothing after this point may make the
+  // call fail -- a caller that sees an error retries, and the same tasks would then be simulated
+  // twice into the same matrices.  A failed event record only costs the timing of this launch.
+  for (auto& recp : h->intervals) {
+    IntervalRec& rec = *recp;
+    rec.results.resize(rec.results.size() + rec.pending.size());
+    rec.pending.clear();
   }
-  {
-    // The abort word is cleared, the kernel enqueued and the launch marked as in flight under the
-    // lock modle_hip_cancel takes: a cancel from another thread either finds nothing in flight
-    // (it came before this launch) or raises the word after the reset -- never in between, where
-    // the reset would swallow it.
-    std::lock_guard<std::mutex> lock(h->abort_mu);
-    __atomic_store_n(h->h_abort, 0u, __ATOMIC_RELEASE);
-    h->cancelled = false;
-    const bool ev0 = hipEventRecord(h->ev_start, h->stream) == hipSuccess;
-    const bool wide = modle_hip_size_class(&h->cfg, max_lefs) != 0;
-    if (waves == 12) {
-      if (wide) simulate_wide12(grid, h->stream, a); else simulate_narrow12(grid, h->stream, a);
-    } else {
-      if (wide) simulate_wide(grid, h->stream, a); else simulate_narrow(grid, h->stream, a);
-    }
-    HIP_TRY(hipGetLastError());
-    // The kernel is enqueued: commit the bookkeeping NOW.  Nothing after this point may make the
-    // call fail -- a caller that sees an error retries, and the same tasks would then be simulated
-    // twice into the same matrices.  A failed event record only costs the timing of this launch.
-    for (auto& recp : h->intervals) {
-      IntervalRec& rec = *recp;
-      rec.results.resize(rec.results.size() + rec.pending.size());
-      rec.pending.clear();
-    }
-    h->launch_map.swap(sorted_map);
-    h->n_launched = sorted.size();
-    h->in_flight = true;
-    h->launched_at = std::chrono::steady_clock::now();
-    h->last_launch.n_tasks = sorted.size();
-    h->last_launch.num_cus = static_cast<uint64_t>(h->num_cus);
-    h->last_launch.workgroups = static_cast<uint64_t>(grid);
-    h->last_launch.waves_per_workgroup = static_cast<uint64_t>(waves);
-    h->last_launch.main_waves_per_workgroup = a.pair_mains != 0 ? a.pair_mains : a.active_waves;
-    h->last_launch.helper_waves = a.pair_mains != 0 ? 1 : 0;
-#ifdef MODLE_RNG_PHILOX
-    h->last_launch.prng_producer_waves = 0;
-#else
-    h->last_launch.prng_producer_waves = (a.pair_mains != 0 && a.pair_mains <= 2) ? 1 : 0;
-#endif
-    h->last_launch.tail_helpers = a.tail_helpers;
-    h->last_launch.size_class = wide ? 1 : 0;
-    h->last_launch.workspace_tries = h->ws_tries;
-    h->last_launch.workspace_probe_us = static_cast<uint64_t>(h->ws_probe_ms * 1000.0f + 0.5f);
-    h->last_launch.workspace_probe_worst_us = static_cast<uint64_t>(h->ws_probe_worst_ms * 1000.0f + 0.5f);
-    const bool ev1 = hipEventRecord(h->ev_stop, h->stream) == hipSuccess;
-    h->timing_valid = ev0 && ev1;
-    if (!h->timing_valid) (void)hipGetLastError();  // (clears the sticky error of the failed record)
+  h->launch_map.swap(pending.map);
+  h->n_launched = pending.tasks.size();
+  h->in_flight = true;
+  h->launched_at = std::chrono::steady_clock::now();
+  h->last_launch = launch_info_of(plan, pending.tasks.size(), static_cast<uint64_t>(h->num_cus));
+  h->last_launch.workspace_tries = h->ws_tries;
+  h->last_launch.workspace_probe_us = static_cast<uint64_t>(h->ws_probe_ms * 1000.0f + 0.5f);
+  h->last_launch.workspace_probe_worst_us = static_cast<uint64_t>(h->ws_probe_worst_ms * 1000.0f + 0.5f);
+  const bool ev1 = hipEventRecord(h->ev_stop, h->stream) == hipSuccess;
+  h->timing_valid = ev0 && ev1;
+  if (!h->timing_valid) (void)hipGetLastError();  // (clears the sticky error of the failed record)
+  return MODLE_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int modle_hip_launch(modle_hip_handle* h, void* stream, char* err, size_t errlen) {
+  if (h == nullptr) return MODLE_HIP_ERR_ARG;
+  if (h->in_flight) {
+    set_err(err, errlen, "a launch is already in flight");
+    return MODLE_HIP_ERR_STATE;
   }
+  const LaunchEnv env = read_launch_env();
+  HIP_TRY(hipSetDevice(h->device));
+  h->stream = static_cast<hipStream_t>(stream);
+  // Nothing of the handle's bookkeeping changes until the kernel has been enqueued (enqueue_and_commit): a launch
+  // that fails on the way leaves every task pending and every result slot as it was.
+  PendingTasks pending = gather_pending(h);
+  if (pending.tasks.empty()) {
+    h->n_launched = 0;
+    h->launch_map.clear();
+    return MODLE_HIP_OK;
+  }
+  const std::vector<Interval> ivs = device_intervals(h);
+  const modle_host::LaunchPlan plan = modle_host::plan_launch(pending.tasks.size(), static_cast<uint64_t>(h->num_cus),
+                                                              pending.max_lefs, h->cfg, env.layout, launch_build());
+  const auto layout = modle_host::workspace_layout(pending.max_lefs, pending.max_barriers, h->params.hist_len);
+  if (const int rc = stage_buffers(h, pending, ivs, plan, layout, env, err, errlen); rc != MODLE_HIP_OK) return rc;
+  SimArgs a;
+  if (const int rc = build_args(h, pending, plan, layout, env, a, err, errlen); rc != MODLE_HIP_OK) return rc;
+  return enqueue_and_commit(h, pending, plan, a, err, errlen);
+}
+
+// The rule a launch would follow, without a device: the same read of the environment, the same build switches.
+int modle_hip_plan_launch(const modle_hip_config* c, uint64_t n_tasks, uint64_t num_cus, uint64_t max_lefs,
+                          modle_hip_launch_info* out) {
+  if (c == nullptr || out == nullptr) return MODLE_HIP_ERR_ARG;
+  *out = launch_info_of(modle_host::plan_launch(n_tasks, num_cus, max_lefs, *c, read_launch_env().layout, launch_build()),
+                        n_tasks, num_cus);
   return MODLE_HIP_OK;
 }
 
@@ -797,59 +887,14 @@ int modle_hip_last_launch_info(modle_hip_handle* h, modle_hip_launch_info* info)
   return MODLE_HIP_OK;
 }
 
-int modle_hip_wait(modle_hip_handle* h, char* err, size_t errlen) {
-  if (h == nullptr) return MODLE_HIP_ERR_ARG;
-  if (!h->in_flight) return MODLE_HIP_OK;
-  HIP_TRY(hipSetDevice(h->device));
-  // Bounded wait.  The stream is polled (no HIP call waits with a deadline); when the launch has
-  // been running for longer than the deadline the abort word is raised -- every wave reads it at the
-  // top of every sixteenth epoch and in every spin loop of the hand-over protocols (sim_rng.h:
-  // spin_nap_aborted) -- and the kernel gets `drain_timeout_s` to drain.  A launch that drains is
-  // reported as MODLE_HIP_ERR_TIMEOUT with the handle usable again (modle_hip_reset); one that does
-  // not is a hung device: MODLE_HIP_ERR_DEVICE, the launch stays in flight and the process should
-  // exit (never re-exec a process that has touched the GPU).
-  bool timed_out = false;
-  {
-    using clock = std::chrono::steady_clock;
-    const bool has_deadline = h->wait_timeout_s > 0.0;
-    const auto deadline = h->launched_at + std::chrono::duration_cast<clock::duration>(
-                                               std::chrono::duration<double>(has_deadline ? h->wait_timeout_s : 0.0));
-    clock::time_point drain_deadline{};
-    unsigned polls = 0;
-    for (;;) {
-      const hipError_t q = hipStreamQuery(h->stream);
-      if (q == hipSuccess) break;
-      if (q != hipErrorNotReady) {
-        set_err(err, errlen, std::string("hipStreamQuery: ") + hipGetErrorString(q));
-        return MODLE_HIP_ERR_DEVICE;
-      }
-      const auto now = clock::now();
-      if (!timed_out && has_deadline && now > deadline) {
-        std::lock_guard<std::mutex> lock(h->abort_mu);
-        __atomic_store_n(h->h_abort, 1u, __ATOMIC_RELEASE);
-        timed_out = true;
-        drain_deadline = now + std::chrono::duration_cast<clock::duration>(
-                                   std::chrono::duration<double>(h->drain_timeout_s));
-      } else if (timed_out && now > drain_deadline) {
-        set_err(err, errlen, "the launch exceeded the wait deadline of " + std::to_string(h->wait_timeout_s) +
-                                 " s and did not drain within " + std::to_string(h->drain_timeout_s) +
-                                 " s of the abort word being raised: the device is hung");
-        return MODLE_HIP_ERR_DEVICE;
-      }
-      // short launches (tests) end within the first polls; long ones are polled every 200 us
-      if (++polls < 4096) {
-        std::this_thread::yield();
-      } else {
-        std::this_thread::sleep_for(std::chrono::microseconds(200));
-      }
-    }
-  }
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  h->in_flight = false;
-  if (!h->timing_valid || hipEventElapsedTime(&h->last_ms, h->ev_start, h->ev_stop) != hipSuccess) {
-    (void)hipGetLastError();
-    h->last_ms = std::nanf("");  // (an event could not be recorded: the launch itself is fine)
-  }
+}  // extern "C"
+
+namespace {
+
+// What modle_hip_wait hands back once the stream is idle: the per-task results into their intervals' slots, and the
+// launch's return code from the status words -- a device status outranks a cancellation, a deadline that aborted
+// tasks outranks both.
+int collect_results(modle_hip_handle* h, bool timed_out, char* err, size_t errlen) {
 #ifdef MODLE_PHASE_TIMERS
   {
     static const char* names[16] = {"burnin_stats", "bind", "rank_rev", "rank_fwd", "sample", "gen_moves",
@@ -916,6 +961,53 @@ int modle_hip_wait(modle_hip_handle* h, char* err, size_t errlen) {
     return MODLE_HIP_ERR_TIMEOUT;
   }
   return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int modle_hip_wait(modle_hip_handle* h, char* err, size_t errlen) {
+  if (h == nullptr) return MODLE_HIP_ERR_ARG;
+  if (!h->in_flight) return MODLE_HIP_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  // Bounded wait.  The stream is polled (no HIP call waits with a deadline); when the launch has
+  // been running for longer than the deadline the abort word is raised -- every wave reads it at the
+  // top of every sixteenth epoch and in every spin loop of the hand-over protocols (sim_rng.h:
+  // spin_nap_aborted) -- and the kernel gets `drain_timeout_s` to drain.  A launch that drains is
+  // reported as MODLE_HIP_ERR_TIMEOUT with the handle usable again (modle_hip_reset); one that does
+  // not is a hung device: MODLE_HIP_ERR_DEVICE, the launch stays in flight and the process should
+  // exit (never re-exec a process that has touched the GPU).
+  bool timed_out = false;
+  unsigned polls = 0;  // (short launches -- tests -- end within the first polls: the stream is polled without a nap)
+  const auto deadline = h->launched_at + as_duration(h->wait_timeout_s);
+  hipError_t q = poll_stream(h->stream, h->wait_timeout_s > 0.0 ? &deadline : nullptr, polls);
+  if (q == hipErrorNotReady) {
+    {
+      std::lock_guard<std::mutex> lock(h->abort_mu);
+      __atomic_store_n(h->h_abort, 1u, __ATOMIC_RELEASE);
+    }
+    timed_out = true;
+    const auto drain_deadline = std::chrono::steady_clock::now() + as_duration(h->drain_timeout_s);
+    q = poll_stream(h->stream, &drain_deadline, polls);
+    if (q == hipErrorNotReady) {
+      set_err(err, errlen, "the launch exceeded the wait deadline of " + std::to_string(h->wait_timeout_s) +
+                               " s and did not drain within " + std::to_string(h->drain_timeout_s) +
+                               " s of the abort word being raised: the device is hung");
+      return MODLE_HIP_ERR_DEVICE;
+    }
+  }
+  if (q != hipSuccess) {
+    set_err(err, errlen, std::string("hipStreamQuery: ") + hipGetErrorString(q));
+    return MODLE_HIP_ERR_DEVICE;
+  }
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  h->in_flight = false;
+  if (!h->timing_valid || hipEventElapsedTime(&h->last_ms, h->ev_start, h->ev_stop) != hipSuccess) {
+    (void)hipGetLastError();
+    h->last_ms = std::nanf("");  // (an event could not be recorded: the launch itself is fine)
+  }
+  return collect_results(h, timed_out, err, errlen);
 }
 
 int modle_hip_enable_state_log(modle_hip_handle* h, uint32_t max_epochs_per_task, char* err,
