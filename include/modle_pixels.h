@@ -1,8 +1,8 @@
 /* modle_pixels.h -- C ABI of the sparse-pixel extraction (modle_amd/libmodle_pixels.so), of the
  * coarsening of a band, of its dense regions, of its marginals, of its insulation sums, of its
  * dot candidates, of its pileups (fixed windows and rescaled ones) and of its random sampling, of the
- * way back from sorted pixels to a band, and of the comparison of two bands stripe by stripe and diagonal
- * by diagonal (further down).
+ * way back from sorted pixels to a band, of the comparison of two bands stripe by stripe and diagonal
+ * by diagonal, and of the stripe profiles of one band (further down).
  *
  * The simulation leaves every interval as a dense band matrix in device memory
  * (modle_hip_interval_outputs).  A cooler file is made of the non-zero pixels only, sorted by
@@ -785,6 +785,56 @@ int modle_pixels_scc(modle_pixels_handle* h, const uint32_t* d_ref, const uint32
 int modle_pixels_scc_to_host(modle_pixels_handle* h, const uint32_t* d_ref, const uint32_t* d_tgt, uint64_t nrows,
                              uint64_t ncols, uint64_t smooth, uint64_t min_diag, uint64_t max_diag,
                              const uint64_t** rows, void* stream, char* err, size_t errlen);
+
+/* ---- stripe profiles: the cross-sections of every bin's stripes ----------------------------------------
+ *
+ * Where one band has a stripe, how long it is and how sharply it stands out of its neighbourhood (the comparison
+ * above takes two bands and says none of that).  M(x, y) is the symmetric matrix of the band, 0 outside the
+ * chromosome.  For the largest offset `max_offset` = m <= MODLE_PIXELS_MAX_PROFILE_OFFSET, the lengths L_1 < ... <
+ * L_K in bins (1 <= K <= MODLE_PIXELS_MAX_PROFILE_LENGTHS, a HOST array) and `min_diag` = d0, for every bin c <
+ * ncols, offset o in [-m, m] and k:
+ *     V[k][o][c] = sum over d0 <= d < L_k of M(c - d, c + o)   the stripe upstream of c, seen o columns to the side
+ *     H[k][o][c] = sum over d0 <= d < L_k of M(c + o, c + d)   the stripe downstream of c, seen o rows to the side
+ * The output is uint64[2][K][2 m + 1][ncols]: direction 0 is V, 1 is H, offset index o + m; the words whose column
+ * or row c + o lies outside [0, ncols) hold 0.  A sum has fewer than nrows terms below 2^32: 64 bits cannot
+ * overflow and there is no range refusal.  The cross-section over o is what makes a stripe a stripe, a peak at o =
+ * 0 over flat shoulders; the decision is one host statement (modle_amd/pixels.py: stripe_calls).
+ *
+ * The accepted call:
+ *     nrows >= 1,  nrows <= ncols,  m <= 8,  1 <= K <= 4,  d0 >= m,  d0 < L_1 < ... < L_K,  L_K + m <= nrows
+ * d0 >= m keeps every cell on its own side of the main diagonal (V reads band[(c + o) * nrows + (d + o)], H reads
+ * band[(c + d) * nrows + (d - o)]: nothing goes through the symmetry), and L_K + m <= nrows keeps every cell inside
+ * the band, so the result is that of the full matrix.  EVERY output word is written exactly once, with a plain
+ * store: the caller does not pre-zero.  Every band word is read at most once per direction; the words that are no
+ * pixels are never read, and every address is a function of the arguments alone.  Nothing here uses floating point.
+ *
+ * MODLE_PIXELS_ERR_ARG, with nothing written: everything outside the accepted call, a null pointer, out_words !=
+ * 2 * K * (2 m + 1) * ncols, a d_out that is not 8-byte aligned or overlaps the band. */
+#define MODLE_PIXELS_MAX_PROFILE_OFFSET 8
+#define MODLE_PIXELS_MAX_PROFILE_LENGTHS 4
+
+/* Enqueues the sums into the device array d_out (uint64[2][K][2 m + 1][ncols]) on `stream`; the call does not
+ * wait (`lengths` is read before it returns). */
+int modle_pixels_stripe_profiles(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols,
+                                 uint64_t max_offset, const uint64_t* lengths, uint64_t n_lengths,
+                                 uint64_t min_diag, uint64_t* d_out, uint64_t out_words, void* stream, char* err,
+                                 size_t errlen);
+
+/* The same into a pinned host buffer of the context (grown on demand, freed by modle_pixels_destroy): *profiles
+ * (uint64[2][K][2 m + 1][ncols]) stays valid until the next call on the context.  Waits for `stream`. */
+int modle_pixels_stripe_profiles_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                                         uint64_t ncols, uint64_t max_offset, const uint64_t* lengths,
+                                         uint64_t n_lengths, uint64_t min_diag, const uint64_t** profiles,
+                                         void* stream, char* err, size_t errlen);
+
+/* The band coarsened by `factor` into scratch of the context (as modle_pixels_coarse_marginals_to_host), then
+ * modle_pixels_stripe_profiles_to_host on it.  *profiles is uint64[2][K][2 m + 1][ncols'];  the lengths, the offset
+ * and min_diag count coarse bins, and the accepted call holds against nrows'. */
+int modle_pixels_coarse_stripe_profiles_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                                                uint64_t ncols, uint64_t factor, uint64_t first_bin,
+                                                uint64_t max_offset, const uint64_t* lengths, uint64_t n_lengths,
+                                                uint64_t min_diag, const uint64_t** profiles, void* stream,
+                                                char* err, size_t errlen);
 
 /* The launch caps this build of the library was compiled with, for the tests that lower them: caps[0] the
  * workgroups of a stripes launch at most (2^20), caps[1] the grid's y of the band fill at most (65535),

@@ -7,6 +7,7 @@ the reference: `Config` (simulation_config.hpp), `Task` / `State` results (simul
 """
 import ctypes as C
 import math
+from collections import namedtuple
 
 import numpy as np
 
@@ -365,6 +366,80 @@ def domain_strength(pile, expected, size, flank_percent):
     if ew == 0.0 or eb == 0.0 or ob == 0:
         return math.nan
     return (float(ow) / ew) / (float(ob) / eb)
+
+
+def stripe_profile_expected(diag_sum, ncols, lengths, min_diag, half_width=0):
+    """What the distance-decay curve expects of the centre of a stripe profile, one float per length: the cell at
+    distance d of the stripe, seen o bins to the side, lies on diagonal d + o (upstream) or d - o (downstream), so
+    for either direction it is the math.fsum over min_diag <= d < L_k and |o| <= half_width of E[d + o], E[d] =
+    float(diag_sum[d]) / float(ncols - d).  `diag_sum`: the sums per diagonal of the band (BandAnalyses.expected).
+    ValueError when a diagonal is not held."""
+    diag = [int(x) for x in np.asarray(diag_sum).reshape(-1)]
+    ncols, d0, h = int(ncols), int(min_diag), int(half_width)
+    ls = [int(x) for x in lengths]
+    if h < 0 or d0 < h or not ls or max(ls) + h > len(diag) or ncols < len(diag):
+        raise ValueError(f"stripe_profile_expected: min_diag {d0}, lengths {ls} and half width {h} on {len(diag)} "
+                         f"diagonals of {ncols} columns")
+    e = [float(s) / float(ncols - d) for d, s in enumerate(diag)]
+    return [math.fsum(e[d + o] for d in range(d0, length) for o in range(-h, h + 1)) for length in ls]
+
+
+def directionality_index(profiles, n_valid, k):
+    """The directionality index of Dixon et al. (Nature 2012) of every bin from the stripe profiles of length
+    class `k` (uint64 [2, K, 2 m + 1, ncols]), numpy float64 [ncols]: from the o = 0 rows, A = V the contacts with
+    the L_k - min_diag bins upstream, B = H those downstream, E = (A + B) / 2 and
+        DI = sign(B - A) * ((A - E)^2 + (B - E)^2) / E,
+    NaN where E == 0.  A - E and B - E are formed exactly (as halves of an integer), the rest in float64.  `n_valid`
+    (pixels.stripe_profile_n_valid of the same call) tells which bins have both windows whole: the index is that
+    of sums, as Dixon has it, and near the ends of the chromosome one window is cut."""
+    prof, nv = np.asarray(profiles), np.asarray(n_valid)
+    if prof.ndim != 4 or prof.dtype != np.uint64 or prof.shape[0] != 2 or prof.shape[2] % 2 != 1 or nv.shape != prof.shape \
+            or not 0 <= int(k) < prof.shape[1]:
+        raise ValueError(f"directionality_index: profiles of shape {prof.shape}, valid cells of shape {nv.shape}, "
+                         f"length class {k}")
+    m = prof.shape[2] // 2
+    out = np.empty(prof.shape[3], dtype=np.float64)
+    for c in range(prof.shape[3]):
+        a, b = int(prof[0, k, m, c]), int(prof[1, k, m, c])
+        if a + b == 0:
+            out[c] = math.nan
+            continue
+        # A - E = (A - B) / 2 = -(B - E): the two squares are equal
+        e = (a + b) / 2
+        half = (a - b) / 2
+        out[c] = math.copysign((half * half + half * half) / e, b - a) if a != b else 0.0
+    return out
+
+
+# a call of stripe_rows: bins and sums as pixels.stripe_calls has them, the quotients as floats
+StripeRow = namedtuple("StripeRow", "direction bin k length centre n_centre left_mean right_mean enrichment "
+                                    "obs_over_exp")
+
+
+def stripe_rows(profiles, diag_sum, max_offset, lengths, min_diag, half_width=0, fold=None, min_count=None, radius=None):
+    """The stripe calls of a band as rows: pixels.stripe_calls of `profiles` and the valid cells of their call,
+    each with the means of its two shoulders, its enrichment (C / nC) / max(Bl / nBl, Br / nBr) (inf over empty
+    shoulders) and its centre over what the distance decay expects (stripe_profile_expected; NaN where that is
+    0).  Every quotient is one division of Python integers or Fractions, rounded once.  None for `fold`,
+    `min_count`, `radius`: the defaults of pixels.stripe_calls."""
+    from fractions import Fraction
+
+    from . import pixels
+
+    prof = np.asarray(profiles)
+    ncols = prof.shape[-1]
+    n_valid = pixels.stripe_profile_n_valid(ncols, max_offset, lengths, min_diag)
+    options = {name: v for name, v in (("fold", fold), ("min_count", min_count), ("radius", radius)) if v is not None}
+    calls = pixels.stripe_calls(prof, n_valid, max_offset, lengths, min_diag, half_width, **options)
+    expected = stripe_profile_expected(diag_sum, ncols, lengths, min_diag, half_width)
+    rows = []
+    for s in calls:
+        centre, left, right = Fraction(s.centre, s.n_centre), Fraction(s.left, s.n_left), Fraction(s.right, s.n_right)
+        side = max(left, right)
+        rows.append(StripeRow(s.direction, s.bin, s.k, int(lengths[s.k]), s.centre, s.n_centre, float(left), float(right),
+                              float(centre / side) if side else math.inf,
+                              s.centre / expected[s.k] if expected[s.k] else math.nan))
+    return rows
 
 
 class BandAnalyses:
@@ -962,6 +1037,53 @@ class BandAnalyses:
         if any(k is not None for k in keep):
             torch.cuda.synchronize(out.device)
         return out
+
+    def stripe_profiles(self, interval_id, max_offset, lengths, min_diag=None, factor=1, first_bin=0, stream=None):
+        """The cross-sections of every bin's stripes: (profiles, n_valid), numpy uint64 [2, K, 2 m + 1, ncols].
+        profiles[0][k][o + m][c] is the sum of the stripe that runs upstream of bin c, the cells M(c - d, c + o) at
+        the distances min_diag <= d < lengths[k], seen o bins to the side; profiles[1] that of the stripe
+        downstream, M(c + o, c + d) (include/modle_pixels.h), formed on the device from the band where it lies
+        (pixels.stripe_profiles); n_valid the number of cells of each inside the chromosome.  `min_diag` None:
+        the smallest the call accepts, max(max_offset, 1).  pixels.PROFILE_RULE is the accepted call.  Call it after
+        wait().  With `factor` > 1 the band is first coarsened on the device (`first_bin` as for pixels()) and
+        the lengths, the offset and `min_diag` count coarse bins."""
+        from . import pixels
+
+        if min_diag is None:
+            min_diag = max(int(max_offset), 1)
+        d_band, _, nrows, ncols = self.outputs(interval_id)
+        prof = pixels.extractor(self.device).stripe_profiles(d_band, nrows, ncols, max_offset, lengths, min_diag, stream,
+                                                             factor, first_bin)
+        return prof, pixels.stripe_profile_n_valid(prof.shape[3], max_offset, lengths, min_diag)
+
+    def stripe_profiles_tensor(self, interval_id, max_offset, lengths, min_diag=None, stream=None):
+        """The sums of stripe_profiles as one torch int64 tensor [2, K, 2 m + 1, ncols] on the device, filled there
+        by the kernels: nothing crosses to the host.  The words hold the uint64 sums bit for bit (they are below
+        2^56).  The work is enqueued on `stream` (None: the default stream, on which torch orders its own work)
+        and not waited for."""
+        import torch
+
+        from . import pixels
+
+        if min_diag is None:
+            min_diag = max(int(max_offset), 1)
+        d_band, _, nrows, ncols = self.outputs(interval_id)
+        out = torch.empty((2, len(lengths), 2 * int(max_offset) + 1, ncols), dtype=torch.int64,
+                          device=torch.device("cuda", self.device))
+        pixels.stripe_profiles_into(d_band, nrows, ncols, max_offset, lengths, min_diag, out.data_ptr(), out.numel(),
+                                    stream, device=self.device)
+        return out
+
+    def call_stripes(self, interval_id, max_offset, lengths, min_diag=None, half_width=0, fold=None, min_count=None,
+                     radius=None, factor=1, first_bin=0):
+        """The stripes of the interval, a list of StripeRow sorted by (direction, bin): stripe_rows of
+        stripe_profiles and of the sums per diagonal (marginals), both formed on the device; the decision is
+        pixels.stripe_calls.  Direction 0: the stripe runs upstream of its anchor bin, 1: downstream."""
+        if min_diag is None:
+            min_diag = max(int(max_offset), 1)
+        prof, _ = self.stripe_profiles(interval_id, max_offset, lengths, min_diag, factor, first_bin)
+        diag_sum, _ = self.marginals(interval_id, 0, factor, first_bin)
+        return stripe_rows(prof, diag_sum, max_offset, lengths, min_diag, half_width, fold, min_count, radius)
 
 
 # ---------------------------------------------------------------------------------------------

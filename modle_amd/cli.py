@@ -40,6 +40,16 @@ on the GPU into one N x N pile with the number of source pixels of every cell, a
 multiple of -r, coarsened on the GPU; default -r); the file also holds what the distance-decay curve expects of
 every cell and the strength of the average domain (api.domain_strength).  observed / area is the pooled mean of a
 cell, in which large domains weigh more: it is not the mean of per-domain interpolations of coolpup.py --rescale.
+With --call-stripes `<prefix>_stripe_calls.bedpe`, the architectural stripes of every interval: for every bin the
+stripe that runs upstream and the one that runs downstream of it are summed on the GPU at the --call-stripes-lengths
+LIST (1 to 4, default 200kb,400kb,800kb) together with their cross-section, the same sums up to --call-stripes-flank
+D (at most 8 bins; default 50kb) to either side, and a bin is called at the longest length at which its centre of
+--call-stripes-width D (an odd number of bins, default one) holds at least --call-stripes-min-count N contacts
+(default 1) and its mean is at least --call-stripes-fold F (default 1.5) times the mean of either shoulder; the
+calls of one direction are thinned to the best within --call-stripes-radius D (default: the flank).
+--call-stripes-ignore-diags N leaves out the first N diagonals (default and at least the bins of the flank, 2 at
+least) and --call-stripes-resolution R (a multiple of -r, coarsened on the GPU; default -r) sets the bin size.  The
+fold, the count and the radius are choices, not measured optima; the rule is pixels.stripe_calls', not Stripenn's.
 Everything heavy is native: parsing and
 task generation in libmodle_hip.so (host), the simulation on the MI355X (one process per GPU;
 under torch.distributed.run the cells are sharded over the ranks and the matrices are summed
@@ -225,6 +235,10 @@ def scc_path(prefix):
     return prefix + "_scc.tsv"
 
 
+def stripe_calls_path(prefix):
+    return prefix + "_stripe_calls.bedpe"
+
+
 def sampled_paths(prefix, mcool=False):
     """(the file of the kept contacts, the file of the others) of --subsample-frac / --subsample-to"""
     ext = ".mcool" if mcool else ".cool"
@@ -346,6 +360,18 @@ def add_analysis_arguments(io):
     io.add_argument("--domains-size", type=int, default=None, metavar="N", help=argparse.SUPPRESS)
     io.add_argument("--domains-flank-percent", type=int, default=None, metavar="P", help=argparse.SUPPRESS)
     io.add_argument("--domains-resolution", type=genomic_distance, default=None, metavar="R", help=argparse.SUPPRESS)
+    # Stripe calling (<prefix>_stripe_calls.bedpe; the module's text describes the options), kept out of the
+    # generated help likewise
+    io.add_argument("--call-stripes", action="store_true", default=None, help=argparse.SUPPRESS)
+    io.add_argument("--call-stripes-lengths", type=window_list, default=None, metavar="LIST", help=argparse.SUPPRESS)
+    io.add_argument("--call-stripes-flank", type=genomic_distance, default=None, metavar="D", help=argparse.SUPPRESS)
+    io.add_argument("--call-stripes-width", type=genomic_distance, default=None, metavar="D", help=argparse.SUPPRESS)
+    io.add_argument("--call-stripes-fold", type=float, default=None, metavar="F", help=argparse.SUPPRESS)
+    io.add_argument("--call-stripes-min-count", type=int, default=None, metavar="N", help=argparse.SUPPRESS)
+    io.add_argument("--call-stripes-ignore-diags", type=int, default=None, metavar="N", help=argparse.SUPPRESS)
+    io.add_argument("--call-stripes-radius", type=genomic_distance, default=None, metavar="D", help=argparse.SUPPRESS)
+    io.add_argument("--call-stripes-resolution", type=genomic_distance, default=None, metavar="R",
+                    help=argparse.SUPPRESS)
 
 
 def build_parser():
@@ -538,10 +564,32 @@ Domains = collections.namedtuple("Domains", "path resolution size flank_percent 
 # Outputs, this rank among the ranks and its device, the five records above (None: not asked for), the
 # diagonals --coverage leaves out, the Domains and the Scc.  (The first five fields are also made positionally:
 # the others default.)
-Preflight = collections.namedtuple(
+_PreflightFields = collections.namedtuple(
     "Preflight", "bin_sizes outputs rank world device insulation dots pileup subsample stripes coverage_min_diag "
                  "domains scc",
     defaults=(None, None, None, None, None, 0, None, None))
+# what --call-stripes asks for: the file (None with --skip-output), the bin size, the lengths, the flank (m bins),
+# the width of the centre (2 h + 1 bins) and the thinning radius in base pairs, the fold, the smallest centre sum
+# and the diagonals left out
+StripeCalls = collections.namedtuple("StripeCalls", "path resolution lengths flank width fold min_count min_diag radius")
+
+
+class Preflight(_PreflightFields):
+    """The 13 fields above, and the StripeCalls as the attribute `stripe_calls` (None: not asked for).  It is no
+    fourteenth field: the tuple is also made positionally and unpacked by its length, and a record that is new
+    must not move what those users see.  Keyword-only here, kept by _replace."""
+    stripe_calls = None  # (of an instance that _make made)
+
+    def __new__(cls, *args, stripe_calls=None, **kw):
+        self = super().__new__(cls, *args, **kw)
+        self.stripe_calls = stripe_calls
+        return self
+
+    def _replace(self, **kw):
+        stripe_calls = kw.pop("stripe_calls", self.stripe_calls)
+        out = super()._replace(**kw)
+        out.stripe_calls = stripe_calls
+        return out
 
 
 def subsample_options(a, cfg):
@@ -744,6 +792,61 @@ def scc_options(a, cfg, stripes):
     return Scc(_file(a, scc_path), smooth, far, min_diag, bool(a.scc_include_zeros))
 
 
+MAX_STRIPE_FLANK_BINS = pixels.MAX_PROFILE_OFFSET
+
+
+def stripe_calls_options(a, cfg):
+    """The stripe calling the arguments ask for, as a StripeCalls, or None.  SystemExit: a --call-stripes-* option
+    without --call-stripes, a resolution that is no multiple of -r, more than 4 lengths, a length, flank, width or
+    radius that is no multiple of the resolution of the calls, a width that is no odd number of bins, a flank
+    below the width or above 8 bins, ignored diagonals below the flank, a length not above the ignored
+    diagonals, lengths that do not increase, a fold that is not positive, a negative count.  The defaults are
+    product choices: lengths of 200, 400 and 800 kb, a flank of 50 kb (at most 8 bins, at least the width), a
+    centre of one bin, pixels.STRIPE_FOLD and STRIPE_MIN_COUNT, as many diagonals ignored as the flank has bins
+    (at least 2), and a thinning radius of the flank."""
+    given = (("--call-stripes-lengths", a.call_stripes_lengths), ("--call-stripes-flank", a.call_stripes_flank),
+             ("--call-stripes-width", a.call_stripes_width), ("--call-stripes-fold", a.call_stripes_fold),
+             ("--call-stripes-min-count", a.call_stripes_min_count),
+             ("--call-stripes-ignore-diags", a.call_stripes_ignore_diags),
+             ("--call-stripes-radius", a.call_stripes_radius), ("--call-stripes-resolution", a.call_stripes_resolution))
+    if not a.call_stripes:
+        _needs("--call-stripes", given)
+        return None
+    res = _analysis_resolution("--call-stripes-resolution", a.call_stripes_resolution, cfg)
+    lengths = [200_000, 400_000, 800_000] if a.call_stripes_lengths is None else [int(x) for x in a.call_stripes_lengths]
+    if not 1 <= len(lengths) <= pixels.MAX_PROFILE_LENGTHS:
+        raise SystemExit(f"--call-stripes-lengths: {len(lengths)} lengths: 1 to {pixels.MAX_PROFILE_LENGTHS}")
+    width = res if a.call_stripes_width is None else int(a.call_stripes_width)
+    if width < res or width % res != 0 or width // res % 2 != 1:
+        raise SystemExit(f"--call-stripes-width: {width} is not an odd number of bins of the resolution of the calls ({res})")
+    flank = max(width, min(MAX_STRIPE_FLANK_BINS, max(1, 50_000 // res)) * res) if a.call_stripes_flank is None \
+        else int(a.call_stripes_flank)
+    radius = flank if a.call_stripes_radius is None else int(a.call_stripes_radius)
+    for name, v in [("--call-stripes-lengths", x) for x in lengths] + [("--call-stripes-flank", flank),
+                                                                      ("--call-stripes-radius", radius)]:
+        if v < 0 or v % res != 0:
+            raise SystemExit(f"{name}: {v} is not a multiple of the resolution of the calls ({res})")
+    if flank < width:
+        raise SystemExit(f"--call-stripes-flank: {flank} is below the width of the centre ({width}): no shoulder is left")
+    if flank // res > MAX_STRIPE_FLANK_BINS:
+        raise SystemExit(f"--call-stripes-flank: {flank} is {flank // res} bins of {res}: at most {MAX_STRIPE_FLANK_BINS}")
+    min_diag = max(flank // res, 2) if a.call_stripes_ignore_diags is None else a.call_stripes_ignore_diags
+    if min_diag < flank // res:
+        raise SystemExit(f"--call-stripes-ignore-diags: {min_diag} is below the {flank // res} bins of the flank: a "
+                         "shoulder would cross the main diagonal")
+    for below, length in zip([min_diag * res] + lengths, lengths):
+        if length <= below:
+            raise SystemExit(f"--call-stripes-lengths: {length} is not above " +
+                             (f"the {min_diag} ignored diagonals ({below})" if length is lengths[0] else f"{below}"))
+    fold = pixels.STRIPE_FOLD if a.call_stripes_fold is None else a.call_stripes_fold
+    if not fold > 0.0 or fold == float("inf"):  # (NaN too)
+        raise SystemExit(f"--call-stripes-fold: {fold} is not a positive number")
+    min_count = pixels.STRIPE_MIN_COUNT if a.call_stripes_min_count is None else a.call_stripes_min_count
+    if min_count < 0:
+        raise SystemExit(f"--call-stripes-min-count: {min_count} is negative")
+    return StripeCalls(_file(a, stripe_calls_path), res, lengths, flank, width, fold, min_count, min_diag, radius)
+
+
 def insulation_options(a, cfg):
     """The insulation track the arguments ask for, as an Insulation, or None.
     SystemExit: --insulation-resolution or --insulation-ignore-diags without --insulation-windows, a
@@ -771,12 +874,13 @@ def preflight(a, cfg):
     """The whole plan of the run, a Preflight: what the arguments alone settle and refuse, without a genome or
     a GPU.  Nothing after it derives an analysis from the arguments again.  SystemExit:
     --coverage-ignore-diags without --coverage, or negative; what insulation_options, dots_options,
-    pileup_options, domains_options, subsample_options, stripes_options and scc_options refuse, in that order
+    pileup_options, domains_options, subsample_options, stripes_options, scc_options and stripe_calls_options
+    refuse, in that order
     (stripes_options
     opens the reference cooler, the one time it is opened before the launch); a bad --mcool-resolutions list; on
     rank 0, an output that exists without --force (cooler or .mcool, then bigwig, then .npz, then the expected,
     the coverage, the insulation, the dots, the pileup and the domains file, then the sampled files, then the
-    stripes, then the SCC).  With
+    stripes, then the SCC, then the stripe calls).  With
     --skip-output no file is planned and none is looked at."""
     if a.coverage_ignore_diags is not None:
         if not a.coverage:
@@ -790,6 +894,7 @@ def preflight(a, cfg):
     sub = subsample_options(a, cfg)
     cmp_ = stripes_options(a, cfg)
     scc = scc_options(a, cfg, cmp_)
+    calls = stripe_calls_options(a, cfg)
     # (a bad list ends the run here, before anything is imported or simulated)
     bin_sizes = None if a.mcool_resolutions is None else mcool_bin_sizes(a.mcool_resolutions, cfg.bin_size)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -797,7 +902,7 @@ def preflight(a, cfg):
     device = a.device if a.device is not None else int(os.environ.get("LOCAL_RANK", "0"))
     analyses = (ins, dots, pile, sub, cmp_, a.coverage_ignore_diags or 0, dom, scc)
     if a.skip_output:
-        return Preflight(bin_sizes, Outputs(None, None, None, None), rank, world, device, *analyses)
+        return Preflight(bin_sizes, Outputs(None, None, None, None), rank, world, device, *analyses, stripe_calls=calls)
     cool_path, bw_path = output_paths(a.output_prefix, mcool=bin_sizes is not None)
     # (cli.cpp:871-875; with several ranks every rank writes its own)
     log_path = a.output_prefix + ("_internal_state.log.gz" if world == 1 else f"_internal_state.rank{rank}.log.gz")
@@ -812,10 +917,11 @@ def preflight(a, cfg):
         planned += [sub.rest_path] if sub is not None and sub.split else []
         planned += [cmp_.path] if cmp_ is not None else []
         planned += [scc.path] if scc is not None else []
+        planned += [calls.path] if calls is not None else []
         for p in planned:
             if p and os.path.exists(p) and not a.force:
                 raise SystemExit(f"refusing to overwrite {p}: pass --force to overwrite")
-    return Preflight(bin_sizes, outputs, rank, world, device, *analyses)
+    return Preflight(bin_sizes, outputs, rank, world, device, *analyses, stripe_calls=calls)
 
 
 def plan_run(a, cfg, pre, log):
@@ -878,6 +984,11 @@ def check_plan(a, cfg, pre, plan, chroms):
                                 pre.scc.min_diag)
         if bad is not None:
             raise SystemExit(f"--scc: {bad}")
+    calls = pre.stripe_calls
+    if calls is not None and calls.path is not None:
+        bad = driver.stripe_calls_misfit(plan, int(cfg.bin_size), calls.resolution, calls.lengths, calls.flank)
+        if bad is not None:
+            raise SystemExit(f"--call-stripes-lengths: {bad}: widen the band with -w")
     return driver.dense_regions(plan, int(cfg.bin_size), chroms, a.dense_region) if a.dense_region else []
 
 

@@ -1399,6 +1399,114 @@ def _interval_stripes(sim, plan, ids, reader, metrics, exclude_zero, sums, k, fa
     return [tuple(pixels.stripe_scores(rows[d], m, exclude_zero) for d in (0, 1)) for m in metrics]
 
 
+def stripe_calls_bins(calls):
+    """(m, h, lengths, min_diag, radius) in bins of the cli.StripeCalls `calls`"""
+    res = int(calls.resolution)
+    return int(calls.flank) // res, (int(calls.width) // res - 1) // 2, [int(x) // res for x in calls.lengths], \
+        int(calls.min_diag), int(calls.radius) // res
+
+
+def stripe_calls_misfit(plan, base, resolution, lengths, flank):
+    """What an entry of the plan that has a matrix cannot hold of the stripe profiles, or None: the longest of
+    `lengths` and the `flank` (bp, multiples of `resolution`) need L_K + m <= nrows' diagonals of its band at
+    `resolution`"""
+    res = int(resolution)
+    need = max(int(x) for x in lengths) // res + int(flank) // res
+    for _, entry, _, _, (nr, _) in plan_bands(plan, base, res):
+        if entry["ncols"] != 0 and need > nr:
+            return (f"the length of {max(int(x) for x in lengths)} with the flank of {int(flank)} needs {need} diagonals "
+                    f"of {res}, the band of {interval_name(entry['interval'])} has {nr}")
+    return None
+
+
+def check_stripe_profiles(name, profiles, max_offset, lengths, min_diag, diag_sum):
+    """What ties the stripe profiles of a band (api.BandAnalyses.stripe_profiles) to its diagonal sums (marginals,
+    at the same bin size), in exact integers.  The cell of V[k][o][c] at distance d is the pixel (x, y) = (c - d,
+    c + o) of diagonal d + o.  For o >= 0 every pixel of that diagonal has its anchor inside the chromosome, 0 <= x
+    + d = c = y - o < ncols, so
+        sum over c of V[k][o][c] = sum over d0 <= d < L_k of diag_sum[d + o]             (o >= 0)
+    and likewise the cell (c + o, c + d) of H, of diagonal d - o, has 0 <= x - o = c = y - d < ncols for o <= 0:
+        sum over c of H[k][o][c] = sum over d0 <= d < L_k of diag_sum[d - o]             (o <= 0).
+    The other signs lose edge pixels: for o < 0 the anchor of a pixel in one of the last |o| columns, c = y + |o|,
+    lies beyond the chromosome, and for o > 0 that of a pixel in one of the first o rows, c = x - o, before it; such
+    a pixel is in no profile, and the sum falls short of the diagonals by what those pixels hold.
+    RuntimeError, naming the interval, the direction, the length and the offset, when one does not hold."""
+    diag = [int(x) for x in diag_sum]
+    m, d0 = int(max_offset), int(min_diag)
+    if max(int(x) for x in lengths) + m > len(diag):
+        raise RuntimeError(f"{name}: the length of {max(lengths)} bins with the offset {m} leaves the {len(diag)} diagonals")
+    for direction, word in enumerate(("upstream", "downstream")):
+        for k, length in enumerate(lengths):
+            for o in range(m + 1):
+                row = profiles[direction][k][m + o if direction == 0 else m - o]
+                got, want = sum(int(x) for x in row), sum(diag[d + o] for d in range(d0, int(length)))
+                if got != want:
+                    raise RuntimeError(f"{name}: the {word} profiles of length {int(length)} at offset "
+                                       f"{o if direction == 0 else -o} add up to {got}, the diagonals {d0 + o} to "
+                                       f"{int(length) + o - 1} give {want}")
+
+
+def stripe_calls_header(calls):
+    """the two header lines of <prefix>_stripe_calls.bedpe: the options of the cli.StripeCalls `calls`, then the
+    columns"""
+    return (f"# resolution={int(calls.resolution)} lengths={','.join(str(int(x)) for x in calls.lengths)} "
+            f"flank={int(calls.flank)} width={int(calls.width)} fold={float(calls.fold)!r} min_count={int(calls.min_count)} "
+            f"ignore_diags={int(calls.min_diag)} radius={int(calls.radius)}\n"
+            "#chrom1\tstart1\tend1\tchrom2\tstart2\tend2\tdirection\tlength\tcentre_sum\tcentre_cells\tleft_mean\t"
+            "right_mean\tenrichment\tobserved_over_expected\n")
+
+
+def stripe_calls_lines(iv, base, factor, half_width, min_diag, rows):
+    """the rows of <prefix>_stripe_calls.bedpe for one interval, one per api.StripeRow, sorted by anchor, then
+    direction: the anchor (the bins of the centre), the extent of the stripe (the bins at the distances min_diag ..
+    length - 1 from the anchor bin: before it for `up`, behind it for `down`), the direction, the length in base
+    pairs, the sum and the cells of the centre, the means of the two shoulders, the enrichment and the centre over
+    what the distance decay expects, floats as %.17g.  The bins are of `factor` * `base` base pairs, with
+    bin_span's ends."""
+    out = []
+    res, h, d0 = int(base) * int(factor), int(half_width), int(min_diag)
+    for r in sorted(rows, key=lambda r: (r.bin, r.direction)):
+        near, far = (r.bin - r.length + 1, r.bin - d0) if r.direction == 0 else (r.bin + d0, r.bin + r.length - 1)
+        lo1, hi1 = bin_span(iv, base, factor, r.bin - h)[0], bin_span(iv, base, factor, r.bin + h)[1]
+        lo2, hi2 = bin_span(iv, base, factor, near)[0], bin_span(iv, base, factor, far)[1]
+        out.append(f"{iv['name']}\t{lo1}\t{hi1}\t{iv['name']}\t{lo2}\t{hi2}\t{('up', 'down')[r.direction]}\t"
+                   f"{r.length * res}\t{r.centre}\t{r.n_centre}\t{_g17(r.left_mean)}\t{_g17(r.right_mean)}\t"
+                   f"{_g17(r.enrichment)}\t{_g17(r.obs_over_exp)}\n")
+    return out
+
+
+def write_stripe_calls(path, plan, base, calls, each):
+    """<prefix>_stripe_calls.bedpe: the header, then the calls of every entry of the plan that is not skipped, in
+    plan order (the plan is sorted by chromosome), at the bin size of the cli.StripeCalls `calls`.  `each(k, factor,
+    first_bin)` returns the api.StripeRows of plan entry k, or None for an entry without a matrix."""
+    _, h, _, d0, _ = stripe_calls_bins(calls)
+    with open(path, "w") as fh:
+        fh.write(stripe_calls_header(calls))
+        for k, entry, first_bin, factor, _ in plan_bands(plan, base, calls.resolution):
+            got = each(k, factor, first_bin)
+            if got is not None:
+                fh.writelines(stripe_calls_lines(entry["interval"], base, factor, h, d0, got))
+
+
+@_needs_matrix
+def _interval_stripe_calls(sim, plan, ids, marginals, calls, k, factor, first_bin):
+    """write_stripe_calls' callback: the profiles summed on the device from the matrix where it lies (with several
+    ranks: the reduced tensor), checked against the diagonal sums of the marginals pass at the same bin size
+    (check_stripe_profiles) before a row is made of them (api.stripe_rows)"""
+    m, h, lengths, d0, radius = stripe_calls_bins(calls)
+    profiles, _ = sim.stripe_profiles(ids[k], m, lengths, d0, factor, first_bin)
+    diag_sum = marginals(k, factor, first_bin)[0]
+    check_stripe_profiles(interval_name(plan[k]["interval"]), profiles, m, lengths, d0, diag_sum)
+    return api.stripe_rows(profiles, diag_sum, m, lengths, d0, h, calls.fold, calls.min_count, radius)
+
+
+def stripe_calls_file(sim, cfg, plan, ids, sums, marginals, log, calls):
+    """<prefix>_stripe_calls.bedpe of the cli.StripeCalls `calls`"""
+    write_stripe_calls(calls.path, plan, int(cfg.bin_size), calls,
+                       functools.partial(_interval_stripe_calls, sim, plan, ids, marginals, calls))
+    log(f"written {calls.path}")
+
+
 def sample_matrices(sim, cfg, plan, ids, total, subsample, bin_sizes, log, **attrs):
     """Writes `subsample.path`, the cooler (or .mcool) of the kept contacts, and with `subsample.split`
     `subsample.rest_path`, that of the others.  The threshold is that of `subsample.frac`, or with
@@ -1585,7 +1693,8 @@ def write_files(sim, cfg, plan, ids, missed, pre, regions, log, **attrs):
     """Rank 0's files of the plan `pre`, in this order: the cooler or .mcool with the missing-interactions
     warnings (`missed`: of collect_outputs), the sampled matrices (sample_matrices), the dense `regions`, the
     distance-decay curves at every bin size of the file, the coverage without the diagonals below
-    `pre.coverage_min_diag`, then insulation_file, dots_file, pileup_file, domains_file and stripes_file (with `pre.scc` the SCC file too).  All of them read
+    `pre.coverage_min_diag`, then insulation_file, dots_file, pileup_file, domains_file, stripes_file (with `pre.scc` the SCC file too) and
+    stripe_calls_file.  All of them read
     the matrices where they lie (with several ranks: the reduced tensors), after the cooler's INT32 range check
     has passed.  `attrs`: write_pixels' keywords."""
     outputs, bin_sizes = pre.outputs, pre.bin_sizes
@@ -1616,6 +1725,8 @@ def write_files(sim, cfg, plan, ids, missed, pre, regions, log, **attrs):
         domains_file(*shared, pre.domains)
     if pre.stripes is not None:
         stripes_file(*shared, pre.stripes, pre.scc)
+    if getattr(pre, "stripe_calls", None) is not None:  # (an attribute of cli.Preflight, not a field)
+        stripe_calls_file(*shared, pre.stripe_calls)
 
 
 def write_outputs(sim, cfg, plan, ids, tensors, pre, regions=(), log=print, backend="nccl", **attrs):

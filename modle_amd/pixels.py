@@ -10,13 +10,16 @@ kept with one probability by a generator keyed by the pixel's coordinates; the w
 checked and scattered into a band on the GPU; and two bands compared stripe by stripe, the integer sums of
 every bin's vertical and horizontal stripe formed on the GPU and turned into scores by stripe_scores, and
 diagonal by diagonal, the sums of every stratum of the two smoothed matrices formed on the GPU and turned into
-HiCRep's stratum-adjusted correlation coefficient by scc_scores.
+HiCRep's stratum-adjusted correlation coefficient by scc_scores; and the stripe profiles of one band, the sums
+of every bin's upstream and downstream stripe at up to four lengths with their cross-section, formed on the GPU
+and turned into stripe calls by stripe_calls.
 There is no host fallback: without the library or
 without a device the calls fail."""
 import ctypes as C
 import math
 import os
 from collections import namedtuple
+from fractions import Fraction
 
 import numpy as np
 
@@ -38,6 +41,11 @@ MAX_STRIPE = 4096  # MODLE_PIXELS_MAX_STRIPE: the deepest band the rank sums are
 STRIPE_METRICS = ("pearson", "spearman", "rmse", "eucl_dist")  # what stripe_scores forms (evaluate.METRICS)
 SCC_ROWS = 11  # MODLE_PIXELS_SCC_ROWS: n and the five 128-bit sums of a stratum
 MAX_SCC_SMOOTH = 20  # MODLE_PIXELS_MAX_SCC_SMOOTH: the largest half-width of the smoothing box
+MAX_PROFILE_OFFSET, MAX_PROFILE_LENGTHS = 8, 4  # MODLE_PIXELS_MAX_PROFILE_OFFSET, MODLE_PIXELS_MAX_PROFILE_LENGTHS
+# The defaults of stripe_calls: product choices, not measured claims.  A centre 1.5 times either shoulder is the
+# enrichment HiCCUPS asks of a dot against its horizontal and vertical neighbourhoods (DOT_FOLDS); one contact
+# keeps empty stripes out; no thinning unless asked for.
+STRIPE_FOLD, STRIPE_MIN_COUNT, STRIPE_RADIUS = 1.5, 1, 0
 DOT_FOLDS = (1.75, 1.75, 1.5, 1.5)  # HiCCUPS' thresholds: donut, lower-left, horizontal, vertical
 MAX_DOT_EDGES, MAX_DOT_OBS = 63, 16384  # MODLE_PIXELS_MAX_DOT_EDGES, MODLE_PIXELS_MAX_DOT_OBS
 DOT_LAMBDA_CHUNKS = 40  # HiCCUPS' number of lambda-chunk edges (dot_lambda_edges)
@@ -57,7 +65,8 @@ EXPORTS = ["modle_pixels_create", "modle_pixels_destroy", "modle_pixels_count", 
            "modle_pixels_sample_to_host", "modle_pixels_band_classify", "modle_pixels_band_check",
            "modle_pixels_band_fill", "modle_pixels_band_from_host", "modle_pixels_stripes_rows",
            "modle_pixels_stripes", "modle_pixels_stripes_to_host", "modle_pixels_scc_groups", "modle_pixels_scc",
-           "modle_pixels_scc_to_host",
+           "modle_pixels_scc_to_host", "modle_pixels_stripe_profiles", "modle_pixels_stripe_profiles_to_host",
+           "modle_pixels_coarse_stripe_profiles_to_host",
            "modle_pixels_build_caps"]  # every symbol include/modle_pixels.h declares
 # what modle_pixels_build_caps reports of the default build: the workgroups of a stripes launch, the grid's y of
 # the band fill, the workgroups of the band check, the threads of the bin1_offset scan
@@ -201,6 +210,11 @@ def lib():
         lb.modle_pixels_scc_groups.restype = C.c_uint64
         lb.modle_pixels_scc.argtypes = strata + [C.c_void_p, C.c_uint64, C.c_void_p] + err
         lb.modle_pixels_scc_to_host.argtypes = strata + [C.POINTER(C.c_void_p), C.c_void_p] + err
+        prof = [C.c_uint64, u64p, C.c_uint64, C.c_uint64]  # max_offset, lengths (a host array), n_lengths, min_diag
+        lb.modle_pixels_stripe_profiles.argtypes = shape + prof + [C.c_void_p, C.c_uint64, C.c_void_p] + err
+        lb.modle_pixels_stripe_profiles_to_host.argtypes = shape + prof + [C.POINTER(C.c_void_p), C.c_void_p] + err
+        lb.modle_pixels_coarse_stripe_profiles_to_host.argtypes = shape + [C.c_uint64] * 2 + prof + \
+            [C.POINTER(C.c_void_p), C.c_void_p] + err
         lb.modle_pixels_build_caps.argtypes = [u64p]
         lb.modle_pixels_build_caps.restype = None
         for name in EXPORTS:
@@ -709,6 +723,122 @@ def scc_scores(rows, ncols, min_diag, max_diag, include_zeros=False):
     return (top / bottom if bottom > 0 else math.nan), rho, weight
 
 
+PROFILE_RULE = "nrows >= 1, nrows <= ncols, m <= 8, 1 <= K <= 4, d0 >= m, d0 < L_1 < ... < L_K, L_K + m <= nrows"
+
+
+def stripe_profile_misfit(nrows, ncols, max_offset, lengths, min_diag):
+    """None when a stripe-profile call is the accepted one, PROFILE_RULE (include/modle_pixels.h states it for
+    the library, this is the one statement on the host; no device and no library is needed), else which part
+    of the rule it breaks.  d0 >= m keeps every cell on its own side of the main diagonal, L_K + m <= nrows
+    inside the band."""
+    nrows, ncols, m, d0 = int(nrows), int(ncols), int(max_offset), int(min_diag)
+    ls = [int(x) for x in lengths]
+    if not 1 <= nrows <= ncols:
+        return f"a band of {nrows} diagonals and {ncols} bins (1 <= nrows <= ncols)"
+    if not 0 <= m <= MAX_PROFILE_OFFSET:
+        return f"the offset {m} is not in [0, {MAX_PROFILE_OFFSET}]"
+    if not 1 <= len(ls) <= MAX_PROFILE_LENGTHS:
+        return f"{len(ls)} lengths (1 to {MAX_PROFILE_LENGTHS})"
+    if d0 < m:
+        return f"min_diag {d0} is below the offset {m}: a cell would cross the main diagonal"
+    if any(b <= a for a, b in zip([d0] + ls, ls)):
+        return f"min_diag and the lengths {[d0] + ls} do not increase strictly"
+    if ls[-1] + m > nrows:
+        return f"the length {ls[-1]} with the offset {m} leaves the {nrows} diagonals of the band"
+    return None
+
+
+def _profile_args(max_offset, lengths, min_diag):
+    """(m, a ctypes uint64 array or None, K, d0) of a stripe-profile call; what is no uint64 is refused here
+    (ctypes would wrap it silently), everything else by the library"""
+    m, d0, ls = int(max_offset), int(min_diag), [int(x) for x in lengths]
+    if not all(0 <= x < 1 << 64 for x in [m, d0] + ls):
+        raise PixelsError(ERR_ARG, f"stripe_profiles: max_offset, min_diag, lengths = {m}, {d0}, {ls} are no uint64")
+    return m, ((C.c_uint64 * len(ls))(*ls) if ls else None), len(ls), d0
+
+
+def stripe_profile_n_valid(ncols, max_offset, lengths, min_diag):
+    """the number of cells inside the chromosome behind every word of a stripe profile, numpy uint64
+    [2, K, 2 m + 1, ncols] (host only, a closed form): V max(0, min(L_k - 1, c) - d0 + 1), H max(0, min(L_k - 1,
+    ncols - 1 - c) - d0 + 1), and 0 where the column or row c + o lies outside [0, ncols)"""
+    ncols, m, d0 = int(ncols), int(max_offset), int(min_diag)
+    ls = [int(x) for x in lengths]
+    if ncols < 0 or m < 0 or d0 < 0 or not ls or any(x < 0 for x in ls):
+        raise PixelsError(ERR_ARG, "stripe_profile_n_valid: a negative argument or no length")
+    c = np.arange(ncols, dtype=np.int64)
+    out = np.zeros((2, len(ls), 2 * m + 1, ncols), dtype=np.uint64)
+    for k, length in enumerate(ls):
+        up = np.maximum(0, np.minimum(length - 1, c) - d0 + 1)
+        down = np.maximum(0, np.minimum(length - 1, ncols - 1 - c) - d0 + 1)
+        for o in range(-m, m + 1):
+            inside = (c + o >= 0) & (c + o < ncols)
+            out[0, k, o + m] = np.where(inside, up, 0)
+            out[1, k, o + m] = np.where(inside, down, 0)
+    return out
+
+
+StripeCall = namedtuple("StripeCall", "direction bin k centre n_centre left n_left right n_right")
+
+
+def stripe_calls(profiles, n_valid, max_offset, lengths, min_diag, half_width=0, fold=STRIPE_FOLD,
+                 min_count=STRIPE_MIN_COUNT, radius=STRIPE_RADIUS):
+    """The stripes of a band from its profiles (Extractor.stripe_profiles, uint64 [2, K, 2 m + 1, ncols]) and
+    stripe_profile_n_valid of the same call: a list of StripeCall, sorted by (direction, bin).  The one statement
+    of what a stripe is, in Python integers and Fractions.  For direction (0: the stripe runs upstream of the
+    anchor, 1: downstream), length class k and anchor c, with h = `half_width` < m:
+        centre   C = the sum over |o| <= h of T[k][o][c], nC its valid cells
+        left     Bl = the sum over o < -h, nBl its valid cells; right Br, nBr over o > h
+    (direction, k, c) passes when every centre and shoulder cell is valid (every one of the 2 m + 1 words has its
+    L_k - d0 cells: no anchor nearer than m to an end, no stripe that runs off the chromosome at that length),
+    C >= min_count, and C / nC >= fold * max(Bl / nBl, Br / nBr), compared as cross-multiplied integers.  An
+    anchor's call is the largest passing k.  The calls of one direction are thinned to local maxima: a call stays
+    unless another call of its direction within `radius` bins has a larger C / nC, or the same and a smaller bin
+    (api.cluster_dots' rule in one dimension).  `fold`, `min_count` and `radius` default to STRIPE_FOLD,
+    STRIPE_MIN_COUNT, STRIPE_RADIUS: product choices, not measured claims.  A float `fold` means the decimal
+    number it prints as."""
+    m, h, d0 = int(max_offset), int(half_width), int(min_diag)
+    ls = [int(x) for x in lengths]
+    prof, nv = np.asarray(profiles), np.asarray(n_valid)
+    if prof.ndim != 4 or prof.dtype != np.uint64 or prof.shape[:3] != (2, len(ls), 2 * m + 1) or nv.shape != prof.shape:
+        raise ValueError(f"stripe_calls: profiles of shape {prof.shape} and type {prof.dtype} with valid cells of "
+                         f"shape {nv.shape} are no uint64 [2, {len(ls)}, {2 * m + 1}, ncols]")
+    if not 0 <= h < m:
+        raise ValueError(f"stripe_calls: the half width {h} must be below the offset {m}: no shoulder is left")
+    fold = Fraction(str(fold)) if isinstance(fold, float) else Fraction(fold)
+    min_count, radius = int(min_count), int(radius)
+    if fold < 0 or radius < 0:
+        raise ValueError(f"stripe_calls: fold {fold} or radius {radius} is negative")
+    ncols = prof.shape[3]
+    fn, fd = fold.numerator, fold.denominator
+    calls = []
+    for direction in range(2):
+        found = {}  # anchor -> StripeCall of the largest passing k
+        for k, length in enumerate(ls):
+            t = [[int(x) for x in prof[direction, k, o]] for o in range(2 * m + 1)]
+            n = [[int(x) for x in nv[direction, k, o]] for o in range(2 * m + 1)]
+            for c in range(ncols):
+                if any(n[o][c] != length - d0 for o in range(2 * m + 1)):
+                    continue
+                centre = sum(t[o][c] for o in range(m - h, m + h + 1))
+                left, right = sum(t[o][c] for o in range(m - h)), sum(t[o][c] for o in range(m + h + 1, 2 * m + 1))
+                n_centre, n_side = (2 * h + 1) * (length - d0), (m - h) * (length - d0)
+                # C / nC >= (fn / fd) * B / nB  <=>  C * nB * fd >= fn * B * nC
+                if centre >= min_count and all(centre * n_side * fd >= fn * b * n_centre for b in (left, right)):
+                    found[c] = StripeCall(direction, c, k, centre, n_centre, left, n_side, right, n_side)
+        kept = sorted(found.values(), key=lambda s: s.bin)
+        means = [Fraction(s.centre, s.n_centre) for s in kept]
+        for i, s in enumerate(kept):
+            beaten = False
+            for step in (-1, 1):
+                j = i + step
+                while 0 <= j < len(kept) and abs(kept[j].bin - s.bin) <= radius and not beaten:
+                    beaten = means[j] > means[i] or (means[j] == means[i] and kept[j].bin < s.bin)
+                    j += step
+            if not beaten:
+                calls.append(s)
+    return calls
+
+
 class Extractor:
     """One context of the library on one device (modle_pixels_create)."""
 
@@ -1112,6 +1242,34 @@ class Extractor:
               *_strata(smooth, min_diag, max_diag), C.byref(ptr), _stream_ptr(stream))
         return _host_array(ptr.value, SCC_ROWS * int(nrows), np.uint64).reshape(SCC_ROWS, int(nrows))
 
+    def stripe_profiles_into(self, d_band, nrows, ncols, max_offset, lengths, min_diag, d_out, out_words, stream=None):
+        """enqueues the stripe profiles of the band into the caller-owned device array `d_out` (uint64[2][K][2 m +
+        1][ncols], 8-byte aligned, `out_words` == 2 * K * (2 m + 1) * ncols): per direction (0 V, the stripe
+        upstream of the anchor; 1 H, downstream), length L_k and offset o in [-m, m] the sum of the stripe's cells
+        at the distances min_diag <= d < L_k, seen o bins to the side; PROFILE_RULE is the accepted call; every
+        word is written (modle_pixels_stripe_profiles)"""
+        m, ls, n, d0 = _profile_args(max_offset, lengths, min_diag)
+        _call(self._L.modle_pixels_stripe_profiles, self._h, d_band, int(nrows), int(ncols), m, ls, n, d0, d_out,
+              int(out_words), _stream_ptr(stream))
+
+    def stripe_profiles(self, d_band, nrows, ncols, max_offset, lengths, min_diag, stream=None, factor=1, first_bin=0,
+                        coarse=None):
+        """the sums of stripe_profiles_into as a numpy uint64[2, K, 2 m + 1, ncols] the caller owns, formed on the
+        device (modle_pixels_stripe_profiles_to_host); stripe_calls turns them into calls"""
+        fn, band, shape = self._form("stripe_profiles_", d_band, nrows, ncols, factor, first_bin, coarse)
+        m, ls, n, d0 = _profile_args(max_offset, lengths, min_diag)
+        ptr = C.c_void_p()
+        _call(fn, self._h, *band, m, ls, n, d0, C.byref(ptr), _stream_ptr(stream))
+        nc = shape()[1]
+        return _host_array(ptr.value, 2 * n * (2 * m + 1) * nc, np.uint64).reshape(2, n, 2 * m + 1, nc)
+
+    def coarse_stripe_profiles(self, d_band, nrows, ncols, factor, first_bin, max_offset, lengths, min_diag,
+                               stream=None):
+        """`stripe_profiles` of the band at `factor` times its bin size, coarsened on the device
+        (modle_pixels_coarse_stripe_profiles_to_host): uint64[2, K, 2 m + 1, ncols'] of coarse_shape; the lengths,
+        the offset and `min_diag` count coarse bins, and PROFILE_RULE holds against nrows'"""
+        return self.stripe_profiles(d_band, nrows, ncols, max_offset, lengths, min_diag, stream, factor, first_bin, True)
+
 
 def extractor(device=0):
     """the process-wide context of `device`"""
@@ -1297,3 +1455,23 @@ def scc(d_ref, d_tgt, nrows, ncols, smooth=0, min_diag=1, max_diag=None, stream=
     """The sums of the strata of the bands at device pointers `d_ref` and `d_tgt`: numpy uint64[SCC_ROWS, nrows],
     formed on the device."""
     return extractor(device).scc(d_ref, d_tgt, nrows, ncols, smooth, min_diag, max_diag, stream)
+
+
+def stripe_profiles_into(d_band, nrows, ncols, max_offset, lengths, min_diag, d_out, out_words, stream=None, device=0):
+    """The stripe profiles of the band at device pointer `d_band`, into the device array `d_out`
+    (uint64[2][K][2 m + 1][ncols]); enqueued on `stream`, nothing crosses to the host."""
+    extractor(device).stripe_profiles_into(d_band, nrows, ncols, max_offset, lengths, min_diag, d_out, out_words, stream)
+
+
+def stripe_profiles(d_band, nrows, ncols, max_offset, lengths, min_diag, stream=None, device=0):
+    """The stripe profiles of the band at device pointer `d_band`: numpy uint64[2, K, 2 m + 1, ncols], formed
+    on the device."""
+    return extractor(device).stripe_profiles(d_band, nrows, ncols, max_offset, lengths, min_diag, stream)
+
+
+def coarse_stripe_profiles(d_band, nrows, ncols, factor, first_bin, max_offset, lengths, min_diag, stream=None,
+                           device=0):
+    """The stripe profiles of the band at `factor` times its bin size: numpy uint64[2, K, 2 m + 1, ncols'],
+    coarsened and formed on the device."""
+    return extractor(device).coarse_stripe_profiles(d_band, nrows, ncols, factor, first_bin, max_offset, lengths,
+                                                    min_diag, stream)
