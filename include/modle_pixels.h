@@ -2,7 +2,7 @@
  * coarsening of a band, of its dense regions, of its marginals, of its insulation sums, of its
  * dot candidates, of its pileups (fixed windows and rescaled ones) and of its random sampling, of the
  * way back from sorted pixels to a band, of the comparison of two bands stripe by stripe and diagonal
- * by diagonal, and of the stripe profiles of one band (further down).
+ * by diagonal, of the stripe profiles of one band and of its triangle sums (further down).
  *
  * The simulation leaves every interval as a dense band matrix in device memory
  * (modle_hip_interval_outputs).  A cooler file is made of the non-zero pixels only, sorted by
@@ -835,6 +835,54 @@ int modle_pixels_coarse_stripe_profiles_to_host(modle_pixels_handle* h, const ui
                                                 uint64_t max_offset, const uint64_t* lengths, uint64_t n_lengths,
                                                 uint64_t min_diag, const uint64_t** profiles, void* stream,
                                                 char* err, size_t errlen);
+
+/* ---- triangle sums: the contacts inside every window on the diagonal --------------------------------------
+ *
+ * What every dynamic-programming domain caller scores (Armatus, Filippova et al. 2014; the modularity form of
+ * MrTADFinder, Yan et al. 2017).  M(a, c) is the matrix of the band, band[c * nrows + (c - a)].  For `max_width` =
+ * W, `min_diag` = d0, every start s < ncols and every k < W:
+ *     T[k][s] = sum of M(a, c) over  s <= a <= c < min(s + k + 1, ncols),  c - a >= d0
+ * the upper triangle of the window of k + 1 bins that starts at bin s, diagonal included, clipped at the
+ * chromosome's end.  The output is uint64[W][ncols].  1 <= W <= nrows keeps every cell inside the band, so the
+ * result is that of the full matrix; d0 >= W gives zeros.  A sum has at most W (W + 1) / 2 terms below 2^32, which
+ * stays below 2^64 for W <= MODLE_PIXELS_MAX_TRIANGLE_WIDTH: wider tables are refused from the arguments alone.
+ * With one table any score f(sum, width) costs O(1) per window, and a diamond of the insulation is a difference
+ * of three triangles.  The decision is one host statement (modle_amd/pixels.py: domain_calls).
+ *
+ * EVERY output word is written, and its final value stored last, with plain stores: the caller does not pre-zero.
+ * The table is formed in the output itself (the column prefixes first, then their prefix along k in place): no
+ * scratch memory of the context is used, there are no atomics and no result depends on the launch.  The words of
+ * the band that are no pixels (d > c, and the one word beyond the band) are never read.  Nothing here uses floating
+ * point.
+ *
+ * MODLE_PIXELS_ERR_ARG, with nothing written: a null pointer, nrows == 0, nrows > ncols, max_width == 0, max_width
+ * > nrows, max_width > MODLE_PIXELS_MAX_TRIANGLE_WIDTH, out_words < max_width * ncols, a d_out that is not 8-byte
+ * aligned or overlaps the band. */
+#define MODLE_PIXELS_MAX_TRIANGLE_WIDTH 65535
+
+/* Enqueues the table into the device array d_out (uint64[W][ncols]) on `stream`; the call does not wait. */
+int modle_pixels_triangles(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols,
+                           uint64_t max_width, uint64_t min_diag, uint64_t* d_out, uint64_t out_words, void* stream,
+                           char* err, size_t errlen);
+
+/* The same into a pinned host buffer of the context (grown on demand, freed by modle_pixels_destroy): *table
+ * (uint64[W][ncols]) stays valid until the next call on the context.  Waits for `stream`. */
+int modle_pixels_triangles_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols,
+                                   uint64_t max_width, uint64_t min_diag, const uint64_t** table, void* stream,
+                                   char* err, size_t errlen);
+
+/* The band coarsened by `factor` into scratch of the context (as modle_pixels_coarse_insulation_to_host), then
+ * modle_pixels_triangles_to_host on it.  *table is uint64[W][ncols']; the widths and min_diag count coarse bins,
+ * and the rule holds against nrows'. */
+int modle_pixels_coarse_triangles_to_host(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows,
+                                          uint64_t ncols, uint64_t factor, uint64_t first_bin, uint64_t max_width,
+                                          uint64_t min_diag, const uint64_t** table, void* stream, char* err,
+                                          size_t errlen);
+
+/* Host only, no device is needed: the number of pixels behind every word of the table, cells[k * ncols + s] =
+ * (w' - d0)(w' - d0 + 1) / 2 with w' = min(k + 1, ncols - s), or 0 when w' <= d0.  MODLE_PIXELS_ERR_ARG for a null
+ * pointer, max_width == 0 or a width above the cap. */
+int modle_pixels_triangle_cells(uint64_t ncols, uint64_t max_width, uint64_t min_diag, uint64_t* cells);
 
 /* The launch caps this build of the library was compiled with, for the tests that lower them: caps[0] the
  * workgroups of a stripes launch at most (2^20), caps[1] the grid's y of the band fill at most (65535),

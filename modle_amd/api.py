@@ -442,6 +442,37 @@ def stripe_rows(profiles, diag_sum, max_offset, lengths, min_diag, half_width=0,
     return rows
 
 
+def insulation_from_triangles(table, windows):
+    """The insulation sums of a band from its triangle table (BandAnalyses.triangle_sums, uint64 [W, ncols]), numpy
+    uint64 [len(windows), ncols], equal word for word to BandAnalyses.insulation at the `min_diag` of the table: the
+    diamond of bin b and window w, the pixels (a, c) with b - w < a <= b <= c < b + w, is the triangle of the
+    window [b - w + 1, b + w) without the two triangles that lie to either side of bin b,
+        ins(b, w) = T(b - w + 1, b + w) - T(b - w + 1, b) - T(b + 1, b + w),
+    T(s, e) = table[e - s - 1][max(s, 0)] being the triangle of the bins [s, e), cut at the chromosome's ends, and 0
+    when it is empty.  ValueError unless 1 <= w and 2 w - 1 <= W for every window."""
+    tab = np.asarray(table)
+    if tab.ndim != 2 or tab.dtype != np.uint64:
+        raise ValueError(f"insulation_from_triangles: a table of shape {tab.shape} and type {tab.dtype} is no uint64 "
+                         "[W, ncols]")
+    width, ncols = tab.shape
+    ws = [int(w) for w in windows]
+    if any(w < 1 or 2 * w - 1 > width for w in ws):
+        raise ValueError(f"insulation_from_triangles: the windows {ws} need 1 <= w and 2 w - 1 <= {width}, the widths "
+                         "of the table")
+
+    def triangle(s, e):  # arrays of starts and ends; the end is cut by the table itself
+        s = np.maximum(s, 0)
+        n = e - s
+        some = (n > 0) & (s < ncols)
+        return np.where(some, tab[np.where(some, n - 1, 0), np.where(some, s, 0)], np.uint64(0))
+
+    b = np.arange(ncols, dtype=np.int64)
+    out = np.zeros((len(ws), ncols), dtype=np.uint64)
+    for i, w in enumerate(ws):
+        out[i] = triangle(b - w + 1, b + w) - triangle(b - w + 1, b) - triangle(b + 1, b + w)
+    return out
+
+
 class BandAnalyses:
     """The analyses of a band matrix in device memory, for any owner of bands that has `device` and
     `outputs(id)` -> (device pointer of the band, occupancy pointer or None, nrows, ncols): the Simulator, whose
@@ -1084,6 +1115,45 @@ class BandAnalyses:
         prof, _ = self.stripe_profiles(interval_id, max_offset, lengths, min_diag, factor, first_bin)
         diag_sum, _ = self.marginals(interval_id, 0, factor, first_bin)
         return stripe_rows(prof, diag_sum, max_offset, lengths, min_diag, half_width, fold, min_count, radius)
+
+    def triangle_sums(self, interval_id, max_width, min_diag=0, factor=1, first_bin=0, stream=None):
+        """The triangle table of the interval, numpy uint64 [max_width, ncols]: T[k][s] is the sum of the contacts
+        inside the window of k + 1 bins that starts at bin s (the pixels (a, c), s <= a <= c < min(s + k + 1, ncols),
+        without the diagonals below `min_diag`; include/modle_pixels.h), formed on the device from the band where it
+        lies (pixels.triangles_to_host).  pixels.TRIANGLE_RULE is the accepted call, pixels.triangle_cells the number
+        of pixels behind every word.  Call it after wait().  With `factor` > 1 the band is first coarsened on the
+        device (`first_bin` as for pixels()) and the widths and `min_diag` count coarse bins."""
+        from . import pixels
+
+        d_band, _, nrows, ncols = self.outputs(interval_id)
+        return pixels.extractor(self.device).triangles_to_host(d_band, nrows, ncols, max_width, min_diag, stream,
+                                                               factor, first_bin)
+
+    def triangle_sums_tensor(self, interval_id, max_width, min_diag=0, stream=None):
+        """The table of triangle_sums as one torch int64 tensor [max_width, ncols] on the device, filled there by
+        the kernels: nothing crosses to the host (the objective or the feature map of a fitting loop).  The words
+        hold the uint64 sums bit for bit.  The work is enqueued on `stream` (None: the default stream, on which
+        torch orders its own work) and not waited for."""
+        import torch
+
+        from . import pixels
+
+        d_band, _, nrows, ncols = self.outputs(interval_id)
+        out = torch.empty((int(max_width), ncols), dtype=torch.int64, device=torch.device("cuda", self.device))
+        pixels.triangles_into(d_band, nrows, ncols, max_width, min_diag, out.data_ptr(), out.numel(), stream,
+                              device=self.device)
+        return out
+
+    def call_domains(self, interval_id, max_width, min_diag=0, gamma=None, min_width=None, factor=1, first_bin=0):
+        """The domains of the interval, a list of pixels.DomainCall sorted by start (bins [start, end) of `factor`
+        times the bin size): pixels.domain_calls of triangle_sums, formed on the device, and of
+        pixels.triangle_cells.  None for `gamma`, `min_width`: the defaults of pixels.domain_calls.  ValueError
+        when a sum reaches 2^53."""
+        from . import pixels
+
+        table = self.triangle_sums(interval_id, max_width, min_diag, factor, first_bin)
+        options = {name: v for name, v in (("gamma", gamma), ("min_width", min_width)) if v is not None}
+        return pixels.domain_calls(table, pixels.triangle_cells(table.shape[1], max_width, min_diag), **options)
 
 
 # ---------------------------------------------------------------------------------------------

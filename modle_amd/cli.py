@@ -50,6 +50,15 @@ calls of one direction are thinned to the best within --call-stripes-radius D (d
 --call-stripes-ignore-diags N leaves out the first N diagonals (default and at least the bins of the flank, 2 at
 least) and --call-stripes-resolution R (a multiple of -r, coarsened on the GPU; default -r) sets the bin size.  The
 fold, the count and the radius are choices, not measured optima; the rule is pixels.stripe_calls', not Stripenn's.
+With --call-domains `<prefix>_domain_calls.bed` (chrom, start, end, name, score, strength), the domains of every
+interval: the contacts inside every window on the diagonal, of every start and every width up to
+--call-domains-max-width D (default 2mb, clamped to the band), are summed on the GPU into one table, and the
+disjoint windows of at least --call-domains-min-width D (default 3 bins) are called that maximise the sum of
+their contacts less --call-domains-gamma G (default 1) times the mean of the chromosome's windows of their width
+(pixels.domain_calls; the strength is the window over that mean).  --call-domains-ignore-diags N leaves out the
+first N diagonals (default 2) and --call-domains-resolution R (a multiple of -r, coarsened on the GPU; default -r)
+sets the bin size.  With --call-domains, and only then, `--domains-at called` averages the domains just called.
+The rule is the project's own, neither Armatus' exponent nor a p-value, and its defaults are choices.
 Everything heavy is native: parsing and
 task generation in libmodle_hip.so (host), the simulation on the MI355X (one process per GPU;
 under torch.distributed.run the cells are sharded over the ranks and the matrices are summed
@@ -239,6 +248,10 @@ def stripe_calls_path(prefix):
     return prefix + "_stripe_calls.bedpe"
 
 
+def domain_calls_path(prefix):
+    return prefix + "_domain_calls.bed"
+
+
 def sampled_paths(prefix, mcool=False):
     """(the file of the kept contacts, the file of the others) of --subsample-frac / --subsample-to"""
     ext = ".mcool" if mcool else ".cool"
@@ -371,6 +384,15 @@ def add_analysis_arguments(io):
     io.add_argument("--call-stripes-ignore-diags", type=int, default=None, metavar="N", help=argparse.SUPPRESS)
     io.add_argument("--call-stripes-radius", type=genomic_distance, default=None, metavar="D", help=argparse.SUPPRESS)
     io.add_argument("--call-stripes-resolution", type=genomic_distance, default=None, metavar="R",
+                    help=argparse.SUPPRESS)
+    # Domain calling (<prefix>_domain_calls.bed; the module's text describes the options), kept out of the
+    # generated help likewise
+    io.add_argument("--call-domains", action="store_true", default=None, help=argparse.SUPPRESS)
+    io.add_argument("--call-domains-max-width", type=genomic_distance, default=None, metavar="D", help=argparse.SUPPRESS)
+    io.add_argument("--call-domains-min-width", type=genomic_distance, default=None, metavar="D", help=argparse.SUPPRESS)
+    io.add_argument("--call-domains-gamma", type=float, default=None, metavar="G", help=argparse.SUPPRESS)
+    io.add_argument("--call-domains-ignore-diags", type=int, default=None, metavar="N", help=argparse.SUPPRESS)
+    io.add_argument("--call-domains-resolution", type=genomic_distance, default=None, metavar="R",
                     help=argparse.SUPPRESS)
 
 
@@ -574,21 +596,31 @@ _PreflightFields = collections.namedtuple(
 StripeCalls = collections.namedtuple("StripeCalls", "path resolution lengths flank width fold min_count min_diag radius")
 
 
-class Preflight(_PreflightFields):
-    """The 13 fields above, and the StripeCalls as the attribute `stripe_calls` (None: not asked for).  It is no
-    fourteenth field: the tuple is also made positionally and unpacked by its length, and a record that is new
-    must not move what those users see.  Keyword-only here, kept by _replace."""
-    stripe_calls = None  # (of an instance that _make made)
+# what --call-domains asks for: the file (None with --skip-output), the bin size, the largest and the smallest
+# width in base pairs, gamma and the diagonals left out
+DomainCalls = collections.namedtuple("DomainCalls", "path resolution max_width min_width gamma min_diag")
 
-    def __new__(cls, *args, stripe_calls=None, **kw):
+
+class Preflight(_PreflightFields):
+    """The 13 fields above, and the StripeCalls and the DomainCalls as the attributes `stripe_calls` and
+    `domain_calls` (None: not asked for).  They are no further fields: the tuple is also made positionally and
+    unpacked by its length, and a record that is new must not move what those users see.  Keyword-only here,
+    kept by _replace."""
+    stripe_calls = None  # (of an instance that _make made)
+    domain_calls = None
+
+    def __new__(cls, *args, stripe_calls=None, domain_calls=None, **kw):
         self = super().__new__(cls, *args, **kw)
         self.stripe_calls = stripe_calls
+        self.domain_calls = domain_calls
         return self
 
     def _replace(self, **kw):
         stripe_calls = kw.pop("stripe_calls", self.stripe_calls)
+        domain_calls = kw.pop("domain_calls", self.domain_calls)
         out = super()._replace(**kw)
         out.stripe_calls = stripe_calls
+        out.domain_calls = domain_calls
         return out
 
 
@@ -847,6 +879,39 @@ def stripe_calls_options(a, cfg):
     return StripeCalls(_file(a, stripe_calls_path), res, lengths, flank, width, fold, min_count, min_diag, radius)
 
 
+def domain_calls_options(a, cfg):
+    """The domain calling the arguments ask for, as a DomainCalls, or None.  SystemExit: a --call-domains-* option
+    without --call-domains, a resolution that is no multiple of -r, a width that is no positive multiple of the
+    resolution of the calls, a largest width below the smallest or above pixels.MAX_TRIANGLE_WIDTH bins, a gamma
+    that is negative or not finite, a negative number of diagonals.  The defaults are product choices: 2 Mb (the
+    whole bins of it, one at least; every band clamps it to its diagonals), pixels.DOMAIN_MIN_WIDTH bins,
+    pixels.DOMAIN_GAMMA, two diagonals ignored."""
+    given = (("--call-domains-max-width", a.call_domains_max_width), ("--call-domains-min-width", a.call_domains_min_width),
+             ("--call-domains-gamma", a.call_domains_gamma), ("--call-domains-ignore-diags", a.call_domains_ignore_diags),
+             ("--call-domains-resolution", a.call_domains_resolution))
+    if not a.call_domains:
+        _needs("--call-domains", given)
+        return None
+    res = _analysis_resolution("--call-domains-resolution", a.call_domains_resolution, cfg)
+    least = pixels.DOMAIN_MIN_WIDTH * res if a.call_domains_min_width is None else int(a.call_domains_min_width)
+    most = max(least, max(1, 2_000_000 // res) * res) if a.call_domains_max_width is None else int(a.call_domains_max_width)
+    for name, v in (("--call-domains-min-width", least), ("--call-domains-max-width", most)):
+        if v < res or v % res != 0:
+            raise SystemExit(f"{name}: {v} is not a positive multiple of the resolution of the calls ({res})")
+    if most < least:
+        raise SystemExit(f"--call-domains-max-width: {most} is below the smallest width ({least})")
+    if most // res > pixels.MAX_TRIANGLE_WIDTH:
+        raise SystemExit(f"--call-domains-max-width: {most} is {most // res} bins of {res}: at most "
+                         f"{pixels.MAX_TRIANGLE_WIDTH}")
+    gamma = pixels.DOMAIN_GAMMA if a.call_domains_gamma is None else a.call_domains_gamma
+    if not 0.0 <= gamma < float("inf"):  # (false for NaN)
+        raise SystemExit(f"--call-domains-gamma: {gamma} is not a finite number that is not negative")
+    min_diag = 2 if a.call_domains_ignore_diags is None else a.call_domains_ignore_diags
+    if min_diag < 0:
+        raise SystemExit(f"--call-domains-ignore-diags: {min_diag} is negative")
+    return DomainCalls(_file(a, domain_calls_path), res, most, least, gamma, min_diag)
+
+
 def insulation_options(a, cfg):
     """The insulation track the arguments ask for, as an Insulation, or None.
     SystemExit: --insulation-resolution or --insulation-ignore-diags without --insulation-windows, a
@@ -874,13 +939,13 @@ def preflight(a, cfg):
     """The whole plan of the run, a Preflight: what the arguments alone settle and refuse, without a genome or
     a GPU.  Nothing after it derives an analysis from the arguments again.  SystemExit:
     --coverage-ignore-diags without --coverage, or negative; what insulation_options, dots_options,
-    pileup_options, domains_options, subsample_options, stripes_options, scc_options and stripe_calls_options
-    refuse, in that order
+    pileup_options, domains_options, subsample_options, stripes_options, scc_options, stripe_calls_options and
+    domain_calls_options refuse, in that order
     (stripes_options
     opens the reference cooler, the one time it is opened before the launch); a bad --mcool-resolutions list; on
     rank 0, an output that exists without --force (cooler or .mcool, then bigwig, then .npz, then the expected,
     the coverage, the insulation, the dots, the pileup and the domains file, then the sampled files, then the
-    stripes, then the SCC, then the stripe calls).  With
+    stripes, then the SCC, then the stripe calls, then the domain calls).  With
     --skip-output no file is planned and none is looked at."""
     if a.coverage_ignore_diags is not None:
         if not a.coverage:
@@ -895,6 +960,7 @@ def preflight(a, cfg):
     cmp_ = stripes_options(a, cfg)
     scc = scc_options(a, cfg, cmp_)
     calls = stripe_calls_options(a, cfg)
+    called = domain_calls_options(a, cfg)
     # (a bad list ends the run here, before anything is imported or simulated)
     bin_sizes = None if a.mcool_resolutions is None else mcool_bin_sizes(a.mcool_resolutions, cfg.bin_size)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -902,7 +968,8 @@ def preflight(a, cfg):
     device = a.device if a.device is not None else int(os.environ.get("LOCAL_RANK", "0"))
     analyses = (ins, dots, pile, sub, cmp_, a.coverage_ignore_diags or 0, dom, scc)
     if a.skip_output:
-        return Preflight(bin_sizes, Outputs(None, None, None, None), rank, world, device, *analyses, stripe_calls=calls)
+        return Preflight(bin_sizes, Outputs(None, None, None, None), rank, world, device, *analyses, stripe_calls=calls,
+                         domain_calls=called)
     cool_path, bw_path = output_paths(a.output_prefix, mcool=bin_sizes is not None)
     # (cli.cpp:871-875; with several ranks every rank writes its own)
     log_path = a.output_prefix + ("_internal_state.log.gz" if world == 1 else f"_internal_state.rank{rank}.log.gz")
@@ -918,10 +985,11 @@ def preflight(a, cfg):
         planned += [cmp_.path] if cmp_ is not None else []
         planned += [scc.path] if scc is not None else []
         planned += [calls.path] if calls is not None else []
+        planned += [called.path] if called is not None else []
         for p in planned:
             if p and os.path.exists(p) and not a.force:
                 raise SystemExit(f"refusing to overwrite {p}: pass --force to overwrite")
-    return Preflight(bin_sizes, outputs, rank, world, device, *analyses, stripe_calls=calls)
+    return Preflight(bin_sizes, outputs, rank, world, device, *analyses, stripe_calls=calls, domain_calls=called)
 
 
 def plan_run(a, cfg, pre, log):
@@ -966,8 +1034,9 @@ def check_plan(a, cfg, pre, plan, chroms):
                              f"not fit the band of {bad[1]} ({bad[4]} diagonals): the largest flank that fits is "
                              f"{bad[5]} ({bad[5] // pre.pileup.resolution} bins)")
     if pre.domains is not None and pre.domains.path is not None:
-        bad = driver.domains_misfit(plan, int(cfg.bin_size), pre.domains.resolution, pre.domains.size,
-                                    pre.domains.sources)
+        # (with --call-domains the source `called` is no file: it stands for the domains the run calls)
+        sources = [x for x in pre.domains.sources if pre.domain_calls is None or x != driver.CALLED_DOMAINS]
+        bad = driver.domains_misfit(plan, int(cfg.bin_size), pre.domains.resolution, pre.domains.size, sources)
         if bad is not None and bad[0] == "bed":
             raise SystemExit(f"--domains-at {bad[1]}: the file cannot be read as BED: {bad[2]}")
         if bad is not None:
@@ -1086,11 +1155,18 @@ def analyze_plan(cfg, reader, names):
     return plan
 
 
-def check_band_memory(plan, free_bytes):
+def check_band_memory(plan, free_bytes, table_bytes=0):
     """SystemExit when the bands of the plan and the scratch of the analyses, ANALYSIS_SCRATCH_BANDS times the
-    largest band, exceed `free_bytes` of device memory"""
+    largest band and `table_bytes`, the largest triangle table of --call-domains
+    (driver.domain_calls_table_bytes), exceed `free_bytes` of device memory"""
     sizes = [(e["nrows"] * e["ncols"] + 1) * 4 for e in plan]
-    need = sum(sizes) + ANALYSIS_SCRATCH_BANDS * max(sizes, default=0)
+    need = sum(sizes) + ANALYSIS_SCRATCH_BANDS * max(sizes, default=0) + int(table_bytes)
+    if table_bytes and need > free_bytes:
+        raise SystemExit(f"analyze: the bands of the {len(plan)} chromosomes ({sum(sizes)} bytes), the scratch of "
+                         f"the analyses ({ANALYSIS_SCRATCH_BANDS} times the largest band, {max(sizes)} bytes) and the "
+                         f"triangle table of --call-domains ({int(table_bytes)} bytes) need {need} bytes; the device has "
+                         f"{int(free_bytes)} free: lower --call-domains-max-width, narrow the band with -w or take "
+                         "fewer chromosomes with --chromosomes")
     if need > free_bytes:
         raise SystemExit(f"analyze: the bands of the {len(plan)} chromosomes ({sum(sizes)} bytes) and the scratch of "
                          f"the analyses ({ANALYSIS_SCRATCH_BANDS} times the largest band, {max(sizes)} bytes) need "
@@ -1156,7 +1232,9 @@ def analyze(a, log=print):
         plan = analyze_plan(cfg, reader, set(names))
         import torch
 
-        check_band_memory(plan, torch.cuda.mem_get_info(pre.device)[0])
+        table = 0 if pre.domain_calls is None else driver.domain_calls_table_bytes(plan, int(cfg.bin_size),
+                                                                                    pre.domain_calls)
+        check_band_memory(plan, torch.cuda.mem_get_info(pre.device)[0], table)
         bands = api.LoadedBands(pre.device)
         try:
             ids = load_bands(bands, reader, plan, log)

@@ -1040,6 +1040,9 @@ def place_domains(plan, base, resolution, flank_percent, domains):
     return {k: (np.array(s, dtype=np.int64), np.array(e, dtype=np.int64)) for k, (s, e) in placed.items()}, unplaced
 
 
+CALLED_DOMAINS = "called"  # the source of --domains-at that, with --call-domains, stands for the domains just called
+
+
 def domains_misfit(plan, base, resolution, size, sources=()):
     """What refuses the average domain before anything is simulated, or None: ("bed", path, why) for the first
     source that read_bed cannot read, else ("size", the grid side, the diagonals of the deepest band) when the
@@ -1507,6 +1510,130 @@ def stripe_calls_file(sim, cfg, plan, ids, sums, marginals, log, calls):
     log(f"written {calls.path}")
 
 
+def domain_calls_bins(calls):
+    """(max_width, min_width, min_diag) in bins of the cli.DomainCalls `calls`"""
+    res = int(calls.resolution)
+    return int(calls.max_width) // res, int(calls.min_width) // res, int(calls.min_diag)
+
+
+def domain_calls_table_bytes(plan, base, calls):
+    """the device memory of the largest triangle table --call-domains forms: over the entries of the plan that
+    have a matrix, 8 bytes times the widths (the largest width, clamped to the nrows' diagonals of the band at
+    the resolution of the calls) times the ncols' bins"""
+    width = domain_calls_bins(calls)[0]
+    return max((8 * min(width, nr) * nc for _, entry, _, _, (nr, nc) in plan_bands(plan, base, calls.resolution)
+                if entry["ncols"] != 0), default=0)
+
+
+def _row_sums(table):
+    """the sum of every row of a uint64 table as Python integers: the two halves of the words summed apart, so
+    that no sum wraps"""
+    tab = np.asarray(table, dtype=np.uint64)
+    lo = (tab & np.uint64(0xFFFFFFFF)).sum(axis=1, dtype=np.uint64)
+    hi = (tab >> np.uint64(32)).sum(axis=1, dtype=np.uint64)
+    return [(int(h) << 32) + int(l) for h, l in zip(hi, lo)]
+
+
+def check_triangles(name, table, min_diag, diag_sum, windows=(), ins_sum=None):
+    """What ties the triangle table of a band (api.BandAnalyses.triangle_sums, uint64 [W, ncols]) to its diagonal
+    sums (marginals, at the same bin size), in exact integers.  The window of k + 1 bins at s, less the windows of
+    k bins at s and at s + 1, plus the window of k - 1 bins at s + 1 that both share, leaves the one pixel (s, s +
+    k) of diagonal k, so for every k < W
+        sum over s of T[k][s] - T[k - 1][s] - T[k - 1][s + 1] + T[k - 2][s + 1] = diag_sum[k]   (0 for k < min_diag),
+    rows -1 and -2 and column ncols counting 0; where the chromosome's end clips the windows the four terms
+    cancel.  With `windows` (bins) and `ins_sum`, the insulation sums of the same band at the same `min_diag`
+    (api.BandAnalyses.insulation): every window with 2 w - 1 <= W equals api.insulation_from_triangles of the
+    table word for word.  RuntimeError, naming the interval and the width or the window, when one does not hold."""
+    tab = np.asarray(table)
+    diag = [int(x) for x in diag_sum]
+    width, d0 = tab.shape[0], int(min_diag)
+    if width > len(diag):
+        raise RuntimeError(f"{name}: the triangle table has {width} widths, the band {len(diag)} diagonals")
+    rows = _row_sums(tab)
+    first = [int(x) for x in tab[:, 0]] if tab.shape[1] else [0] * width
+
+    def shifted(k):  # the sum over s of T[k][s + 1]
+        return rows[k] - first[k] if k >= 0 else 0
+
+    for k in range(width):
+        got = rows[k] - (rows[k - 1] if k >= 1 else 0) - shifted(k - 1) + shifted(k - 2)
+        want = diag[k] if k >= d0 else 0
+        if got != want:
+            raise RuntimeError(f"{name}: the windows of {k + 1} bins hold {got} contacts on diagonal {k} beyond those "
+                               f"of {k} bins, the diagonal sums give {want}")
+    if ins_sum is not None:
+        for w, row in zip(windows, ins_sum):
+            if 2 * int(w) - 1 <= width and not np.array_equal(api.insulation_from_triangles(tab, [int(w)])[0],
+                                                               np.asarray(row, dtype=np.uint64)):
+                raise RuntimeError(f"{name}: the insulation sums of the window of {int(w)} bins are not the "
+                                   "difference of three triangles of the table")
+
+
+def domain_calls_header(calls):
+    """the two header lines of <prefix>_domain_calls.bed: the options of the cli.DomainCalls `calls`, then the
+    columns"""
+    return (f"# resolution={int(calls.resolution)} max_width={int(calls.max_width)} min_width={int(calls.min_width)} "
+            f"gamma={float(calls.gamma)!r} ignore_diags={int(calls.min_diag)}\n"
+            "#chrom\tstart\tend\tname\tscore\tstrength\n")
+
+
+def domain_calls_lines(iv, base, factor, rows):
+    """the rows of <prefix>_domain_calls.bed for one interval, one per pixels.DomainCall, in the order of their
+    starts: the chromosome, the start of the first and the end of the last bin of the domain (bins of `factor` *
+    `base` base pairs with bin_span's ends), a name made of the three, the score and the strength as %.17g"""
+    out = []
+    for r in rows:
+        lo, hi = bin_span(iv, base, factor, r.start)[0], bin_span(iv, base, factor, r.end - 1)[1]
+        out.append(f"{iv['name']}\t{lo}\t{hi}\t{iv['name']}:{lo}-{hi}\t{_g17(r.score)}\t{_g17(r.strength)}\n")
+    return out
+
+
+def write_domain_calls(path, plan, base, calls, each):
+    """<prefix>_domain_calls.bed: the header, then the domains of every entry of the plan that is not skipped, in
+    plan order (the plan is sorted by chromosome), at the bin size of the cli.DomainCalls `calls`.  `each(k,
+    factor, first_bin)` returns the pixels.DomainCalls of plan entry k, or None for an entry without a matrix.
+    read_bed reads the file as it is."""
+    with open(path, "w") as fh:
+        fh.write(domain_calls_header(calls))
+        for k, entry, first_bin, factor, _ in plan_bands(plan, base, calls.resolution):
+            got = each(k, factor, first_bin)
+            if got is not None:
+                fh.writelines(domain_calls_lines(entry["interval"], base, factor, got))
+
+
+@_needs_matrix
+def _interval_domain_calls(sim, plan, ids, marginals, calls, insulation, k, factor, first_bin):
+    """write_domain_calls' callback: the triangle table formed on the device from the matrix where it lies (with
+    several ranks: the reduced tensor), the largest width clamped to the band, checked against the diagonal sums
+    of the marginals pass at the same bin size and, when `insulation` (a cli.Insulation or None) ran at the same
+    bin size and with the same diagonals ignored, against its sums (check_triangles) before a row is made of it
+    (pixels.domain_calls)"""
+    from . import pixels
+
+    width, least, d0 = domain_calls_bins(calls)
+    _, _, nrows, ncols = sim.outputs(ids[k])
+    nr, _ = pixels.band_shape(nrows, ncols, factor, first_bin)
+    width = min(width, nr)
+    table = sim.triangle_sums(ids[k], width, d0, factor, first_bin)
+    windows, ins_sum = (), None
+    if insulation is not None and int(insulation.resolution) == int(calls.resolution) and int(insulation.min_diag) == d0:
+        windows = [int(w) // int(insulation.resolution) for w in insulation.windows]
+        ins_sum, _ = sim.insulation(ids[k], windows, d0, factor, first_bin)
+    check_triangles(interval_name(plan[k]["interval"]), table, d0, marginals(k, factor, first_bin)[0], windows, ins_sum)
+    try:
+        return pixels.domain_calls(table, pixels.triangle_cells(table.shape[1], width, d0), gamma=calls.gamma,
+                                   min_width=least)
+    except ValueError as e:
+        raise RuntimeError(f"{interval_name(plan[k]['interval'])}: {e}") from None
+
+
+def domain_calls_file(sim, cfg, plan, ids, sums, marginals, log, calls, insulation=None):
+    """<prefix>_domain_calls.bed of the cli.DomainCalls `calls`"""
+    write_domain_calls(calls.path, plan, int(cfg.bin_size), calls,
+                       functools.partial(_interval_domain_calls, sim, plan, ids, marginals, calls, insulation))
+    log(f"written {calls.path}")
+
+
 def sample_matrices(sim, cfg, plan, ids, total, subsample, bin_sizes, log, **attrs):
     """Writes `subsample.path`, the cooler (or .mcool) of the kept contacts, and with `subsample.split`
     `subsample.rest_path`, that of the others.  The threshold is that of `subsample.frac`, or with
@@ -1653,13 +1780,15 @@ def pileup_file(sim, cfg, plan, ids, sums, marginals, log, pileup, interval_dots
     log(f"written {pileup.path}")
 
 
-def domains_file(sim, cfg, plan, ids, sums, marginals, log, domains):
-    """<prefix>_domains.tsv of the cli.Domains `domains`"""
+def domains_file(sim, cfg, plan, ids, sums, marginals, log, domains, called=None):
+    """<prefix>_domains.tsv of the cli.Domains `domains`; with `called`, the <prefix>_domain_calls.bed that
+    domain_calls_file has just written, the source `called` stands for that file"""
     base, res = int(cfg.bin_size), int(domains.resolution)
     placed, unplaced = {}, {}
     for what in domains.sources:
         if what not in placed:
-            placed[what], unplaced[what] = place_domains(plan, base, res, domains.flank_percent, read_bed(what))
+            bed = called if called is not None and what == CALLED_DOMAINS else what
+            placed[what], unplaced[what] = place_domains(plan, base, res, domains.flank_percent, read_bed(bed))
             if unplaced[what]:
                 log(f"--domains-at {what}: {unplaced[what]} domains lie in no simulated interval")
     write_domains(domains.path, plan, base, res, domains.size, domains.flank_percent, domains.sources,
@@ -1693,7 +1822,8 @@ def write_files(sim, cfg, plan, ids, missed, pre, regions, log, **attrs):
     """Rank 0's files of the plan `pre`, in this order: the cooler or .mcool with the missing-interactions
     warnings (`missed`: of collect_outputs), the sampled matrices (sample_matrices), the dense `regions`, the
     distance-decay curves at every bin size of the file, the coverage without the diagonals below
-    `pre.coverage_min_diag`, then insulation_file, dots_file, pileup_file, domains_file, stripes_file (with `pre.scc` the SCC file too) and
+    `pre.coverage_min_diag`, then insulation_file, dots_file, pileup_file, domain_calls_file, domains_file (whose source
+    `called` reads the domain calls back), stripes_file (with `pre.scc` the SCC file too) and
     stripe_calls_file.  All of them read
     the matrices where they lie (with several ranks: the reduced tensors), after the cooler's INT32 range check
     has passed.  `attrs`: write_pixels' keywords."""
@@ -1721,8 +1851,11 @@ def write_files(sim, cfg, plan, ids, missed, pre, regions, log, **attrs):
     interval_dots = dots_file(*shared, pre.dots) if pre.dots is not None else None
     if pre.pileup is not None:
         pileup_file(*shared, pre.pileup, interval_dots)
+    called = getattr(pre, "domain_calls", None)  # (an attribute of cli.Preflight, not a field)
+    if called is not None:
+        domain_calls_file(*shared, called, pre.insulation)
     if pre.domains is not None:
-        domains_file(*shared, pre.domains)
+        domains_file(*shared, pre.domains, None if called is None else called.path)
     if pre.stripes is not None:
         stripes_file(*shared, pre.stripes, pre.scc)
     if getattr(pre, "stripe_calls", None) is not None:  # (an attribute of cli.Preflight, not a field)

@@ -12,7 +12,8 @@ every bin's vertical and horizontal stripe formed on the GPU and turned into sco
 diagonal by diagonal, the sums of every stratum of the two smoothed matrices formed on the GPU and turned into
 HiCRep's stratum-adjusted correlation coefficient by scc_scores; and the stripe profiles of one band, the sums
 of every bin's upstream and downstream stripe at up to four lengths with their cross-section, formed on the GPU
-and turned into stripe calls by stripe_calls.
+and turned into stripe calls by stripe_calls; and its triangle sums, the contacts inside every window on the
+diagonal up to a largest width, formed on the GPU and turned into domain calls by domain_calls.
 There is no host fallback: without the library or
 without a device the calls fail."""
 import ctypes as C
@@ -46,6 +47,11 @@ MAX_PROFILE_OFFSET, MAX_PROFILE_LENGTHS = 8, 4  # MODLE_PIXELS_MAX_PROFILE_OFFSE
 # enrichment HiCCUPS asks of a dot against its horizontal and vertical neighbourhoods (DOT_FOLDS); one contact
 # keeps empty stripes out; no thinning unless asked for.
 STRIPE_FOLD, STRIPE_MIN_COUNT, STRIPE_RADIUS = 1.5, 1, 0
+MAX_TRIANGLE_WIDTH = 65535  # MODLE_PIXELS_MAX_TRIANGLE_WIDTH: W (W + 1) / 2 pixels below 2^32 stay below 2^64
+# The defaults of domain_calls: product choices, not measured claims.  gamma 1 scores a window against the mean
+# window of its width; three bins is the smallest window that has a pixel beyond the two diagonals `simulate`
+# ignores by default.
+DOMAIN_GAMMA, DOMAIN_MIN_WIDTH = 1.0, 3
 DOT_FOLDS = (1.75, 1.75, 1.5, 1.5)  # HiCCUPS' thresholds: donut, lower-left, horizontal, vertical
 MAX_DOT_EDGES, MAX_DOT_OBS = 63, 16384  # MODLE_PIXELS_MAX_DOT_EDGES, MODLE_PIXELS_MAX_DOT_OBS
 DOT_LAMBDA_CHUNKS = 40  # HiCCUPS' number of lambda-chunk edges (dot_lambda_edges)
@@ -66,7 +72,8 @@ EXPORTS = ["modle_pixels_create", "modle_pixels_destroy", "modle_pixels_count", 
            "modle_pixels_band_fill", "modle_pixels_band_from_host", "modle_pixels_stripes_rows",
            "modle_pixels_stripes", "modle_pixels_stripes_to_host", "modle_pixels_scc_groups", "modle_pixels_scc",
            "modle_pixels_scc_to_host", "modle_pixels_stripe_profiles", "modle_pixels_stripe_profiles_to_host",
-           "modle_pixels_coarse_stripe_profiles_to_host",
+           "modle_pixels_coarse_stripe_profiles_to_host", "modle_pixels_triangles", "modle_pixels_triangles_to_host",
+           "modle_pixels_coarse_triangles_to_host", "modle_pixels_triangle_cells",
            "modle_pixels_build_caps"]  # every symbol include/modle_pixels.h declares
 # what modle_pixels_build_caps reports of the default build: the workgroups of a stripes launch, the grid's y of
 # the band fill, the workgroups of the band check, the threads of the bin1_offset scan
@@ -215,6 +222,12 @@ def lib():
         lb.modle_pixels_stripe_profiles_to_host.argtypes = shape + prof + [C.POINTER(C.c_void_p), C.c_void_p] + err
         lb.modle_pixels_coarse_stripe_profiles_to_host.argtypes = shape + [C.c_uint64] * 2 + prof + \
             [C.POINTER(C.c_void_p), C.c_void_p] + err
+        tri = [C.c_uint64, C.c_uint64]  # max_width, min_diag
+        lb.modle_pixels_triangles.argtypes = shape + tri + [C.c_void_p, C.c_uint64, C.c_void_p] + err
+        lb.modle_pixels_triangles_to_host.argtypes = shape + tri + [C.POINTER(C.c_void_p), C.c_void_p] + err
+        lb.modle_pixels_coarse_triangles_to_host.argtypes = shape + [C.c_uint64] * 2 + tri + \
+            [C.POINTER(C.c_void_p), C.c_void_p] + err
+        lb.modle_pixels_triangle_cells.argtypes = [C.c_uint64] * 3 + [u64p]
         lb.modle_pixels_build_caps.argtypes = [u64p]
         lb.modle_pixels_build_caps.restype = None
         for name in EXPORTS:
@@ -839,6 +852,124 @@ def stripe_calls(profiles, n_valid, max_offset, lengths, min_diag, half_width=0,
     return calls
 
 
+TRIANGLE_RULE = ("no null pointer, 0 < nrows <= ncols, 1 <= max_width <= nrows, max_width <= 65535, "
+                 "out_words >= max_width * ncols, an 8-byte aligned output that does not overlap the band")
+
+
+def _triangle_args(max_width, min_diag):
+    """(W, d0) of a triangle call; what is no uint64 is refused here (ctypes would wrap it silently), everything
+    else by the library"""
+    w, d0 = int(max_width), int(min_diag)
+    if not all(0 <= x < 1 << 64 for x in (w, d0)):
+        raise PixelsError(ERR_ARG, f"triangles: max_width, min_diag = {w}, {d0} are no uint64")
+    return w, d0
+
+
+def triangle_cells(ncols, max_width, min_diag=0):
+    """the number of pixels behind every word of the triangle table, numpy uint64 [max_width, ncols]
+    (modle_pixels_triangle_cells; no device is needed): (w' - d0)(w' - d0 + 1) / 2 with w' = min(k + 1, ncols - s),
+    0 when w' <= d0"""
+    ncols = int(ncols)
+    w, d0 = _triangle_args(max_width, min_diag)
+    if not 0 <= ncols < 1 << 63:
+        raise PixelsError(ERR_ARG, f"triangle_cells: ncols = {ncols} is no column count")
+    if not 1 <= w <= MAX_TRIANGLE_WIDTH:  # (before the array is made)
+        raise PixelsError(ERR_ARG, f"triangle_cells: invalid argument (1 <= max_width <= {MAX_TRIANGLE_WIDTH})")
+    out = np.zeros((w, ncols), dtype=np.uint64)
+    rc = lib().modle_pixels_triangle_cells(ncols, w, d0, out.ctypes.data_as(C.POINTER(C.c_uint64)))
+    if rc != 0:
+        raise PixelsError(rc, f"triangle_cells: invalid argument (1 <= max_width <= {MAX_TRIANGLE_WIDTH})")
+    return out
+
+
+def triangle_sums_host(band, nrows, ncols, max_width, min_diag=0):
+    """The triangle table of a band on the host, numpy uint64 [max_width, ncols]: what the tests hold the kernels
+    against, and a way to try a score without a device.  It shares no code with the library.  T[k][s] is the sum of
+    the pixels (a, c), s <= a <= c < min(s + k + 1, ncols), c - a >= min_diag, of the band `band[c * nrows + (c -
+    a)]` (numpy uint32, nrows * ncols words or more).  Formed in uint64, in which the sums are exact (max_width <=
+    MAX_TRIANGLE_WIDTH): per column the running sums down the diagonals, the words that are no pixels (d > c)
+    masked before they are used; those sums read along the matrix rows; their running sums over the widths.
+    ValueError outside 1 <= max_width <= nrows <= ncols."""
+    nrows, ncols, w, d0 = int(nrows), int(ncols), int(max_width), int(min_diag)
+    if not (1 <= w <= nrows <= ncols and w <= MAX_TRIANGLE_WIDTH and d0 >= 0):
+        raise ValueError(f"triangle_sums_host: max_width {w}, min_diag {d0} on a band of {nrows} x {ncols} "
+                         f"(1 <= max_width <= nrows <= ncols, max_width <= {MAX_TRIANGLE_WIDTH})")
+    words = np.asarray(band).reshape(-1)[:nrows * ncols].reshape(ncols, nrows)[:, :w]
+    d, c = np.arange(w, dtype=np.int64)[None, :], np.arange(ncols, dtype=np.int64)[:, None]
+    column = np.cumsum(np.where((d >= d0) & (d <= c), words, 0).astype(np.uint64), axis=1, dtype=np.uint64)
+    added = np.zeros((w, ncols), dtype=np.uint64)  # what width k + 1 adds to width k at start s: column s + k
+    for k in range(w):
+        added[k, :ncols - k] = column[k:, k]
+    return np.cumsum(added, axis=0, dtype=np.uint64)
+
+
+DomainCall = namedtuple("DomainCall", "start end width sum cells score strength")
+
+
+def domain_calls(table, cells, *, gamma=DOMAIN_GAMMA, min_width=DOMAIN_MIN_WIDTH, max_width=None):
+    """The domains of a band from its triangle table (Extractor.triangles_to_host, uint64 [W, ncols]) and
+    triangle_cells of the same call: a list of DomainCall sorted by start, bins [start, end).  The one statement
+    of what a domain is; the project's own rule: modularity against the chromosome's own windows, neither
+    Armatus' gamma exponent nor a p-value.  For a width w = k + 1 (min_width <= w <= max_width; None: W) let n_w =
+    ncols - w + 1 be the number of windows that lie wholly in the chromosome and, where n_w >= 1,
+        mu_w = (the sum of T[k][s] over s < n_w, in Python integers) / n_w      one division, rounded once
+        Q(s, w) = float64(T[k][s]) - gamma * mu_w                               the product rounded, then the difference
+        strength(s, w) = float64(T[k][s]) / mu_w                                NaN where mu_w == 0
+    The called domains are the disjoint windows wholly in the chromosome that maximise the sum of Q; a bin may
+    stay outside every domain at a score of 0.  opt[0] = 0, and for e = 1 .. ncols
+        opt[e] = max(opt[e - 1], max over w <= e of opt[e - w] + Q(e - w, w)),
+    every sum one float64 addition.  Ties: leaving bin e - 1 out wins over any window that only equals it, and of
+    equal windows the shorter wins (a candidate replaces the best so far only when it is strictly larger, the
+    widths taken upwards); the domains are read back from e = ncols.  Everything is IEEE float64 arithmetic in a
+    fixed order, without a fused multiply-add, on integers that a float64 holds exactly: the same table gives the
+    same calls on any machine.  ValueError: a table entry at or above 2^53 (refused, not rounded), shapes that do
+    not agree, min_width < 1, a gamma that is not finite.  `gamma` and `min_width` default to DOMAIN_GAMMA and
+    DOMAIN_MIN_WIDTH: product choices, not measured claims."""
+    tab, cel = np.asarray(table), np.asarray(cells)
+    if tab.ndim != 2 or tab.dtype != np.uint64 or cel.shape != tab.shape:
+        raise ValueError(f"domain_calls: a table of shape {tab.shape} and type {tab.dtype} with cells of shape "
+                         f"{cel.shape} are no uint64 [W, ncols]")
+    width, ncols = tab.shape
+    gamma = float(gamma)
+    lo = int(min_width)
+    hi = min(width if max_width is None else int(max_width), width, ncols)
+    if lo < 1 or not math.isfinite(gamma):
+        raise ValueError(f"domain_calls: min_width {lo} is below 1 or gamma {gamma} is not finite")
+    if tab.size and int(tab.max()) >= 1 << 53:
+        raise ValueError(f"domain_calls: a table entry of {int(tab.max())} is at or above 2^53: a float64 would round it")
+    if hi < lo or ncols == 0:
+        return []
+    ks = np.arange(lo - 1, hi, dtype=np.int64)  # the rows of the table that are asked for, widths upwards
+    # (the exact sum of a row: its words are below 2^53, so numpy's uint64 sum of fewer than 2^11 of them cannot wrap)
+    totals = [sum(int(tab[k, i:min(i + 2047, ncols - k)].sum(dtype=np.uint64)) for i in range(0, ncols - k, 2047))
+              for k in ks]
+    mu = np.array([t / (ncols - k) for t, k in zip(totals, ks)], dtype=np.float64)
+    gmu = gamma * mu
+    opt = np.zeros(ncols + 1, dtype=np.float64)
+    choice = np.zeros(ncols + 1, dtype=np.int64)  # the width of the window that ends at e, 0: bin e - 1 is left out
+    for e in range(1, ncols + 1):
+        fit = ks[:max(0, min(len(ks), e - lo + 1))]  # w = k + 1 <= e
+        best, taken = opt[e - 1], 0
+        if len(fit):
+            cand = opt[e - 1 - fit] + (tab[fit, e - 1 - fit].astype(np.float64) - gmu[:len(fit)])
+            i = int(np.argmax(cand))  # (the first of equal ones: the shortest)
+            if cand[i] > best:
+                best, taken = cand[i], int(fit[i]) + 1
+        opt[e], choice[e] = best, taken
+    calls, e = [], ncols
+    while e > 0:
+        w = int(choice[e])
+        if w == 0:
+            e -= 1
+            continue
+        s, k = e - w, w - 1
+        t, m = int(tab[k, s]), float(mu[k - (lo - 1)])
+        calls.append(DomainCall(s, e, w, t, int(cel[k, s]), float(np.float64(t) - gmu[k - (lo - 1)]),
+                                float(t) / m if m != 0.0 else math.nan))
+        e -= w
+    return calls[::-1]
+
+
 class Extractor:
     """One context of the library on one device (modle_pixels_create)."""
 
@@ -1270,6 +1401,32 @@ class Extractor:
         the offset and `min_diag` count coarse bins, and PROFILE_RULE holds against nrows'"""
         return self.stripe_profiles(d_band, nrows, ncols, max_offset, lengths, min_diag, stream, factor, first_bin, True)
 
+    def triangles_into(self, d_band, nrows, ncols, max_width, min_diag, d_out, out_words, stream=None):
+        """enqueues the triangle table of the band into the caller-owned device array `d_out` (uint64[max_width]
+        [ncols], 8-byte aligned, `out_words` >= max_width * ncols): T[k][s] the sum of the pixels inside the window of
+        k + 1 bins that starts at bin s, without the diagonals below `min_diag`; TRIANGLE_RULE is the accepted call;
+        every word is written (modle_pixels_triangles)"""
+        w, d0 = _triangle_args(max_width, min_diag)
+        _call(self._L.modle_pixels_triangles, self._h, d_band, int(nrows), int(ncols), w, d0, d_out, int(out_words),
+              _stream_ptr(stream))
+
+    def triangles_to_host(self, d_band, nrows, ncols, max_width, min_diag=0, stream=None, factor=1, first_bin=0,
+                          coarse=None):
+        """the table of triangles_into as a numpy uint64[max_width, ncols] the caller owns, formed on the device
+        (modle_pixels_triangles_to_host); domain_calls turns it into calls"""
+        fn, band, shape = self._form("triangles_", d_band, nrows, ncols, factor, first_bin, coarse)
+        w, d0 = _triangle_args(max_width, min_diag)
+        ptr = C.c_void_p()
+        _call(fn, self._h, *band, w, d0, C.byref(ptr), _stream_ptr(stream))
+        nc = shape()[1]
+        return _host_array(ptr.value, w * nc, np.uint64).reshape(w, nc)
+
+    def coarse_triangles_to_host(self, d_band, nrows, ncols, factor, first_bin, max_width, min_diag=0, stream=None):
+        """`triangles_to_host` of the band at `factor` times its bin size, coarsened on the device
+        (modle_pixels_coarse_triangles_to_host): uint64[max_width, ncols'] of coarse_shape; the widths and
+        `min_diag` count coarse bins, and TRIANGLE_RULE holds against nrows'"""
+        return self.triangles_to_host(d_band, nrows, ncols, max_width, min_diag, stream, factor, first_bin, True)
+
 
 def extractor(device=0):
     """the process-wide context of `device`"""
@@ -1475,3 +1632,22 @@ def coarse_stripe_profiles(d_band, nrows, ncols, factor, first_bin, max_offset, 
     coarsened and formed on the device."""
     return extractor(device).coarse_stripe_profiles(d_band, nrows, ncols, factor, first_bin, max_offset, lengths,
                                                     min_diag, stream)
+
+
+def triangles_into(d_band, nrows, ncols, max_width, min_diag, d_out, out_words, stream=None, device=0):
+    """The triangle table of the band at device pointer `d_band`, into the device array `d_out`
+    (uint64[max_width][ncols]); enqueued on `stream`, nothing crosses to the host."""
+    extractor(device).triangles_into(d_band, nrows, ncols, max_width, min_diag, d_out, out_words, stream)
+
+
+def triangles_to_host(d_band, nrows, ncols, max_width, min_diag=0, stream=None, device=0):
+    """The triangle table of the band at device pointer `d_band`: numpy uint64[max_width, ncols], formed on the
+    device."""
+    return extractor(device).triangles_to_host(d_band, nrows, ncols, max_width, min_diag, stream)
+
+
+def coarse_triangles_to_host(d_band, nrows, ncols, factor, first_bin, max_width, min_diag=0, stream=None, device=0):
+    """The triangle table of the band at `factor` times its bin size: numpy uint64[max_width, ncols'], coarsened
+    and formed on the device."""
+    return extractor(device).coarse_triangles_to_host(d_band, nrows, ncols, factor, first_bin, max_width, min_diag,
+                                                      stream)

@@ -179,7 +179,8 @@ struct modle_pixels_handle {
   // The result of the form that waits, whichever ran last (sums_to_host): of _insulation_to_host n_windows rows of
   // ncols words; of _dot_hist_to_host the table 4 x n_chunks x n_obs; of _pileup_to_host the pile with n_used
   // behind it; of _rescale_to_host pile, area and n_used; of _stripes_to_host two directions of rows(what) rows
-  // of ncols words; of _scc_to_host 11 rows of nrows words; of _stripe_profiles_to_host 2 x K x (2 m + 1) rows of ncols words.
+  // of ncols words; of _scc_to_host 11 rows of nrows words; of _stripe_profiles_to_host 2 x K x (2 m + 1) rows of ncols words;
+  // of _triangles_to_host max_width rows of ncols words.
   GrowBuf<uint64_t, true> sums;
   // the two host lists of _pileup_to_host (bin1, then bin2) and of _rescale_to_host (start, then end) (upload_lists)
   GrowBuf<int64_t> lists;
