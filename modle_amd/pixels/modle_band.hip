@@ -27,10 +27,14 @@
 
 #include "modle_pixels.h"
 #include "pixels_context.h"
+#include "pixels_device.h"
 
 namespace {
 
-using u64 = unsigned long long;
+using modle_pixels_device::u64;
+using modle_pixels_device::wave_max;
+using modle_pixels_device::wave_min;
+using modle_pixels_device::wave_sum;
 
 constexpr unsigned kBandCols = MODLE_PIXELS_BAND_TILE_COLS;    // columns of a tile of band_fill
 constexpr unsigned kBandDiags = MODLE_PIXELS_BAND_TILE_DIAGS;  // diagonals of a tile
@@ -70,11 +74,6 @@ __device__ inline bool at_or_beyond(int64_t id, int64_t off, uint64_t x) {
   return rel(id, off, &r) && r >= x;
 }
 
-__device__ inline u64 wave_sum(u64 v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  return v;
-}
-
 __global__ __launch_bounds__(kCheckThreads) void band_check(const int64_t* __restrict__ bin1,
                                                             const int64_t* __restrict__ bin2,
                                                             const int32_t* __restrict__ count, uint64_t n, uint64_t nrows,
@@ -108,11 +107,9 @@ __global__ __launch_bounds__(kCheckThreads) void band_check(const int64_t* __res
     const u64 s = wave_sum(acc[k]);
     if ((threadIdx.x & 63) == 0 && s != 0) atomicAdd(&words[k], s);
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    mx = max(mx, __shfl_down(mx, o));
-    bad_order = min(bad_order, static_cast<u64>(__shfl_down(bad_order, o)));
-    bad_sign = min(bad_sign, static_cast<u64>(__shfl_down(bad_sign, o)));
-  }
+  mx = wave_max(mx);
+  bad_order = wave_min(bad_order);
+  bad_sign = wave_min(bad_sign);
   if ((threadIdx.x & 63) == 0) {
     if (mx != 0) atomicMax(&words[kMaxCount], static_cast<u64>(mx));
     if (bad_order != kNone) atomicMin(&words[kBadOrder], bad_order);

@@ -50,6 +50,7 @@
 
 #include "modle_pixels.h"
 #include "pixels_context.h"
+#include "pixels_device.h"
 
 namespace {
 
@@ -63,35 +64,8 @@ constexpr int kSeg = 8;                                  // threads per line of 
 static_assert(kPitch % 2 == 1, "an odd pitch keeps both passes free of bank conflicts");
 static_assert(kSeg * (kT + 2 * kMaxW) <= static_cast<int>(kDotThreads), "a thread per segment");
 
-typedef unsigned long long u64;
-
-// one pass of the summed-area table: line l < S (threads l + S * seg), elements base[e * se], e < S
-__device__ __forceinline__ void scan_pass(u64* sat, int S, int line_stride, int se) {
-  const int t = static_cast<int>(threadIdx.x);
-  const int line = t % S, seg = t / S;
-  const int L = (S + kSeg - 1) / kSeg;
-  const bool active = seg < kSeg;
-  u64* base = sat + kPitch + 1 + line * line_stride;  // cell (0, 0) of the tile is A[1][1]
-  const int e0 = min(S, seg * L), e1 = min(S, e0 + L);
-  if (active) {
-    u64 acc = 0;
-    for (int e = e0; e < e1; ++e) {
-      acc += base[e * se];
-      base[e * se] = acc;
-    }
-  }
-  __syncthreads();
-  u64 off = 0;
-  if (active)
-    for (int s = 1; s <= seg; ++s) {
-      const int end = min(S, s * L);  // one past the last element of segment s - 1
-      if (end > min(S, (s - 1) * L)) off += base[(end - 1) * se];
-    }
-  __syncthreads();
-  if (active && seg > 0)
-    for (int e = e0; e < e1; ++e) base[e * se] += off;
-  __syncthreads();
-}
+using modle_pixels_device::sat_scan_pass;
+using modle_pixels_device::u64;
 
 // What the tile feeds (the template argument of the kernel): the fold decision and / or the sums
 // (modle_pixels_dots), the lambda-chunk histogram (modle_pixels_dot_hist), the threshold decision
@@ -199,6 +173,8 @@ __global__ __launch_bounds__(kDotThreads) void pixels_dots(const uint32_t* __res
       sat[t * kPitch] = 0;
     }
     // tile cell (r, c) is matrix cell (i0 - w + r, j0 - w + c); lane <-> r descending, d ascending
+    // (build_table of modle_scc.hip is not merged with this: its tile is a rectangle across the main diagonal,
+    // loaded an item per thread; only the two scan passes are shared)
     const int nchunk = (S + 63) / 64;
     const int items = S * nchunk;
     for (int it0 = wv * kUnroll; it0 < items; it0 += kDotWaves * kUnroll) {
@@ -218,8 +194,9 @@ __global__ __launch_bounds__(kDotThreads) void pixels_dots(const uint32_t* __res
       }
     }
     __syncthreads();
-    scan_pass(sat, S, 1, kPitch);  // along r, a line per c
-    scan_pass(sat, S, kPitch, 1);  // along c, a line per r
+    // (S <= kT + 2 * kMaxW, which the pass is told: a line has kSeg segments whatever w is)
+    sat_scan_pass<kDotThreads, kPitch, kSeg, kT + 2 * kMaxW>(sat, S, S, 1, kPitch);  // along r, a line per c
+    sat_scan_pass<kDotThreads, kPitch, kSeg, kT + 2 * kMaxW>(sat, S, S, kPitch, 1);  // along c, a line per r
   }
 
   const uint64_t plane = static_cast<uint64_t>(nrows) * static_cast<uint64_t>(ncols);

@@ -29,8 +29,12 @@
 
 #include "modle_pixels.h"
 #include "pixels_context.h"
+#include "pixels_device.h"
 
 namespace {
+
+using modle_pixels_device::wave_last;
+using modle_pixels_device::wave_scan;
 
 constexpr unsigned kBins = 64;    // bins of one workgroup = lanes of a wave
 constexpr unsigned kWaves = 4;    // waves of a workgroup, each with an LDS row of its own
@@ -78,6 +82,8 @@ __global__ __launch_bounds__(kBins * kWaves) void pixels_insulation(const uint32
     wave_sync();  // the row's readers of the column before are done
     if (lane == 0) row[0] = 0;
     unsigned long long carry = 0;
+    // (modle_profiles.hip has a loop like this one; only the scan inside is shared: there the prefix is picked
+    // at cut points by a shuffle, here every word of it goes to the LDS row)
     for (unsigned c0 = 0; c0 < dn; c0 += kUnroll * 64) {
       uint32_t v[kUnroll];
 #pragma unroll
@@ -88,15 +94,10 @@ __global__ __launch_bounds__(kBins * kWaves) void pixels_insulation(const uint32
 #pragma unroll
       for (unsigned u = 0; u < kUnroll; ++u) {
         if (c0 + u * 64 >= dn) break;  // (the same in every lane)
-        unsigned long long x = v[u];   // inclusive scan over the wave
-#pragma unroll
-        for (unsigned s = 1; s < 64; s *= 2) {
-          const unsigned long long y = __shfl_up(x, s);
-          if (lane >= s) x += y;
-        }
+        const unsigned long long x = wave_scan(v[u], lane);
         const unsigned d = c0 + u * 64 + lane;
         if (d < dn) row[d + 1] = carry + x;
-        carry += __shfl(x, 63);
+        carry += wave_last(x);
       }
     }
     wave_sync();  // the row is whole

@@ -39,6 +39,8 @@ constexpr unsigned kDepth = 256;   // band words (d) of one tile = threads of a 
 constexpr unsigned kUnroll = 4;    // columns in flight, reduced together
 static_assert(kCols % kUnroll == 0 && kDepth % 64 == 0, "whole groups of columns, whole waves");
 
+// (not a reduction of pixels_device.h: those leave their result in lane 0, and here every lane of a group of 16
+// needs it, four columns at a time)
 __device__ __forceinline__ unsigned long long xor_lanes(unsigned long long x, int mask) {
   return __shfl_xor(x, mask);
 }

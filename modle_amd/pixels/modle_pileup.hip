@@ -25,10 +25,11 @@
 
 #include "modle_pixels.h"
 #include "pixels_context.h"
+#include "pixels_device.h"
 
 namespace {
 
-using u64 = unsigned long long;
+using modle_pixels_device::u64;
 
 constexpr unsigned kBatch = 256;         // lanes of a workgroup = anchors of a batch
 constexpr unsigned kPileupGroups = 256;  // workgroups at most: MODLE_PIXELS_PILEUP_GROUPS

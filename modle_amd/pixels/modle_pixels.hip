@@ -24,8 +24,13 @@
 
 #include "modle_pixels.h"
 #include "pixels_context.h"
+#include "pixels_device.h"
 
 namespace {
+
+using modle_pixels_device::wave_max;
+using modle_pixels_device::wave_scan;
+using modle_pixels_device::wave_sum;
 
 constexpr unsigned kCountCols = 64;     // columns of one pixels_count tile
 constexpr unsigned kCountDepth = 256;  // band words (d) of one pixels_count tile
@@ -71,10 +76,8 @@ __global__ __launch_bounds__(kCountThreads) void pixels_count(const uint32_t* __
     const unsigned int c = slots[s];
     if (c != 0) atomicAdd(&row_count[row0 + static_cast<int64_t>(s)], static_cast<unsigned long long>(c));
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    sum += __shfl_down(sum, o);
-    mx = max(mx, __shfl_down(mx, o));
-  }
+  sum = wave_sum(sum);
+  mx = wave_max(mx);
   if ((threadIdx.x & 63) == 0) {
     if (sum != 0) atomicAdd(&stats->sum, sum);
     if (mx != 0) atomicMax(&stats->max_count, mx);
@@ -85,22 +88,18 @@ __global__ __launch_bounds__(kCountThreads) void pixels_count(const uint32_t* __
 __global__ __launch_bounds__(kScanThreads) void pixels_scan(unsigned long long* __restrict__ offsets,
                                                             uint64_t ncols,
                                                             DeviceStats* __restrict__ stats) {
-  __shared__ unsigned long long wave_sum[kScanThreads / 64];
+  __shared__ unsigned long long wave_total[kScanThreads / 64];
   const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned long long carry = 0;
   for (uint64_t base = 0; base < ncols; base += kScanThreads) {
     const uint64_t idx = base + threadIdx.x;
     const unsigned long long v = idx < ncols ? offsets[idx] : 0;
-    unsigned long long x = v;
-    for (unsigned o = 1; o < 64; o <<= 1) {
-      const unsigned long long y = __shfl_up(x, o);
-      if (lane >= o) x += y;
-    }
-    if (lane == 63) wave_sum[wave] = x;
+    const unsigned long long x = wave_scan(v, lane);
+    if (lane == 63) wave_total[wave] = x;
     __syncthreads();
     unsigned long long before = 0, total = 0;
     for (unsigned w = 0; w < kScanThreads / 64; ++w) {
-      const unsigned long long s = wave_sum[w];
+      const unsigned long long s = wave_total[w];
       if (w < wave) before += s;
       total += s;
     }

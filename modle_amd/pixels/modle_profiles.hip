@@ -41,15 +41,19 @@
 
 #include "modle_pixels.h"
 #include "pixels_context.h"
+#include "pixels_device.h"
 
 namespace {
 
-using u64 = unsigned long long;
+using modle_pixels_device::grid_of;
+using modle_pixels_device::group_id;
+using modle_pixels_device::u64;
+using modle_pixels_device::wave_last;
+using modle_pixels_device::wave_scan;
 
 constexpr unsigned kBins = 64;    // rows of a workgroup of the horizontal kernel = lanes of a wave
 constexpr unsigned kWaves = 4;    // waves of a workgroup
 constexpr unsigned kUnroll = 4;   // loads in flight per lane
-constexpr unsigned kGridX = 1u << 20;  // a grid's x; the workgroups beyond go to y (no loop strides by the grid)
 constexpr unsigned kMaxOffset = MODLE_PIXELS_MAX_PROFILE_OFFSET;
 constexpr unsigned kMaxLengths = MODLE_PIXELS_MAX_PROFILE_LENGTHS;
 static_assert((kMaxLengths + 1) * (2 * kMaxOffset + 1) <= 128, "two cut points per lane of the vertical kernel");
@@ -66,8 +70,6 @@ __device__ __forceinline__ uint32_t cut_at(const Cuts& cuts, unsigned i) {
   for (unsigned k = 1; k <= kMaxLengths; ++k) v = i == k ? cuts.b[k] : v;
   return v;
 }
-
-__device__ __forceinline__ u64 group_id() { return static_cast<u64>(blockIdx.y) * gridDim.x + blockIdx.x; }
 
 // out: direction 0, [K][W][ncols]
 __global__ __launch_bounds__(64 * kWaves) void profiles_vertical(const uint32_t* __restrict__ band, u64 nrows,
@@ -96,6 +98,8 @@ __global__ __launch_bounds__(64 * kWaves) void profiles_vertical(const uint32_t*
 
   const uint32_t* col = band + q * nrows;
   u64 carry = 0, base = dlo;
+  // (modle_insulation.hip has a loop like this one; only the scan inside is shared: there every word of the prefix
+  // goes to LDS, here it is picked at the cut points by a shuffle)
   for (u64 s0 = dlo; s0 < dtop; s0 += kUnroll * 64) {  // (the same in every lane)
     uint32_t v[kUnroll];
 #pragma unroll
@@ -106,12 +110,7 @@ __global__ __launch_bounds__(64 * kWaves) void profiles_vertical(const uint32_t*
 #pragma unroll
     for (unsigned u = 0; u < kUnroll; ++u) {
       if (s0 + u * 64 >= dtop) break;  // (the same in every lane)
-      u64 x = v[u];                    // inclusive scan over the wave
-#pragma unroll
-      for (unsigned sh = 1; sh < 64; sh *= 2) {
-        const u64 y = __shfl_up(x, sh);
-        if (lane >= sh) x += y;
-      }
+      const u64 x = wave_scan(v[u], lane);
       const u64 excl = carry + x - v[u];  // the sum of the words dlo .. base + lane - 1
 #pragma unroll
       for (unsigned s = 0; s < 2; ++s) {
@@ -119,7 +118,7 @@ __global__ __launch_bounds__(64 * kWaves) void profiles_vertical(const uint32_t*
         const u64 y = __shfl(excl, static_cast<int>(at & 63));
         if (at < 64) p[s] = y;
       }
-      carry += __shfl(x, 63);
+      carry += wave_last(x);
       base += 64;
     }
   }
@@ -235,11 +234,6 @@ bool bad_request(uint64_t nrows, uint64_t m, const uint64_t* lengths, uint64_t n
 }
 
 uint64_t words_of(uint64_t m, uint64_t n_lengths, uint64_t ncols) { return 2 * n_lengths * (2 * m + 1) * ncols; }
-
-dim3 grid_of(uint64_t groups) {
-  const uint64_t x = std::min<uint64_t>(groups, kGridX);
-  return dim3(static_cast<unsigned>(x), static_cast<unsigned>((groups + x - 1) / x));
-}
 
 // enqueues the kernels on checked arguments
 int profiles_impl(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, uint64_t ncols, uint64_t m,

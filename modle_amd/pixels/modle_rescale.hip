@@ -27,10 +27,11 @@
 
 #include "modle_pixels.h"
 #include "pixels_context.h"
+#include "pixels_device.h"
 
 namespace {
 
-using u64 = unsigned long long;
+using modle_pixels_device::u64;
 
 constexpr unsigned kLanes = 1024;                         // lanes of a workgroup of pixels_rescale
 constexpr unsigned kMaxR = MODLE_PIXELS_MAX_RESCALE;      // grid side at most

@@ -27,8 +27,7 @@
 
 namespace {
 
-using u32 = uint32_t;
-using u64 = uint64_t;
+using u32 = uint32_t;  // (64-bit words are uint64_t here: the short name of pixels_device.h is unsigned long long)
 
 constexpr unsigned kThreads = 256;  // lanes of a workgroup
 constexpr unsigned kIters = 8;      // words of a lane: 2048 contiguous words per workgroup
@@ -42,8 +41,8 @@ static_assert(MODLE_PIXELS_SAMPLE_TIER1_TRIALS % 4 == 0, "tier 1 ends at a Philo
 __host__ __device__ inline void philox4x32_10(u32 c0, u32 c1, u32 c2, u32 c3, u32 k0, u32 k1, u32 out[4]) {
 #pragma unroll
   for (int r = 0; r < 10; ++r) {
-    const u64 p0 = static_cast<u64>(0xD2511F53u) * c0;
-    const u64 p1 = static_cast<u64>(0xCD9E8D57u) * c2;
+    const uint64_t p0 = static_cast<uint64_t>(0xD2511F53u) * c0;
+    const uint64_t p1 = static_cast<uint64_t>(0xCD9E8D57u) * c2;
     const u32 n0 = static_cast<u32>(p1 >> 32) ^ c1 ^ k0;
     const u32 n1 = static_cast<u32>(p1);
     const u32 n2 = static_cast<u32>(p0 >> 32) ^ c3 ^ k1;
@@ -112,23 +111,23 @@ __device__ __forceinline__ u32 sample_word(const Draw& g, u32 I, u32 J, u32 n, u
   return kept;
 }
 
-__global__ __launch_bounds__(kThreads) void pixels_sample(const u32* __restrict__ band, u32 nrows, u64 words,
+__global__ __launch_bounds__(kThreads) void pixels_sample(const u32* __restrict__ band, u32 nrows, uint64_t words,
                                                           u32 id0, Draw g, int mode, u32 step_j, u32 step_d,
                                                           u32* __restrict__ kept_out, u32* __restrict__ rest_out) {
   const unsigned lane = threadIdx.x & 63;
-  const u64 base = static_cast<u64>(blockIdx.x) * (kThreads * kIters);
+  const uint64_t base = static_cast<uint64_t>(blockIdx.x) * (kThreads * kIters);
   // word base + threadIdx.x is (j, d); `words` = nrows * ncols is the trailing word
-  const u64 jb = base / nrows;  // (the same in every lane)
+  const uint64_t jb = base / nrows;  // (the same in every lane)
   const u32 x = static_cast<u32>(base - jb * nrows) + threadIdx.x;  // < 2^24 + 256
   const u32 q = x / nrows;
-  u64 j = jb + q;
+  uint64_t j = jb + q;
   u32 d = x - q * nrows;
 
   u32 n[kIters], I[kIters], J[kIters];
   bool inside[kIters];
 #pragma unroll
   for (unsigned u = 0; u < kIters; ++u) {
-    const u64 w = base + u * kThreads + threadIdx.x;
+    const uint64_t w = base + u * kThreads + threadIdx.x;
     inside[u] = w <= words;
     const bool pixel = w < words && d <= j;
     n[u] = pixel ? band[w] : 0u;
@@ -147,7 +146,7 @@ __global__ __launch_bounds__(kThreads) void pixels_sample(const u32* __restrict_
     else
       kept = mode == kKeepAll ? n[u] : 0u;
     if (inside[u]) {
-      const u64 w = base + u * kThreads + threadIdx.x;
+      const uint64_t w = base + u * kThreads + threadIdx.x;
       if (kept_out != nullptr) kept_out[w] = kept;
       if (rest_out != nullptr) rest_out[w] = n[u] - kept;
     }
@@ -156,13 +155,13 @@ __global__ __launch_bounds__(kThreads) void pixels_sample(const u32* __restrict_
 
 using modle_pixels_detail::set_err;
 
-constexpr u64 kTwo32 = 1ull << 32;
+constexpr uint64_t kTwo32 = 1ull << 32;
 
-Draw make_draw(u64 seed, u32 salt, u64 threshold) {
+Draw make_draw(uint64_t seed, u32 salt, uint64_t threshold) {
   return Draw{static_cast<u32>(seed), static_cast<u32>(seed >> 32), salt, static_cast<u32>(threshold)};
 }
 
-int mode_of(u64 threshold) { return threshold == 0 ? kKeepNone : threshold == kTwo32 ? kKeepAll : kDrawMode; }
+int mode_of(uint64_t threshold) { return threshold == 0 ? kKeepNone : threshold == kTwo32 ? kKeepAll : kDrawMode; }
 
 constexpr const char* kRule =
     "(0 < nrows <= ncols, an output, threshold <= 2^32, a band, its stats; no output overlaps the band or the other)";
@@ -175,7 +174,8 @@ int refuse(const char* who, uint64_t nrows, uint64_t ncols, int64_t bin_offset, 
     set_err(err, errlen, std::string(who) + ": invalid argument " + kRule);
     return MODLE_PIXELS_ERR_ARG;
   }
-  if (bin_offset < 0 || static_cast<u64>(bin_offset) > kTwo32 || static_cast<u64>(bin_offset) + ncols > kTwo32) {
+  if (bin_offset < 0 || static_cast<uint64_t>(bin_offset) > kTwo32 ||
+      static_cast<uint64_t>(bin_offset) + ncols > kTwo32) {
     set_err(err, errlen, std::string(who) + ": the bin ids bin_offset .. bin_offset + ncols - 1 do not fit 32 bits");
     return MODLE_PIXELS_ERR_RANGE;
   }
@@ -194,7 +194,7 @@ int sample_impl(modle_pixels_handle* h, const uint32_t* d_band, uint64_t nrows, 
                 uint64_t threshold, uint64_t seed, uint32_t salt, uint32_t* d_kept, uint32_t* d_rest,
                 hipStream_t stream, char* err, size_t errlen) {
   PIX_TRY(hipSetDevice(h->device));
-  const u64 words = nrows * ncols;  // and the trailing word
+  const uint64_t words = nrows * ncols;  // and the trailing word
   const dim3 grid(static_cast<unsigned>(words / (kThreads * kIters) + 1));
   hipLaunchKernelGGL(pixels_sample, grid, dim3(kThreads), 0, stream, d_band, static_cast<u32>(nrows), words,
                      static_cast<u32>(bin_offset), make_draw(seed, salt, threshold), mode_of(threshold),
@@ -236,7 +236,7 @@ extern "C" int modle_pixels_sample(modle_pixels_handle* h, const uint32_t* d_ban
                   h == nullptr || d_band == nullptr || stats == nullptr || (d_kept == nullptr && d_rest == nullptr),
                   err, errlen);
   if (rc != MODLE_PIXELS_OK) return rc;
-  const u64 nb = modle_pixels_detail::band_bytes(nrows, ncols);
+  const uint64_t nb = modle_pixels_detail::band_bytes(nrows, ncols);
   if (modle_pixels_detail::any_overlap({{d_kept, nb}, {d_rest, nb}}, {{d_band, nb}})) {
     set_err(err, errlen, "modle_pixels_sample: an output overlaps the band or the other output");
     return MODLE_PIXELS_ERR_ARG;

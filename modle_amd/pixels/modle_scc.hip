@@ -23,7 +23,7 @@
 //           words -- cell (R, C) is band[max(R, C) * nrows + |R - C|], so a box crosses the main diagonal
 //           through the symmetry; a cell outside the matrix, or on a diagonal no box of the strip reaches,
 //           counts 0 and is not loaded --, turns it into a summed-area table with the two segmented scan
-//           passes of modle_dots.hip, and every lane takes the box sums of its four rows into registers: four
+//           passes modle_dots.hip uses too (pixels_device.h), and every lane takes the box sums of its four rows into registers: four
 //           reads each.  Then the table is rebuilt for B in the same LDS and the products are formed.  Consecutive
 //           lanes read consecutive table words, and the pitch of 137 words is odd, so both scan passes and the
 //           box reads are free of bank conflicts.
@@ -43,10 +43,13 @@
 
 #include "modle_pixels.h"
 #include "pixels_context.h"
+#include "pixels_device.h"
 
 namespace {
 
-using u64 = unsigned long long;
+using modle_pixels_device::add128;
+using modle_pixels_device::sat_scan_pass;
+using modle_pixels_device::u64;
 
 constexpr int kStrip = 64;                                      // strata of a workgroup = lanes of a wave
 constexpr unsigned kThreads = 512;
@@ -71,12 +74,9 @@ static_assert(kMaxTileCols <= static_cast<int>(kThreads) && kMaxTileRows <= stat
               "a thread per line of a scan pass");
 static_assert(kMeetWords <= kSatWords, "the waves meet in the table's LDS");
 
-__device__ __forceinline__ void add128(u64& lo, u64& hi, u64 x_lo, u64 x_hi) {
-  lo += x_lo;
-  hi += x_hi + (lo < x_lo ? 1u : 0u);
-}
-
 // the eleven words of a stratum, in the order of the output rows
+// (Mom / Acc<kWhat> of modle_stripes.hip are not merged with this: either layout is its pinned output rows, 11 and 9
+// words, and n is counted differently; only add128 underneath is shared)
 struct Acc {
   u64 w[kWords];
   __device__ __forceinline__ void zero() {
@@ -158,40 +158,11 @@ __global__ __launch_bounds__(kThreads) void scc_stream(const uint32_t* __restric
   leave_partial(acc, meet, partial);
 }
 
-// One pass of the summed-area table: `nlines` lines of `nelem` elements, element e of line l at
-// base[l * line_stride + e * se]; a line goes to `segs` threads, which scan their segments in place, read the
-// totals of the segments before theirs and add them (modle_dots.hip: scan_pass, for a rectangle).
-__device__ __forceinline__ void scan_pass(u64* sat, int nlines, int nelem, int line_stride, int se) {
-  const int t = static_cast<int>(threadIdx.x);
-  const int segs = min(static_cast<int>(kThreads) / nlines, kMaxSeg);
-  const int line = t % nlines, seg = t / nlines;
-  const int L = (nelem + segs - 1) / segs;
-  const bool active = seg < segs;
-  u64* base = sat + kPitch + 1 + line * line_stride;  // cell (0, 0) of the tile is A[1][1]
-  const int e0 = min(nelem, seg * L), e1 = min(nelem, e0 + L);
-  if (active) {
-    u64 acc = 0;
-    for (int e = e0; e < e1; ++e) {
-      acc += base[e * se];
-      base[e * se] = acc;
-    }
-  }
-  __syncthreads();
-  u64 off = 0;
-  if (active)
-    for (int s = 1; s <= seg; ++s) {
-      const int end = min(nelem, s * L);  // one past the last element of segment s - 1
-      if (end > min(nelem, (s - 1) * L)) off += base[(end - 1) * se];
-    }
-  __syncthreads();
-  if (active && seg > 0)
-    for (int e = e0; e < e1; ++e) base[e * se] += off;
-  __syncthreads();
-}
-
 // The summed-area table of the tile of `band` whose cell (0, 0) is matrix cell (r0, c0): A[r + 1][c + 1] = the
 // sum of the cells (<= r, <= c), r < sr, c < sc.  Only the cells on the signed diagonals dlo .. dhi (column
 // minus row) are loaded; the others count 0.  Ends with a barrier.
+// (The loader of modle_dots.hip is not merged with this: its tile is square, loaded a column per wave with the lanes
+// reversed and without the symmetry; only the two scan passes are shared.)
 __device__ __forceinline__ void build_table(u64* sat, const uint32_t* __restrict__ band, int64_t nrows,
                                             int64_t ncols, int64_t r0, int64_t c0, int sr, int sc, int64_t dlo,
                                             int64_t dhi) {
@@ -219,8 +190,8 @@ __device__ __forceinline__ void build_table(u64* sat, const uint32_t* __restrict
     }
   }
   __syncthreads();
-  scan_pass(sat, sc, sr, 1, kPitch);  // along r, a line per c
-  scan_pass(sat, sr, sc, kPitch, 1);  // along c, a line per r
+  sat_scan_pass<kThreads, kPitch, kMaxSeg>(sat, sc, sr, 1, kPitch);  // along r, a line per c
+  sat_scan_pass<kThreads, kPitch, kMaxSeg>(sat, sr, sc, kPitch, 1);  // along c, a line per r
 }
 
 // grid (strips, G), h >= 1; two workgroups on a CU are four waves on a SIMD

@@ -33,10 +33,13 @@
 
 #include "modle_pixels.h"
 #include "pixels_context.h"
+#include "pixels_device.h"
 
 namespace {
 
-using u64 = unsigned long long;
+using modle_pixels_device::add128;
+using modle_pixels_device::u64;
+using modle_pixels_device::wave_sum;
 
 constexpr unsigned kBins = 64;      // stripes of a workgroup of the horizontal kernel = lanes of a wave
 constexpr unsigned kWaves = 4;      // waves of a workgroup
@@ -48,14 +51,11 @@ constexpr unsigned kMaxGrid = MODLE_STRIPES_MAX_GRID;
 constexpr uint64_t kAll = MODLE_PIXELS_STRIPES_MOMENTS | MODLE_PIXELS_STRIPES_MASKED | MODLE_PIXELS_STRIPES_RANKS;
 
 // the nine words of a stripe pair, in the order of the output rows
+// (Acc of modle_scc.hip is not merged with this: either layout is its pinned output rows, 9 and 11 words, and n is
+// counted differently; only add128 underneath is shared)
 struct Mom {
   u64 w[kMomRows];
 };
-
-__device__ __forceinline__ void add128(u64& lo, u64& hi, u64 x_lo, u64 x_hi) {
-  lo += x_lo;
-  hi += x_hi + (lo < x_lo ? 1u : 0u);
-}
 
 __device__ __forceinline__ void mom_zero(Mom& m) {
 #pragma unroll
@@ -137,6 +137,8 @@ __global__ __launch_bounds__(64 * kWaves) void stripes_vertical(const uint32_t* 
 #pragma unroll
       for (unsigned u = 0; u < kUnroll; ++u) acc.add(va[u], vb[u]);
     }
+    // (not pixels_device.h's wave_sum: the words of a 128-bit sum merge with a carry, so a step shifts the whole
+    // struct, word by word, and merges it)
 #pragma unroll
     for (unsigned s = 32; s > 0; s >>= 1) {
       Acc<kWhat> o;
@@ -260,9 +262,7 @@ __global__ __launch_bounds__(64 * kWaves) void stripes_ranks(const uint32_t* __r
       r[2] += ra * rb;
     }
 #pragma unroll
-    for (unsigned s = 32; s > 0; s >>= 1)
-#pragma unroll
-      for (unsigned k = 0; k < kRankRows; ++k) r[k] += __shfl_down(r[k], s);
+    for (unsigned k = 0; k < kRankRows; ++k) r[k] = wave_sum(r[k]);
     if ((tid & 63) == 0)
 #pragma unroll
       for (unsigned k = 0; k < kRankRows; ++k) part[tid >> 6][k] = r[k];

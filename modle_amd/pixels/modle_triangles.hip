@@ -38,21 +38,21 @@
 
 #include "modle_pixels.h"
 #include "pixels_context.h"
+#include "pixels_device.h"
 
 namespace {
 
-using u64 = unsigned long long;
+using modle_pixels_device::grid_of;
+using modle_pixels_device::group_id;
+using modle_pixels_device::u64;
 
 constexpr unsigned kCols = 64;         // columns of a workgroup of `columns` = lanes of its wave
 constexpr unsigned kStride = kCols + 1;  // words of a tile row
 constexpr unsigned kLoads = 8;         // loads in flight per lane of `columns`
 constexpr unsigned kWalk = 16;         // loads in flight per lane of `walk`
-constexpr unsigned kGridX = 1u << 20;  // a grid's x; the workgroups beyond go to y (no loop strides by the grid)
 constexpr u64 kMaxWidth = MODLE_PIXELS_MAX_TRIANGLE_WIDTH;
 // W (W + 1) / 2 pixels below 2^32 stay below 2^64
 static_assert(kMaxWidth * (kMaxWidth + 1) / 2 <= 0xFFFFFFFFFFFFFFFFull / 0xFFFFFFFFull, "the sums must not wrap");
-
-__device__ __forceinline__ u64 group_id() { return static_cast<u64>(blockIdx.y) * gridDim.x + blockIdx.x; }
 
 // out[d][c - d] = P(c, d) for the columns c of the workgroup, 0 <= c - d < ncols, d < W
 __global__ __launch_bounds__(kCols) void triangles_columns(const uint32_t* __restrict__ band, u64 nrows, u64 ncols,
@@ -129,11 +129,6 @@ constexpr const char* kRule =
 // what every entry point refuses of the width on a band of `nrows`
 bool bad_width(uint64_t nrows, uint64_t max_width) {
   return max_width == 0 || max_width > nrows || max_width > kMaxWidth;
-}
-
-dim3 grid_of(uint64_t groups) {
-  const uint64_t x = std::min<uint64_t>(groups, kGridX);
-  return dim3(static_cast<unsigned>(x), static_cast<unsigned>((groups + x - 1) / x));
 }
 
 // enqueues the kernels on checked arguments
